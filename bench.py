@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: InsTaG face-branch train step at 512x512 with 100k Gaussians (config C3).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one full train step on one synthetic frame per rank: PMF + UMF (6 grid encodes + MLPs)
@@ -12,9 +12,18 @@ region.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N rank processes itself (before this process
 touches a GPU); under torch.distributed.run it must agree with WORLD_SIZE.
 
-Timing: after W warm-up steps the trainer state is snapshotted; `--windows` (default 5) windows of exactly K steps each
-start from that same state, each bracketed by barrier + synchronize on both sides and reduced with MAX over ranks; the
-reported `ms_per_step` / `value` are those of the MEDIAN window (all windows are listed).
+Timing: W warm-up steps, then exactly K timed steps, bracketed by barrier + synchronize on both sides and reduced with MAX
+over ranks.  With `--windows` > 1 the trainer state is snapshotted after the warm-up and every window of exactly K steps
+starts from that same state; the reported `ms_per_step` / `value` are those of the MEDIAN window (all windows are listed).
+
+A plain run measures the headline figure and nothing else.  `--full` adds everything else the benchmark measures: five
+windows by default, per-kernel durations and rooflines (an instrumented pass of their own), the rendered-targets,
+host-frames and density-control workloads and the CPU oracle baseline.
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the last timed step handed its caller -- its loss and L1
+term and the trained state it updated (every per-Gaussian parameter, both motion networks, the densification
+statistics) -- as DIR/<name>.npy (float32; float64 for integer arrays).  The inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -183,6 +192,41 @@ def cpu_baseline(n_gaussians, size, sh_degree, budget_s=30.0):
                       f"figure to set beside it is raster_fwd_bwd_ms_per_frame, not value"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(trainer, out_dir, limit=DUMP_LIMIT_BYTES):
+    """The arrays the last step handed its caller -> out_dir/<name>.npy: trainer.last's loss and L1 term, and the state
+    the step updated in place (the per-Gaussian parameters, the UMF and PMF weights, the densification statistics).
+    If they exceed `limit` bytes, a fixed seeded sample of the Gaussians' rows is written (gaussians.sample_rows.npy
+    holds the row indices)."""
+    import numpy as np
+    import torch
+    g = trainer.g
+    arrays = {"loss": trainer.last["loss"], "l1": trainer.last["l1"]}
+    arrays.update({f"gaussians.{k}": v for k, v in g._p.items()})
+    arrays.update({f"umf.{k}": v for k, v in trainer.motion_net.named_parameters()})
+    if g.neural_motion_grid is not None:
+        arrays.update({f"pmf.{k}": v for k, v in g.neural_motion_grid.named_parameters()})
+    arrays.update({"stats.xyz_gradient_accum": g.xyz_gradient_accum, "stats.denom": g.denom,
+                   "stats.max_radii2D": g.max_radii2D})
+    n = g.num_points
+    per_row = sum(v[0].numel() * 8 for v in arrays.values() if v.dim() and v.shape[0] == n)
+    other = sum(v.numel() * 8 for v in arrays.values() if not (v.dim() and v.shape[0] == n))
+    rows = None
+    if per_row * n + other > limit:
+        keep = max(1, (limit - other - 8 * n) // per_row)
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {k: (v.detach()[rows.to(v.device)] if v.dim() and v.shape[0] == n else v) for k, v in arrays.items()}
+        arrays["gaussians.sample_rows"] = rows
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        v = v.detach().cpu()
+        v = v.double() if not v.is_floating_point() or v.dtype == torch.float64 else v.float()
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.numpy())
+    return len(arrays)
+
+
 def spawn_ranks(n):
     """`--gpus n` without a launcher: start the n rank processes.  Runs BEFORE this process touches a GPU (counting
     devices does not initialise one on this image) and never re-executes a process that has."""
@@ -225,7 +269,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps, each from the same state")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps, each from the same state (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel durations and rooflines, the "
+                         "secondary workloads (see the --no-* options) and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, L1, trained state) as DIR/<name>.npy")
     ap.add_argument("--gaussians", type=int, default=100000)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--sh-degree", type=int, default=1)
@@ -239,12 +289,14 @@ def main():
                     help="skip the reference_schedule workload (700 iterations across density-control events)")
     ap.add_argument("--schedule-iterations", type=int, default=700)
     ap.add_argument("--all-workloads", action="store_true",
-                    help="several ranks: also run the secondary workloads (by default a multi-rank run measures the "
-                         "headline workload only: its line must not depend on the extras)")
+                    help="several ranks with --full: also run the secondary workloads (by default a multi-rank run "
+                         "measures the headline workload only: its line must not depend on the extras)")
     ap.add_argument("--allow-eager-fallback", action="store_true",
                     help="several ranks: if the step cannot be captured next to the collective library, time eager "
                          "launches instead of failing (the line then says so in config.execution)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     t_start = time.perf_counter()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -316,8 +368,9 @@ def main():
     L = _lib.lib()
     import ctypes as C
 
-    def measure(stable, windows):
-        """-> dict(ms windows, median, kernels, R, graph info) of one workload, from a freshly built trainer."""
+    def measure(stable, windows, dump_dir=None):
+        """-> dict(ms windows, median, kernels, R, graph info) of one workload, from a freshly built trainer.  Without
+        --full the kernels / R / MLP figures (an instrumented pass of their own) are not measured."""
         trainer = build_trainer(N, dev, sh_degree=args.sh_degree, seed=0, densify=False)
         frames = make_frames(trainer, stable)
 
@@ -344,12 +397,14 @@ def main():
                 use_graph = False
         run(args.warmup)
         torch.cuda.synchronize()
-        snap = trainer.snapshot()
+        # (one window and nothing after it: no state to return to)
+        snap = trainer.snapshot() if windows > 1 or args.full else None
         if graph is not None:
             graph.plan.clear()
         times = []
         for w in range(windows):
-            trainer.restore(snap)
+            if snap is not None:
+                trainer.restore(snap)
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
@@ -372,6 +427,13 @@ def main():
             overflow = graph.check_overflow()
             if overflow:
                 raise SystemExit(f"instance capacity exceeded during the timed region: {overflow}")
+        if dump_dir is not None and rank == 0:
+            log(f"wrote {dump_outputs(trainer, dump_dir)} arrays of the last timed step to {dump_dir}")
+        if not args.full:
+            trainer._drop_graph()
+            diff_gauss.set_capacity_plan(None)
+            return dict(times=times, median=statistics.median(times), kern={}, R=0, graph=use_graph, why=why, mlp=None,
+                        entries=None, durations_from=None)
         # Per-kernel durations IN REPLAY MODE: the step is captured once more with every launch of the C ABI bracketed by
         # external event-record nodes (instag_prof_graph_*: HIP events on the stream the kernel is launched on, inside the
         # graph) and replayed the same number of steps from the SAME restored state; the kernels run next to the same
@@ -542,10 +604,10 @@ def main():
                     recapture_ms=1e3 * getattr(trainer, "recapture_seconds", 0.0),
                     density_ms=1e3 * getattr(trainer, "density_seconds", 0.0), start=start)
 
-    if world > 1 and not args.all_workloads:
+    if not args.full or (world > 1 and not args.all_workloads):
         args.no_stable_targets = args.no_host_frames = args.no_schedule = True
     log(f"config: {N} Gaussians, {size}x{size}, world {world}")
-    main_run = measure(False, max(1, args.windows))
+    main_run = measure(False, max(1, args.windows), args.dump_outputs)
     stable_run = None
     if not args.no_stable_targets:
         stable_run = measure(True, max(1, min(3, args.windows)))
@@ -637,17 +699,21 @@ def main():
                        "execution": "hipGraph replay" if main_run["graph"] else
                                     ("eager" + (f" (graph capture failed: {main_run['why']})" if main_run["why"] else "")),
                        "timing": f"median of {len(main_run['times'])} windows of {args.steps} steps, each from the "
-                                 "same snapshotted state"},
+                                 "same snapshotted state" if len(main_run["times"]) > 1 else
+                                 f"one window of {args.steps} steps after {args.warmup} warm-up steps"},
             "windows_ms_per_step": [round(1e3 * t / args.steps, 4) for t in main_run["times"]],
-            "roofline": roofline,
-            "roofline_valu": valu.get(dom) and dict(valu[dom], other={k: v for k, v in valu.items() if v and k != dom},
-                                                    walked=ent),
-            "kernel_durations_from": main_run["durations_from"],
-            "secondary_rooflines": secondary,
-            "kernels_us": {k: round(v["avg_us"], 2) for k, v in kern.items()},
-            "raster_fwd_bwd_ms_per_frame": round(sum(v["total_ms"] for k, v in kern.items()
-                                                     if k not in NON_RASTER) / args.steps, 4),
         }
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                "roofline_valu": valu.get(dom) and dict(valu[dom], other={k: v for k, v in valu.items()
+                                                                          if v and k != dom}, walked=ent),
+                "kernel_durations_from": main_run["durations_from"],
+                "secondary_rooflines": secondary,
+                "kernels_us": {k: round(v["avg_us"], 2) for k, v in kern.items()},
+                "raster_fwd_bwd_ms_per_frame": round(sum(v["total_ms"] for k, v in kern.items()
+                                                         if k not in NON_RASTER) / args.steps, 4),
+            })
         if stable_run is not None:
             sm = stable_run["median"]
             out["stable_targets"] = {
@@ -693,7 +759,7 @@ def main():
             out["c3_phase_with_density_control"] = schedule_entry(
                 c3_run, "the headline's step (C3 phase in every iteration) with density control on (densify / prune every "
                         "100 iterations), rendered targets, end to end including the re-captures")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("timing the CPU oracle baseline (bounded sample)")
             out["cpu_baseline"] = cpu_baseline(N, size, args.sh_degree, args.cpu_budget)
         print(json.dumps(out), flush=True)

@@ -3,7 +3,7 @@
 # .ab_prev/<basename>, put there before the call: git show HEAD:<file> > .ab_prev/<basename>) and with the working-tree version, twice each, same box
 mkdir -p gpurun_out
 f=$1; b=$(basename $f)
-B="python bench.py --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
+B="python bench.py --full --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
 cp $f .ab_prev/new_$b
 run() {
   python -m instag_amd.build > /dev/null 2>&1 || { echo "build failed ($1)"; return; }

@@ -2,7 +2,7 @@
 # usage: r03_flag_variants.sh <source stem> "<flags A>" "<flags B>" ...  -> rebuild that source with each flag set, raster tests, bench
 mkdir -p gpurun_out
 stem=$1; shift
-B="python bench.py --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
+B="python bench.py --full --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
 for cfg in "$@"; do
   export INSTAG_EXTRA_FLAGS_${stem}="$cfg"
   python -m instag_amd.build > /dev/null 2>&1 || { echo "build failed: $cfg"; continue; }

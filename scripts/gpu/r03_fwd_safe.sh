@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: r03_fwd_safe.sh "<flags>" ...  -> like r03_fwd_variants.sh, every bench under its own short timeout, progress kept
 mkdir -p gpurun_out
-B="python bench.py --steps 30 --warmup 5 --windows 3 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
+B="python bench.py --full --steps 30 --warmup 5 --windows 3 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
 i=0
 for cfg in "$@"; do
   i=$((i+1))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: r03_fwd_variants.sh "<flags A>" "<flags B>" ...  -> rebuild raster_blend with each flag set, short bench (no tests)
 mkdir -p gpurun_out
-B="python bench.py --steps 30 --warmup 5 --windows 3 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
+B="python bench.py --full --steps 30 --warmup 5 --windows 3 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
 for cfg in "$@"; do
   export INSTAG_EXTRA_FLAGS_raster_blend="$cfg"
   python -m instag_amd.build > /dev/null 2>&1 || { echo "build failed: $cfg"; continue; }

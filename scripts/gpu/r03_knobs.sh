@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: r03_knobs.sh "ENV1=a ENV2=b" "ENV1=c" ...   -> one short bench per setting
 mkdir -p gpurun_out
-B="python bench.py --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
+B="python bench.py --full --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
 for setting in "$@"; do
   out=$(env $setting $B 2>/dev/null | tail -1)
   python - "$setting" "$out" <<'PY'

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of weight-gradient kernel variants: rebuild mlp.hip with the given -D flags on the box, test, bench
 mkdir -p gpurun_out
-B="python bench.py --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
+B="python bench.py --full --steps 30 --warmup 5 --windows 5 --no-stable-targets --no-cpu-baseline --no-host-frames --no-schedule"
 for cfg in "$@"; do
   export INSTAG_EXTRA_FLAGS_mlp="$cfg"
   python -m instag_amd.build > /dev/null 2>&1 || { echo "build failed: $cfg"; continue; }
