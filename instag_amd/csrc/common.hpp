@@ -89,6 +89,10 @@ struct GeomLayout {
   size_t dsort_digit_base;                  // [4][256]
   size_t dsort_partials;                    // [blocks][4][256]
   size_t scan_state, scan_state_words;      // u64 [1 + blocks] as 32-bit words; cleared by the preprocess kernel
+  // one-pass instance sort: [preprocess blocks][tiles] partial tile counts (row stride = tiles, room for WIDE_DIGITS),
+  // per-tile totals, per-tile dropped counts (right behind scan_state: cleared with it, pre_zero_words in all)
+  size_t tile_partials, tile_total, tile_dropped, pre_zero_words;
+  uint32_t pre_blocks;
   uint32_t dsort_blocks, dkey_blocks;
   size_t total;
 };
@@ -104,7 +108,8 @@ ImageLayout image_layout(int32_t H, int32_t W);
 struct BinningLayout {
   // instance sort: keys K0 = keys_unsorted -> (ktmp) -> keys, values likewise (pair form only)
   size_t keys_unsorted, vals_unsorted, keys, vals, ktmp, vtmp, gid_unsorted, point_list;
-  size_t tsort_zero, tsort_zero_words;      // [16 words: tickets][3 passes x blocks x 256 look-back words]
+  size_t tsort_zero, tsort_zero_words;      // [16 words: tickets][3 passes x blocks x 256 look-back words], or for the
+                                            // one-pass sort [16][wide blocks x (tiles + 1) / 2 look-back word pairs]
   size_t tsort_digit_base;                  // [3][256]
   size_t tsort_partials;                    // [1024][3][256]
   size_t sort_count;                        // u32: instances actually binned

@@ -180,7 +180,13 @@ GeomLayout geom_layout(int32_t N) {
   L.dkey_blocks = depth_key_blocks((int32_t)n);
   L.dsort_partials = o; o = align_up(o + (size_t)L.dkey_blocks * 4 * 256 * sizeof(uint32_t), 256);
   L.scan_state_words = 2 * (1 + (size_t)div_up<size_t>(n, 1024));
-  L.scan_state = o; o = align_up(o + L.scan_state_words * sizeof(uint32_t), 256);
+  L.scan_state = o;
+  L.tile_dropped = o + L.scan_state_words * sizeof(uint32_t);
+  L.pre_zero_words = L.scan_state_words + WIDE_DIGITS;
+  o = align_up(o + L.pre_zero_words * sizeof(uint32_t), 256);
+  L.tile_total = o; o = align_up(o + WIDE_DIGITS * sizeof(uint32_t), 256);
+  L.pre_blocks = preprocess_blocks((int32_t)n);
+  L.tile_partials = o; o = align_up(o + (size_t)L.pre_blocks * WIDE_DIGITS * sizeof(uint32_t), 256);
   L.total = o;
   return L;
 }
@@ -213,7 +219,8 @@ BinningLayout binning_layout(int64_t R, int32_t H, int32_t W) {
   L.point_list = o; o = align_up(o + r * sizeof(uint32_t), 256);
   L.tsort_blocks = sort_blocks((uint32_t)r, SORT_IPT_TILE);
   // [tickets + look-back words][seg_count + pad][row flags, two sets]: one region, cleared by the duplicate kernel
-  const size_t sort_words = 16 + (size_t)3 * L.tsort_blocks * 256;
+  const size_t wide_words = wide_tiles((int)tiles) ? (size_t)tile_pass_blocks((uint32_t)r) * 2 * ((tiles + 1) / 2) : 0;
+  const size_t sort_words = 16 + std::max((size_t)3 * L.tsort_blocks * 256, wide_words);
   L.row_flag_stride = align_up(r, 16);
   L.seg_slots = r / SEG_LEN + tiles + 2;
   L.tsort_zero_words = sort_words + 4 + 2 * L.row_flag_stride / 4 + 8 * tiles + L.seg_slots;
@@ -301,7 +308,8 @@ static int per_gaussian_stage(const instag_raster_args* a, const Camera& c, char
   }
   if (int e = launch_preprocess(c, a, (float*)(gb + L.rec2d), (float*)(gb + L.cov3d), tiles_touched,
                                 (uint32_t*)(gb + L.flags), (float*)(gb + L.cull_thr), radii,
-                                (uint32_t*)(gb + L.scan_state), (uint32_t)L.scan_state_words, s)) return e;
+                                (uint32_t*)(gb + L.tile_partials), (uint32_t*)(gb + L.scan_state),
+                                (uint32_t)L.pre_zero_words, s)) return e;
   if (lane != nullptr) INSTAG_CHECK_HIP(hipStreamWaitEvent(s, lane->join, 0));
   return launch_scan_counts(a->N, (const uint32_t*)(gb + L.order), tiles_touched, point_offsets,
                             (uint64_t*)(gb + L.scan_state), s);
@@ -382,12 +390,29 @@ static int forward_tail(const instag_raster_args* a, void* geom, size_t geom_byt
   uint32_t* partials = (uint32_t*)(bb + BL.tsort_partials);
   uint32_t* sort_count = (uint32_t*)(bb + BL.sort_count);
   const bool packed = use_packed_keys(R, tiles);
-  if (R > 0 && a->N > 0) {
+  // Which instance sort: with packed keys (fewer than 2,047 tiles) ONE pass by the whole tile id that also writes the
+  // lists and the ranges; otherwise digit passes of at most 8 bits, then the range kernel.  INSTAG_TILE_SORT=passes
+  // forces the second (tests compare the two).  Both give the one stable order, bit for bit.
+  const char* e_sort = getenv("INSTAG_TILE_SORT");
+  const bool one_pass = packed && !(e_sort && strcmp(e_sort, "passes") == 0);
+  if (R > 0 && a->N > 0 && one_pass) {
+    const WideTileCounts wide{(const uint32_t*)(gb + GL.tile_partials), (int)GL.pre_blocks,
+                              (uint32_t*)(gb + GL.tile_total), (uint32_t*)(gb + GL.tile_dropped)};
+    const TilePasses none{0, 0, {0, 0, 0}};
+    if (int e = launch_duplicate(c, (float*)(gb + GL.rec2d), (const uint32_t*)(gb + GL.order),
+                                 (const uint32_t*)(gb + GL.point_offsets), (const uint32_t*)(gb + GL.flags),
+                                 (const float*)(gb + GL.cull_thr), K0, V0, gid_u, (uint32_t)R, ranges, packed, status,
+                                 sort_count, none, partials, zero, (uint32_t)BL.tsort_zero_words, &wide, s)) return e;
+    ProfScope p(K_SORT, s);
+    if (int e = launch_tile_pass(K0, gid_u, K1, V1, point_list, ranges, sort_count, (uint32_t)R, tiles,
+                                 (const uint32_t*)(gb + GL.tile_total), (const uint32_t*)(gb + GL.tile_dropped), zero,
+                                 (uint64_t*)(zero + 16), s)) return e;
+  } else if (R > 0 && a->N > 0) {
     const TilePasses tp = tile_passes(tiles);
     if (int e = launch_duplicate(c, (float*)(gb + GL.rec2d), (const uint32_t*)(gb + GL.order),
                                  (const uint32_t*)(gb + GL.point_offsets), (const uint32_t*)(gb + GL.flags),
                                  (const float*)(gb + GL.cull_thr), K0, V0, gid_u, (uint32_t)R, ranges, packed, status,
-                                 sort_count, tp, partials, zero, (uint32_t)BL.tsort_zero_words, s)) return e;
+                                 sort_count, tp, partials, zero, (uint32_t)BL.tsort_zero_words, nullptr, s)) return e;
     {
       ProfScope p(K_SORT, s);
       if (int e = launch_hist_reduce(partials, (int)duplicate_blocks(a->N), tp.npass, HIST_SLICES, digit_base, s))

@@ -13,6 +13,18 @@ struct Camera {  // kernel-side view of instag_raster_args' scalar part
 
 Camera make_camera(const instag_raster_args* a);
 
+// Instance sort as ONE pass whose digit is the whole tile id (raster_sort.hip: tile_pass_kernel).  Its per-tile counts
+// come from the preprocess kernel (per-block partials [blocks][tiles], plain stores), summed per tile by the duplicate
+// kernel into `total`; in capacity mode with overflow the duplicate kernel also counts the instances it drops per tile
+// into `dropped` (zero at its launch: cleared by the preprocess kernel).  Instances binned into tile t = total - dropped.
+constexpr int WIDE_DIGITS = 2048;
+inline bool wide_tiles(int tiles) { return tiles < (1 << 11) - 1; }
+struct WideTileCounts {
+  const uint32_t* partials;
+  int n_partials;
+  uint32_t *total, *dropped;
+};
+
 // digit p of a tile id = (tile >> (p * bits_per)) & ((1 << nbits[p]) - 1): the instance sort's passes (<= 8 bits each)
 struct TilePasses {
   int npass, bits_per, nbits[3];
@@ -28,9 +40,12 @@ inline TilePasses tile_passes(int tiles) {
 }
 
 // raster_preprocess.hip (built with -ffp-contract=off: bit-exact against the oracle)
+// tile_partials: [blocks of 256 Gaussians][tiles] kept-instance counts per tile (written when wide_tiles(tiles), else
+// unused; may be null)
 int launch_preprocess(const Camera& c, const instag_raster_args* a, float* rec2d, float* cov3d,
                       uint32_t* tiles_touched, uint32_t* flags, float* cull_thr, int32_t* radii,
-                      uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s);
+                      uint32_t* tile_partials, uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s);
+uint32_t preprocess_blocks(int32_t N);
 uint32_t depth_key_blocks(int32_t N);
 int launch_depth_keys(const Camera& c, const float* means3D, uint32_t* depth_key, uint32_t* partials,
                       uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s);
@@ -41,7 +56,7 @@ int launch_duplicate(const Camera& c, float* rec2d, const uint32_t* order,
                      const uint32_t* point_offsets, const uint32_t* flags, const float* cull_thr, uint32_t* keys,
                      uint32_t* vals, uint32_t* gid_unsorted, uint32_t capacity, int32_t* ranges,
                      bool packed, int32_t* status, uint32_t* sort_count, const TilePasses& tp, uint32_t* partials,
-                     uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s);
+                     uint32_t* zero_words, uint32_t n_zero_words, const WideTileCounts* wide, hipStream_t s);
 int launch_ranges(int64_t R, const uint32_t* count_ptr, const uint32_t* keys_sorted, uint32_t* slots_sorted,
                   const uint32_t* gid_unsorted, uint32_t* point_list, int32_t* ranges, uint32_t ntiles, bool packed,
                   hipStream_t s);
@@ -59,6 +74,11 @@ int read_sort_stalls(uint32_t* host_out, hipStream_t s, bool synchronize);
 int clear_sort_stalls(hipStream_t s);
 uint32_t* sort_stalls_device_ptr();
 int launch_hist_reduce(const uint32_t* partials, int nblk, int npass, int slices, uint32_t* out, hipStream_t s);
+uint32_t tile_pass_blocks(uint32_t count_max);
+int launch_tile_pass(const uint32_t* keys_in, const uint32_t* gid_unsorted, uint32_t* keys_out, uint32_t* slots_out,
+                     uint32_t* point_list, int32_t* ranges, const uint32_t* count_ptr, uint32_t count_max, int tiles,
+                     const uint32_t* tile_total, const uint32_t* tile_dropped, uint32_t* ticket, uint64_t* lookback,
+                     hipStream_t s, uint64_t* stamps = nullptr);
 int launch_scan_counts(int N, const uint32_t* order, const uint32_t* tiles_touched, uint32_t* point_offsets,
                        uint64_t* state, hipStream_t s);
 

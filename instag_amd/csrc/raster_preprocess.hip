@@ -66,14 +66,11 @@ struct PreIn {
   const float *means3D, *shs, *colors, *opac, *scales, *rots, *cov3Dp, *extra, *shs_rest;
 };
 
-__global__ void __launch_bounds__(256)
-preprocess_kernel(Camera c, PreIn in, float* __restrict__ rec2d, float* __restrict__ cov3d,
-                  uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ flags_out,
-                  float* __restrict__ cull_thr, int32_t* __restrict__ radii,
-                  uint32_t* __restrict__ zero_words, uint32_t n_zero_words) {
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  // housekeeping for a later launch: the look-back state of the instance-offset scan starts out zero
-  for (uint32_t k = (uint32_t)g; k < n_zero_words; k += gridDim.x * 256u) zero_words[k] = 0u;
+// one Gaussian; s_tc (LDS, or null): the block's kept-instance count per tile
+__device__ __forceinline__ void
+preprocess_one(int g, const Camera& c, const PreIn& in, float* __restrict__ rec2d, float* __restrict__ cov3d,
+               uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ flags_out,
+               float* __restrict__ cull_thr, int32_t* __restrict__ radii, uint32_t* s_tc) {
   if (g >= c.N) return;
   radii[g] = 0;
   tiles_touched[g] = 0;
@@ -244,7 +241,12 @@ preprocess_kernel(Camera c, PreIn in, float* __restrict__ rec2d, float* __restri
   int kept = 0;
   if (thr >= 0.0f) {
     for (int ty_ = rminy; ty_ < rmaxy; ++ty_)
-      for (int tx_ = rminx; tx_ < rmaxx; ++tx_) kept += tile_kept(pix_x, pix_y, conA, conB, conC, thr, tx_, ty_) ? 1 : 0;
+      for (int tx_ = rminx; tx_ < rmaxx; ++tx_) {
+        if (tile_kept(pix_x, pix_y, conA, conB, conC, thr, tx_, ty_)) {
+          ++kept;
+          if (s_tc != nullptr) atomicAdd(&s_tc[ty_ * c.grid_x + tx_], 1u);
+        }
+      }
   }
   cull_thr[g] = thr;
   radii[g] = radius;
@@ -259,6 +261,34 @@ preprocess_kernel(Camera c, PreIn in, float* __restrict__ rec2d, float* __restri
   rec[1] = make_float4(conC, op, cr, cg);
   rec[2] = make_float4(cb, tz, nvx, nvy);
   rec[3] = make_float4(nvz, (c.E > 0 && in.extra) ? in.extra[g] : 0.0f, 0.0f, __uint_as_float(rect));
+}
+
+// One thread per Gaussian.  With tile_partials (an image of fewer than 2,047 tiles) the block also counts its kept
+// instances per tile -- the histogram of the one-pass instance sort, which does not depend on depth order -- in LDS and
+// writes it out with plain stores (row blockIdx.x of [blocks][tiles]): no global counter to clear, and this kernel runs
+// beside the depth sort, off the chain the instance sort waits on.
+__global__ void __launch_bounds__(256)
+preprocess_kernel(Camera c, PreIn in, float* __restrict__ rec2d, float* __restrict__ cov3d,
+                  uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ flags_out,
+                  float* __restrict__ cull_thr, int32_t* __restrict__ radii, uint32_t* __restrict__ tile_partials,
+                  uint32_t* __restrict__ zero_words, uint32_t n_zero_words) {
+  __shared__ uint32_t s_tc[WIDE_DIGITS];
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  const int tiles = c.grid_x * c.grid_y;
+  const bool hist = tile_partials != nullptr;       // (uniform: the launcher passes null unless wide_tiles(tiles))
+  // housekeeping for later launches: the look-back state of the instance-offset scan and the duplicate kernel's
+  // dropped-instance counters start out zero
+  for (uint32_t k = (uint32_t)g; k < n_zero_words; k += gridDim.x * 256u) zero_words[k] = 0u;
+  if (hist) {
+    for (int k = threadIdx.x; k < tiles; k += 256) s_tc[k] = 0u;
+    __syncthreads();
+  }
+  preprocess_one(g, c, in, rec2d, cov3d, tiles_touched, flags_out, cull_thr, radii, hist ? s_tc : nullptr);
+  if (hist) {
+    __syncthreads();
+    uint32_t* out = tile_partials + (size_t)blockIdx.x * tiles;
+    for (int k = threadIdx.x; k < tiles; k += 256) out[k] = s_tc[k];
+  }
 }
 
 // Depth keys of ALL Gaussians (the float bits of view-space z, the same expression as in preprocess_kernel: this TU is
@@ -311,7 +341,9 @@ depth_key_kernel(int N, const float* __restrict__ view, const float* __restrict_
 // The kernel also prepares the instance sort that follows it: per-block histograms of the tile-id digits (LDS integer
 // atomics, written out with plain stores: the sort needs no zero-initialised global counters), the clearing of the
 // sort's tickets / look-back words and of the tile ranges, the number of instances to sort (a device word: unused
-// capacity is neither padded nor sorted) and, in capacity mode, the status words.
+// capacity is neither padded nor sorted) and, in capacity mode, the status words.  For the one-pass tile sort
+// (`wide`) it writes no digit histograms: it sums the preprocess kernel's per-tile partials instead and, when the
+// capacity overflows, counts the instances it drops per tile.
 constexpr int DUP_LANES = 16;
 constexpr int DUP_PER_BLOCK = 256 / DUP_LANES;
 
@@ -322,8 +354,10 @@ duplicate_kernel(int N, int ngroups, int grid_x, float* __restrict__ rec2d, cons
                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ gid_unsorted,
                  uint32_t capacity, int32_t* __restrict__ ranges, uint32_t nranges, int packed,
                  int32_t* __restrict__ status, uint32_t* __restrict__ sort_count, TilePasses tp,
-                 uint32_t* __restrict__ partials, uint32_t* __restrict__ zero_words, uint32_t n_zero_words) {
+                 uint32_t* __restrict__ partials, uint32_t* __restrict__ zero_words, uint32_t n_zero_words,
+                 WideTileCounts wide) {
   __shared__ uint32_t s_dh[3][256];
+  __shared__ uint32_t s_red[256];
   const uint32_t gtid = blockIdx.x * 256u + threadIdx.x;
   const uint32_t total = gridDim.x * 256u;
   for (int k = threadIdx.x; k < 3 * 256; k += 256) (&s_dh[0][0])[k] = 0u;
@@ -353,6 +387,34 @@ duplicate_kernel(int N, int ngroups, int grid_x, float* __restrict__ rec2d, cons
   // housekeeping that used to be memset nodes: tile ranges start out empty, the sort's tickets / look-back words zero
   for (uint32_t k = gtid; k < nranges; k += total) ranges[k] = 0;
   for (uint32_t k = gtid; k < n_zero_words; k += total) zero_words[k] = 0u;
+  const bool wide_sort = wide.total != nullptr;
+  if (wide_sort) {
+    // the one-pass instance sort's tile totals: the preprocess kernel's partials summed per tile, 16 tiles per round of
+    // a block, 16 slices of the partials per tile (thread = slice * 16 + tile), the slices added in order
+    const int ntiles = (int)(nranges / 2), tl = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    for (int t0 = blockIdx.x * 16; t0 < ntiles; t0 += gridDim.x * 16) {
+      const int t = t0 + tl;
+      uint32_t sum = 0;
+      for (int j0 = sl; j0 < wide.n_partials; j0 += 16 * 8) {
+        uint32_t h[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int j = j0 + 16 * k;
+          h[k] = (t < ntiles && j < wide.n_partials) ? wide.partials[(size_t)j * ntiles + t] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) sum += h[k];
+      }
+      s_red[threadIdx.x] = sum;
+      __syncthreads();
+      if (sl == 0 && t < ntiles) {
+        uint32_t tot = 0;
+        for (int k = 0; k < 16; ++k) tot += s_red[k * 16 + tl];
+        wide.total[t] = tot;
+      }
+      __syncthreads();
+    }
+  }
   __syncthreads();
 
   const int q = threadIdx.x % DUP_LANES;
@@ -375,7 +437,7 @@ duplicate_kernel(int N, int ngroups, int grid_x, float* __restrict__ rec2d, cons
       float* rec = rec2d + (size_t)g * REC_FLOATS;
       // (also for a dropped Gaussian: the backward recognises it by offset + count > capacity)
       if (q == 0) rec[R_OFFSET] = __uint_as_float(off);
-      if (fits) {
+      if (fits || wide_sort) {
         const uint32_t rect = __float_as_uint(rec[R_RECT]);
         rminx = (int)(rect & 1023u); rminy = (int)((rect >> 10) & 1023u); rw = (int)(rect >> 20);
         ntiles = rw * (int)(flags[g] >> 16);
@@ -388,7 +450,10 @@ duplicate_kernel(int N, int ngroups, int grid_x, float* __restrict__ rec2d, cons
       const int y = rminy + t / rw, x = rminx + t % rw;
       const bool kept = t < ntiles && tile_kept(px, py, A, B, C, thr, x, y);
       const uint32_t bits = (uint32_t)(__builtin_amdgcn_ballot_w64(kept) >> grp_shift) & ((1u << DUP_LANES) - 1u);
-      if (kept) {
+      if (kept && !fits) {
+        // capacity mode, overflow (flagged): a dropped instance; the one-pass sort's totals counted it, take it out
+        atomicAdd(&wide.dropped[y * grid_x + x], 1u);
+      } else if (kept) {
         const uint32_t o = off + (uint32_t)__builtin_popcount(bits & ((1u << q) - 1u));
         const uint32_t tile = (uint32_t)(y * grid_x + x);
         if (packed) {
@@ -503,15 +568,18 @@ Camera make_camera(const instag_raster_args* a) {
   return c;
 }
 
+uint32_t preprocess_blocks(int32_t N) { return (uint32_t)div_up(std::max(N, 1), 256); }
+
 int launch_preprocess(const Camera& c, const instag_raster_args* a, float* rec2d, float* cov3d,
                       uint32_t* tiles_touched, uint32_t* flags, float* cull_thr, int32_t* radii,
-                      uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s) {
+                      uint32_t* tile_partials, uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s) {
   if (c.N == 0) return INSTAG_OK;
   PreIn in{a->means3D, a->shs, a->colors_precomp, a->opacities, a->scales, a->rotations,
            a->cov3Ds_precomp, a->extra_attrs, a->shs_rest};
+  if (!wide_tiles(c.grid_x * c.grid_y)) tile_partials = nullptr;
   ProfScope p(K_PREPROCESS, s);
-  preprocess_kernel<<<div_up(c.N, 256), 256, 0, s>>>(c, in, rec2d, cov3d, tiles_touched, flags, cull_thr, radii,
-                                                     zero_words, n_zero_words);
+  preprocess_kernel<<<preprocess_blocks(c.N), 256, 0, s>>>(c, in, rec2d, cov3d, tiles_touched, flags, cull_thr, radii,
+                                                           tile_partials, zero_words, n_zero_words);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
@@ -533,14 +601,15 @@ int launch_duplicate(const Camera& c, float* rec2d, const uint32_t* order,
                      const uint32_t* point_offsets, const uint32_t* flags, const float* cull_thr, uint32_t* keys,
                      uint32_t* vals, uint32_t* gid_unsorted, uint32_t capacity, int32_t* ranges,
                      bool packed, int32_t* status, uint32_t* sort_count, const TilePasses& tp, uint32_t* partials,
-                     uint32_t* zero_words, uint32_t n_zero_words, hipStream_t s) {
+                     uint32_t* zero_words, uint32_t n_zero_words, const WideTileCounts* wide, hipStream_t s) {
   if (c.N == 0) return INSTAG_OK;
+  const WideTileCounts w = wide != nullptr ? *wide : WideTileCounts{nullptr, 0, nullptr, nullptr};
   ProfScope p(K_DUPLICATE, s);
   const int ngroups = div_up(c.N, DUP_PER_BLOCK);
   duplicate_kernel<<<duplicate_blocks(c.N), 256, 0, s>>>(c.N, ngroups, c.grid_x, rec2d, order, point_offsets, flags,
                                                          cull_thr, keys, vals, gid_unsorted, capacity, ranges,
                                                          (uint32_t)(2 * c.grid_x * c.grid_y), packed ? 1 : 0, status,
-                                                         sort_count, tp, partials, zero_words, n_zero_words);
+                                                         sort_count, tp, partials, zero_words, n_zero_words, w);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }

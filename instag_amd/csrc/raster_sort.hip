@@ -1,7 +1,11 @@
 // Stable LSD radix sort passes and the instance-offset scan of the rasterizer's binning stage, written for its two
 // jobs: (1) Gaussians by view depth (32-bit float bits, N keys), (2) instances by tile id (the few bits of the tile
 // index, R keys in depth order).  Both replace rocPRIM calls of round 1 (10 + 12 launches and 5 memset nodes per
-// forward, merge sort below 1 M keys) with 4 + 2 launches and no memset node:
+// forward, merge sort below 1 M keys) with 4 + 1 launches and no memset node.  The instance sort is ONE pass
+// (tile_pass_kernel) whose digit is the whole tile id when the keys are packed (fewer than 2,047 tiles, R < 2^21): its
+// per-tile counts come from the preprocess kernel's partial histograms (summed per tile by the duplicate kernel), and
+// it writes the final lists and the tile ranges itself.  Otherwise -- or with INSTAG_TILE_SORT=passes -- it is 1-2
+// digit passes of at most 8 bits after hist_reduce_kernel, and the range kernel follows.  Common to all passes:
 //
 //   * one launch per digit pass: decoupled look-back over per-(block, digit) counters (flag and count in ONE 32-bit
 //     word, agent-scope relaxed atomics), block order by a ticket drawn at block start, so a block only ever waits for
@@ -9,7 +13,8 @@
 //   * the look-back words and tickets must be zero at launch: they are cleared by the kernel that runs BEFORE the first
 //     pass anyway (depth-key kernel / duplicate kernel), one private set per pass, so nothing is cleared between passes;
 //   * the global digit histograms come from per-block partial histograms written with plain stores by those same
-//     kernels (no global atomics, no zero-initialised counters), summed and scanned by one small launch;
+//     kernels (no global atomics, no zero-initialised counters), summed by the pass itself or by one small launch (the
+//     one tile pass: per-tile counts from the preprocess kernel, summed in the duplicate kernel);
 //   * the number of keys is read from DEVICE memory (capacity mode: the instance count never reaches the host), so
 //     unused capacity is neither padded nor sorted.
 //
@@ -268,6 +273,212 @@ radix_pass_kernel(const uint32_t* __restrict__ keys_in, uint32_t* __restrict__ k
 #undef INSTAG_STAMP
 }
 
+// exclusive scan of one value per thread over the PASS_THREADS threads of the block (s_w: 16 words of LDS); *total: the
+// sum over the block
+__device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t* s_w, uint32_t* total) {
+  constexpr int WAVES = PASS_THREADS / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0, sum = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    const uint32_t x = s_w[w];
+    base += (w < wave) ? x : 0u;
+    sum += x;
+  }
+  *total = sum;
+  return base + inc - v;
+}
+
+// The instance sort in ONE pass: the digit is the whole tile id of a packed key (tile << PACK_SHIFT | slot, fewer than
+// 2,047 tiles), the keys come in depth order, so the stable sort by this digit is the final (tile, depth) order.  The
+// structure is that of radix_pass_kernel (ticket order, wave64 match ranking, decoupled look-back per (block, digit)
+// with flag and count in one word, reorder through LDS) with these differences:
+//   * per-wave digit counters are 16-bit (a block holds TILE_WIDE < 2^16 keys): 16 waves x 2,048 digits = 64 KB of LDS;
+//   * thread t owns digits 2t and 2t + 1: their look-back words are the two halves of ONE 64-bit word, polled together;
+//   * the per-tile totals are not summed from partials here: tile_total - tile_dropped (duplicate kernel) per tile, and
+//     their exclusive scan gives each tile's start -- block 0 writes `ranges` from them (an empty tile keeps (0, 0));
+//   * the scatter writes the final lists: keys, slots (`vals`) and point_list = gid_unsorted[slot].  The slot of the key
+//     at unsorted position o is o itself, so the Gaussian ids are loaded coalesced beside the keys.
+constexpr int TILE_WIDE_IPT = 5;                                  // 5,120 keys per block: 207 blocks for 1.06 M keys
+constexpr int TILE_WIDE = PASS_THREADS * TILE_WIDE_IPT;
+
+__global__ void __launch_bounds__(PASS_THREADS)
+tile_pass_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ gid_unsorted,
+                 uint32_t* __restrict__ keys_out, uint32_t* __restrict__ slots_out, uint32_t* __restrict__ point_list,
+                 int32_t* __restrict__ ranges, const uint32_t* __restrict__ count_ptr, uint32_t count_max, int ntiles,
+                 int nbits, const uint32_t* __restrict__ tile_total, const uint32_t* __restrict__ tile_dropped,
+                 uint32_t* __restrict__ ticket, uint64_t* __restrict__ lookback, int lb_stride,
+                 uint64_t* __restrict__ stamps) {
+  constexpr int IPT = TILE_WIDE_IPT;
+  constexpr int WAVES = PASS_THREADS / 64;
+  constexpr int PAIRS = WIDE_DIGITS / 2;
+  static_assert(PAIRS == PASS_THREADS, "one thread per digit pair");
+  static_assert(2 * TILE_WIDE < 65536, "16-bit digit offsets");
+#define INSTAG_STAMP(k) do { if (stamps != nullptr && threadIdx.x == 0) stamps[(size_t)s_bid * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+  __shared__ uint32_t s_cnt[WAVES][PAIRS];   // per-wave 16-bit digit counts (digit 2p low half, 2p + 1 high half), then
+                                             // the digit's run start in the block + the wave's offset inside the run
+  __shared__ uint32_t s_gbase[WIDE_DIGITS];  // global position of the digit's run minus its start in the block
+  __shared__ uint32_t s_keys[TILE_WIDE];
+  __shared__ uint32_t s_gid[TILE_WIDE];
+  __shared__ uint32_t s_w[WAVES], s_w2[WAVES];
+  __shared__ uint32_t s_bid;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int k = tid; k < WAVES * PAIRS; k += PASS_THREADS) (&s_cnt[0][0])[k] = 0u;
+  if (tid == 0) s_bid = atomicAdd(ticket, 1u);
+  __syncthreads();
+  const uint32_t bid = s_bid;
+  INSTAG_STAMP(0);
+  uint32_t count = count_ptr ? *count_ptr : count_max;
+  count = min(count, count_max);
+  const uint64_t base = (uint64_t)bid * TILE_WIDE;
+  if (base >= count) return;                         // (whole block: bid is uniform)
+  const uint32_t valid = (uint32_t)min((uint64_t)TILE_WIDE, (uint64_t)count - base);
+
+  uint32_t key[IPT], gid[IPT], rank[IPT];
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const uint32_t idx = min((uint32_t)wave * (64 * IPT) + i * 64 + lane, valid - 1u);   // stable order = (wave, i, lane)
+    key[i] = keys_in[base + idx];
+    gid[i] = gid_unsorted[base + idx];
+  }
+  // instances per tile of the two digits this thread owns (0 past the last tile)
+  const int d0 = 2 * tid;
+  uint32_t gt0 = 0, gt1 = 0;
+  if (d0 < ntiles) gt0 = tile_total[d0] - tile_dropped[d0];
+  if (d0 + 1 < ntiles) gt1 = tile_total[d0 + 1] - tile_dropped[d0 + 1];
+  INSTAG_STAMP(1);
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  uint16_t* cnt16 = reinterpret_cast<uint16_t*>(&s_cnt[wave][0]);
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const uint32_t idx = (uint32_t)wave * (64 * IPT) + i * 64 + lane;
+    const bool ok = idx < valid;
+    const uint32_t d = key[i] >> PACK_SHIFT;
+    uint64_t peers = __builtin_amdgcn_ballot_w64(ok);
+    for (int b = 0; b < nbits; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const uint64_t m = __builtin_amdgcn_ballot_w64(bit);
+      peers &= bit ? m : ~m;
+    }
+    const uint32_t prev = ok ? cnt16[d] : 0u;
+    if (ok && lane == __builtin_ctzll(peers)) cnt16[d] = (uint16_t)(prev + (uint32_t)__builtin_popcountll(peers));
+    rank[i] = prev + (uint32_t)__builtin_popcountll(peers & lt_mask);
+  }
+  __syncthreads();
+  INSTAG_STAMP(2);
+  {
+    // the two digits' per-wave counts -> exclusive wave offsets; their runs' starts in the block; their tiles' starts
+    uint32_t wc[WAVES], c0 = 0, c1 = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      wc[w] = s_cnt[w][tid];
+      const uint32_t lo = wc[w] & 0xFFFFu, hi = wc[w] >> 16;
+      wc[w] = c0 | (c1 << 16);
+      c0 += lo;
+      c1 += hi;
+    }
+    uint32_t unused = 0;
+    const uint32_t dstart0 = block_exclusive_scan_1024(c0 + c1, s_w, &unused);
+    const uint32_t dstart1 = dstart0 + c0;
+    uint32_t tsum = 0;
+    const uint32_t gstart0 = block_exclusive_scan_1024(gt0 + gt1, s_w2, &tsum);
+    const uint32_t gstart1 = gstart0 + gt0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) s_cnt[w][tid] = wc[w] + (dstart0 | (dstart1 << 16));
+    // the totals must account for exactly the instances to sort, or the positions below would be wrong: say so (the
+    // stores stay inside [0, count) whatever happens)
+    if (tid == 0 && tsum != count) atomicAdd(&g_sort_stalls, 1u);
+    if (bid == 0) {
+      if (d0 < ntiles) {
+        ranges[2 * d0] = gt0 ? (int32_t)gstart0 : 0;
+        ranges[2 * d0 + 1] = gt0 ? (int32_t)(gstart0 + gt0) : 0;
+      }
+      if (d0 + 1 < ntiles) {
+        ranges[2 * d0 + 2] = gt1 ? (int32_t)gstart1 : 0;
+        ranges[2 * d0 + 3] = gt1 ? (int32_t)(gstart1 + gt1) : 0;
+      }
+    }
+    INSTAG_STAMP(3);
+    // look-back: a digit no instance holds needs none (its prefix is 0 in every block); a block that has not published
+    // yet drew its ticket before this one, so it is running and publishes without waiting for anybody
+    uint32_t excl0 = 0, excl1 = 0;
+    bool done0 = gt0 == 0, done1 = gt1 == 0;
+    if (!(done0 && done1)) {
+      uint64_t* mine = lookback + (size_t)bid * lb_stride + tid;
+      st_agent64(mine, (uint64_t)(LB_PARTIAL | c0) | ((uint64_t)(LB_PARTIAL | c1) << 32));
+      uint32_t b = bid;
+      while (b > 0 && !(done0 && done1)) {
+        uint64_t st[LB_CHUNK];
+#pragma unroll
+        for (int j = 0; j < LB_CHUNK; ++j)
+          st[j] = (uint32_t)j < b ? ld_agent64(lookback + (size_t)(b - 1 - j) * lb_stride + tid) : 0ull;
+#pragma unroll
+        for (int j = 0; j < LB_CHUNK; ++j) {
+          if ((uint32_t)j < b && !(done0 && done1)) {
+            const uint64_t* p = lookback + (size_t)(b - 1 - j) * lb_stride + tid;
+            auto waiting = [&](uint64_t v) {
+              return (!done0 && ((uint32_t)v & LB_FLAGS) == 0u) || (!done1 && ((uint32_t)(v >> 32) & LB_FLAGS) == 0u);
+            };
+            for (int polls = 0; waiting(st[j]) && polls < SPIN_LIMIT; ++polls) {
+              __builtin_amdgcn_s_sleep(1);
+              st[j] = ld_agent64(p);
+            }
+            if (waiting(st[j])) atomicAdd(&g_sort_stalls, 1u);             // gave up: the result is wrong, say so
+            const uint32_t w0 = (uint32_t)st[j], w1 = (uint32_t)(st[j] >> 32);
+            if (!done0) {
+              excl0 += w0 & LB_VALUE;
+              done0 = (w0 & LB_FLAGS) == LB_COMPLETE;
+            }
+            if (!done1) {
+              excl1 += w1 & LB_VALUE;
+              done1 = (w1 & LB_FLAGS) == LB_COMPLETE;
+            }
+          }
+        }
+        b = b > (uint32_t)LB_CHUNK ? b - LB_CHUNK : 0u;
+      }
+      st_agent64(mine, (uint64_t)(LB_COMPLETE | (excl0 + c0)) | ((uint64_t)(LB_COMPLETE | (excl1 + c1)) << 32));
+    }
+    s_gbase[d0] = gstart0 + excl0 - dstart0;
+    s_gbase[d0 + 1] = gstart1 + excl1 - dstart1;
+  }
+  __syncthreads();
+  INSTAG_STAMP(4);
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const uint32_t idx = (uint32_t)wave * (64 * IPT) + i * 64 + lane;
+    if (idx < valid) {
+      const uint32_t p = (uint32_t)cnt16[key[i] >> PACK_SHIFT] + rank[i];
+      s_keys[p] = key[i];
+      s_gid[p] = gid[i];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const uint32_t p = (uint32_t)k * PASS_THREADS + tid;
+    if (p < valid) {
+      const uint32_t kv = s_keys[p];
+      const uint32_t dst = s_gbase[kv >> PACK_SHIFT] + p;
+      if (dst < count) {
+        keys_out[dst] = kv;
+        slots_out[dst] = kv & ((1u << PACK_SHIFT) - 1u);
+        point_list[dst] = s_gid[p];
+      }
+    }
+  }
+  INSTAG_STAMP(5);
+#undef INSTAG_STAMP
+}
+
 // second-level partial histograms: out[j][p][d] = sum of partials[b][p][d] over the j-th slice of the blocks b
 // (grid = (npass, slices); the pass kernels sum the few slices themselves)
 __global__ void __launch_bounds__(SORT_THREADS)
@@ -390,6 +601,27 @@ int launch_radix_pass(int ipt, bool has_values, bool write_keys, const uint32_t*
 #undef INSTAG_PASS
   set_error("launch_radix_pass: unsupported variant");
   return INSTAG_E_ARG;
+}
+
+uint32_t tile_pass_blocks(uint32_t count_max) { return div_up<uint32_t>(count_max, TILE_WIDE); }
+
+int launch_tile_pass(const uint32_t* keys_in, const uint32_t* gid_unsorted, uint32_t* keys_out, uint32_t* slots_out,
+                     uint32_t* point_list, int32_t* ranges, const uint32_t* count_ptr, uint32_t count_max, int tiles,
+                     const uint32_t* tile_total, const uint32_t* tile_dropped, uint32_t* ticket, uint64_t* lookback,
+                     hipStream_t s, uint64_t* stamps) {
+  if (!wide_tiles(tiles) || tiles <= 0) {
+    set_error("launch_tile_pass: too many tiles for the one-pass sort");
+    return INSTAG_E_ARG;
+  }
+  const uint32_t blocks = tile_pass_blocks(count_max);
+  if (blocks == 0) return INSTAG_OK;
+  int nbits = 0;
+  while ((1 << nbits) < tiles) ++nbits;
+  tile_pass_kernel<<<blocks, PASS_THREADS, 0, s>>>(keys_in, gid_unsorted, keys_out, slots_out, point_list, ranges,
+                                                   count_ptr, count_max, tiles, nbits, tile_total, tile_dropped,
+                                                   ticket, lookback, (tiles + 1) / 2, stamps);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
 }
 
 int launch_hist_reduce(const uint32_t* partials, int nblk, int npass, int slices, uint32_t* out, hipStream_t s) {
