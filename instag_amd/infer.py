@@ -14,9 +14,9 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, diff_gauss
+from . import _lib, diff_gauss, graphs
 from .renderer import render_fuse
-from .train import Frame, _no_gc
+from .train import Frame
 
 
 class FuseRenderer:
@@ -67,16 +67,9 @@ class FuseRenderer:
         K = max(1, int(frames_per_replay))
         self._static = [example.clone_static() for _ in range(K)]
         self._static_bg = [torch.zeros(3, example.image_height, example.image_width, device=dev) for _ in range(K)]
-        diff_gauss.set_capacity_plan(None)
-        needed = []
-        for _ in range(2):                              # eager warm-up measures the instance counts of both passes
-            self._render(self._static[0], self._static_bg[0])
-            needed.append(diff_gauss.LAST_STATS["num_rendered"])
-        # LAST_STATS holds the last (mouth) pass; size both slots by the larger scene to stay safe
-        n_face, n_mouth = self.g.num_points, self.gm.num_points
-        cap = int(max(needed) * headroom * max(1.0, n_face / max(1, n_mouth))) + 4096
-        self._plan = diff_gauss.CapacityPlan([cap, cap] * K, dev)
-        diff_gauss.set_capacity_plan(self._plan)
+        counts = graphs.measure(lambda: self._render(self._static[0], self._static_bg[0]), 2)
+        self._plan = graphs.install(graphs.inference_capacities(counts, headroom, self.g.num_points,
+                                                                self.gm.num_points, K), dev)
         lanes = [_lib.side_stream(dev, ("infer_lane", k)) for k in range(K)]
 
         def all_frames():
@@ -95,17 +88,9 @@ class FuseRenderer:
                 main.wait_stream(lanes[k])
             return outs
 
-        s = _lib.warmup_stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._plan.begin_step()
-                all_frames()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
+        graphs.warm(self._plan, all_frames, dev)
         self._graph = torch.cuda.CUDAGraph()
-        self._plan.begin_step()
-        with _no_gc(), _lib.graph_capture(self._graph):
+        with graphs.capture(self._graph, self._plan):
             outs = all_frames()
             self._out = torch.stack(outs)
         self._lanes = lanes

@@ -30,7 +30,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, graphs
 from .gaussian_model import GaussianModel, OptimizationParams
 from .losses import face_loss
 
@@ -297,12 +297,13 @@ class FaceTrainer:
         # train_face.py:59-60: AdamW(betas .9/.99, eps 1e-8, wd .01), lr x0.1 during warm-up then 0.5^(it/iters)
         self._setup_optimizers()
         self.last = {}
-        self._graph = None
-        self._graph_phase = None
-        self._graph_cache = {}
+        self._graph = None            # the captured step replayed last
+        self._graph_cache = {}        # phase -> captured step
         self._graph_mode = None       # set by enable_graph: headroom / split / sticky capacity of the captured steps
         self._pool = None             # one private memory pool for every capture of this trainer (re-captures reuse it)
         self.recaptures = 0
+        self.recapture_seconds = 0.0  # host time of the re-captures
+        self.density_seconds = 0.0    # host time of the density-control events (they synchronise)
 
     # ---- optimizers: learning rates are device scalars on the GPU so a captured step can be replayed -------
     def _setup_optimizers(self):
@@ -571,17 +572,14 @@ class FaceTrainer:
             # (two prunes in the reference; both tests are per Gaussian, so one rebuild with the union removes the same rows)
             self.g.prune_points(green | (self.g.get_xyz[:, -1] < -0.07))
         self._drop_graph(keep_mode=True)          # (graph mode stays on: the next iteration captures its step again)
-        self.density_seconds = getattr(self, "density_seconds", 0.0) + time.perf_counter() - t0     # host time (it syncs)
+        self.density_seconds += time.perf_counter() - t0
         return True
 
     def _drop_graph(self, keep_mode: bool = False):
         """Forget every captured step (the parameter set changed, or the caller wants eager launches).  ``keep_mode``:
         graph mode stays on -- step() captures again when it next needs a step of some phase."""
-        if self._graph is not None or getattr(self, "_graph_cache", None):
-            from . import diff_gauss
-            diff_gauss.set_capacity_plan(None)
+        graphs.drop_plan(self._graph, *self._graph_cache.values())
         self._graph = None
-        self._graph_phase = None
         self._graph_cache = {}
         if not keep_mode:
             self._graph_mode = None
@@ -606,8 +604,8 @@ class FaceTrainer:
         g = GraphedStep(self, frame, mode["headroom"], 0, mode["split"], phase, min_capacity=cap)
         mode["capacity"], mode["capacity_n"] = g.capacity, n
         self._graph_cache[phase] = g
-        self.recaptures = getattr(self, "recaptures", 0) + 1
-        self.recapture_seconds = getattr(self, "recapture_seconds", 0.0) + time.perf_counter() - t0      # host time
+        self.recaptures += 1
+        self.recapture_seconds += time.perf_counter() - t0
         return g
 
     def _overflow_decision(self, graph) -> int:
@@ -629,24 +627,21 @@ class FaceTrainer:
         self._set_learning_rates(it)
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         phase = self.phase_of(it)
-        mode = getattr(self, "_graph_mode", None)
+        mode = self._graph_mode
         g = None
         if self._densify_due(it):
             # the parameter set is about to change: every captured step is stale.  This iteration runs eagerly (density
             # control sits between backward and the optimizers); the next one captures again
             self._drop_graph(keep_mode=True)
-        elif mode is not None or self._graph_cache or self._graph is not None:
+        elif mode is not None:
             # one captured step per phase (FacePhase): the schedule alternates between a few of them (the hair
             # iterations toggle six times out of seven)
             g = self._graph_cache.get(phase)
-            if g is None and self._graph is not None and self._graph_phase == phase:
-                g = self._graph
-            if g is None and mode is not None and mode["auto"]:
+            if g is None and mode["auto"]:
                 g = self._recapture(frame, phase)
-            if g is None and self._graph is not None:
-                from . import diff_gauss
-                diff_gauss.set_capacity_plan(None)          # a phase nobody captured (auto off): eager launches
-            self._graph, self._graph_phase = g, (phase if g is not None else None)
+            if g is None:
+                graphs.drop_plan(self._graph)          # a phase nobody captured (auto off): eager launches
+            self._graph = g
         if g is not None:
             g.replay(frame)
             loss, Ll1 = g.loss, g.l1
@@ -656,16 +651,11 @@ class FaceTrainer:
                     # some replayed step needed more instances than the captured capacity (its image was truncated to
                     # the nearest Gaussians, gradients of the dropped ones zero): capture again, sized from the peak
                     # need -- lazily, phase by phase, without consuming iterations (_recapture)
-                    if mode is None:
-                        mode = self._graph_mode = dict(headroom=1.4, split=g.split, auto=True, capacity=g.capacity,
-                                                       capacity_n=max(1, self.g.num_points))
                     mode["capacity"] = max(mode["capacity"], int(1.4 * peak) + 4096)
                     mode["auto"] = True
                     self._drop_graph(keep_mode=True)
         else:
-            from . import diff_gauss
-            if diff_gauss._CAPACITY_PLAN is not None:
-                diff_gauss._CAPACITY_PLAN.begin_step()
+            graphs.begin_eager_step()
             pkg, loss, Ll1 = self._forward_backward(frame, phase, fold_aux=True)
             self._stats_and_optimizers(pkg, distributed, it, frame)
             self._zero_grad()
@@ -732,8 +722,6 @@ class FaceTrainer:
         parameter set changes (densify / prune / opacity reset) or a replay overflowed the instance capacity.  With
         ``auto_recapture`` step() then captures the step it needs again by itself, without warm-up steps and without
         touching the training state (_recapture); without it such a step launches eagerly."""
-        if not hasattr(self, "_graph_cache"):
-            self._graph_cache = {}
         self._graph = None
         if phase is None:
             after = self.iteration + (0 if keep_state else max(1, warmup_steps) + 2) + 1
@@ -743,51 +731,21 @@ class FaceTrainer:
             warm_density_control(self.device, self.g.max_sh_degree, self.opt)
         self._graph = GraphedStep(self, example_frame, headroom, max(1, warmup_steps), split_for_allreduce, phase,
                                   min_capacity=min_capacity, restore=snap)
-        self._graph_phase = phase
         self._graph_cache[phase] = self._graph
-        prev = getattr(self, "_graph_mode", None)
+        prev = self._graph_mode
         self._graph_mode = dict(headroom=headroom, split=self._graph.split, auto=bool(auto_recapture),
                                 capacity=max(self._graph.capacity, prev["capacity"] if prev else 0),
                                 capacity_n=max(1, self.g.num_points))
         return self._graph
 
 
-class _no_gc:
-    """No cyclic garbage collection inside a stream-capture window.  The crash this once papered over (a segmentation
-    fault in capture_end) is addressed at its cause in instag_amd/_keepalive.py: tensors that cross streams are no
-    longer marked with record_stream inside a capture, the capture's owner keeps them alive until it has ended.  The
-    collector stays off during the window all the same: a collection there frees an earlier step's blocks into the
-    capture's private pool at an arbitrary point of the captured sequence, which makes captures irreproducible.
-    ``collect=False`` (re-captures inside a train loop): no full collection in front either -- it costs tens of
-    milliseconds, as much as ten train steps."""
-
-    def __init__(self, collect: bool = True):
-        self.collect = collect
-
-    def __enter__(self):
-        import gc
-        self.was = gc.isenabled()
-        if self.collect:
-            gc.collect()
-        gc.disable()
-
-    def __exit__(self, *exc):
-        import gc
-        if self.was:
-            gc.enable()
-        return False
-
-
-class GraphedStep:
-    CHECK_EVERY = 64         # replays between two looks at the (sticky, device-side) overflow flags
-
+class GraphedStep(graphs.CapturedStep):
     def __init__(self, trainer: FaceTrainer, example: Frame, headroom: float, warmup_steps: int,
                  split_for_allreduce: Optional[bool] = None, phase: FacePhase = C3_PHASE, min_capacity: int = 0,
                  restore=None):
         """``warmup_steps`` > 0: the cold path (eager steps measure the instance count and warm every library; with
         ``restore`` = a trainer.snapshot() the training state is put back afterwards).  0: the warm path of
         FaceTrainer._recapture -- nothing runs, ``min_capacity`` is the capacity."""
-        from . import diff_gauss
         self.phase = phase
         t = self.trainer = trainer
         dev = t.device
@@ -809,63 +767,43 @@ class GraphedStep:
                                 and os.environ.get("INSTAG_EARLY_OPTIMIZER", "0") == "1")
         self.static = example.clone_static()
         cold = warmup_steps > 0
+
+        def pre():
+            t.iteration += 1
+            t._set_learning_rates(t.iteration)
+
+        def eager_step():
+            pkg = t._forward_backward(self.static, phase, fold_aux=True)[0]
+            t._stats_and_optimizers(pkg, self.distributed)
+            t._zero_grad()
+
         if cold:
-            # 1. eager warm-up in the normal (host round trip) mode: measures R of both raster passes
-            diff_gauss.set_capacity_plan(None)
-            needed = 0
-            for _ in range(warmup_steps):
-                t.iteration += 1
-                t._set_learning_rates(t.iteration)
-                # (only the package is kept, and only for the statistics: a live loss tensor would keep this step's
-                # autograd graph -- and with it every parameter's gradient accumulator, bound to THIS stream -- alive
-                # into the capture, whose backward would then hop to this stream for every AccumulateGrad)
-                pkg = t._forward_backward(self.static, phase, fold_aux=True)[0]
-                t._stats_and_optimizers(pkg, self.distributed)
-                t._zero_grad()
-                del pkg
-                needed = max(needed, diff_gauss.LAST_STATS["num_rendered"])
-            cap = max(int(needed * headroom) + 4096, int(min_capacity))
+            cap = graphs.face_capacity(graphs.measure(eager_step, warmup_steps, pre), headroom, min_capacity)
         else:
             assert min_capacity > 0, "a warm capture needs the capacity of an earlier one"
             cap = int(min_capacity)
             t._prepare_optimizers()          # tables of the new parameter set: allocations / uploads outside the capture
             from . import renderer
             renderer.prepare_screenspace(t.g)      # (likewise the zeros behind the screen-space gradient carrier)
-        self.plan = diff_gauss.CapacityPlan([cap, cap], dev)
-        self._replays = 0
-        diff_gauss.set_capacity_plan(self.plan)
+        self.plan = graphs.install([cap, cap], dev)
         if cold:
-            # 2. two eager steps in capacity mode on a side stream (allocator / library warm-up for capture)
-            s = _lib.warmup_stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    t.iteration += 1
-                    t._set_learning_rates(t.iteration)
-                    self.plan.begin_step()
-                    pkg = t._forward_backward(self.static, phase, fold_aux=True)[0]
-                    t._stats_and_optimizers(pkg, self.distributed)
-                    t._zero_grad()
-                    del pkg
-            torch.cuda.current_stream(dev).wait_stream(s)
-            torch.cuda.synchronize(dev)
+            graphs.warm(self.plan, eager_step, dev, pre)
             if restore is not None:
                 t.restore(restore)
                 t._set_learning_rates(max(1, t.iteration))
-        # 3. capture.  With several ranks the gradient exchange stays outside the graphs:
+        # With several ranks the gradient exchange stays outside the graphs:
         #    graph A = forward + backward (+ bucket fill), eager all-reduce, graph B = statistics + optimizers.
         # other threads (the collective library's watchdog) may touch the HIP runtime while this thread captures
-        mode = {"capture_error_mode": "thread_local"} if self.distributed else {}
+        options = {"capture_error_mode": "thread_local"} if self.distributed else {}
         if t._pool is None:
             t._pool = _lib.GraphPool(dev)
-        mode["pool"] = t._pool.handle
-        mode["light"] = not cold
+        options["pool"] = t._pool.handle
+        options["light"] = not cold
         self.graph_a = torch.cuda.CUDAGraph()
         self.graph_b = None
         dot = os.environ.get("INSTAG_GRAPH_DOT")       # diagnostics: the captured step's nodes and edges (DOT)
         if dot:
             self.graph_a.enable_debug_mode()
-        self.plan.begin_step()
         self.graph_a2 = None
         # single graph, optimizers in two launches (INSTAG_EARLY_OPTIMIZER=1, off by default): statistics and the
         # per-Gaussian parameters except the positions (20 of 24 floats per Gaussian) on a side stream beside the motion
@@ -874,7 +812,7 @@ class GraphedStep:
         # any fork point
         if self.early_optimizer:
             side = _lib.side_stream(dev, "early_optimizer")
-            with _no_gc(cold), _lib.graph_capture(self.graph_a, **mode):
+            with graphs.capture(self.graph_a, self.plan, cold, **options):
                 main = torch.cuda.current_stream(dev)
                 pkg, loss, l1, early, finish = t._forward_backward_cut(self.static, phase, fold_aux=True)
 
@@ -903,28 +841,26 @@ class GraphedStep:
                 t._zero_grad()
             del pkg, finish
         elif not self.split:
-            with _no_gc(cold), _lib.graph_capture(self.graph_a, **mode):
+            with graphs.capture(self.graph_a, self.plan, cold, **options):
                 pkg, loss, l1 = t._forward_backward(self.static, phase, fold_aux=True)
                 t._stats_and_optimizers(pkg, False)
                 t._zero_grad()
-            # nothing captured is released before the capture has ended (ROCm 7.2: frees inside the capture
-            # window intermittently crash hipStreamEndCapture)
             del pkg
         elif self.early:
-            with _no_gc(cold), _lib.graph_capture(self.graph_a, **mode):
+            with graphs.capture(self.graph_a, self.plan, cold, **options):
                 pkg, loss, l1, early, finish = t._forward_backward_cut(self.static, phase)
                 self._vs_grad, self._radii = pkg["viewspace_points"].grad, pkg["radii"]
                 self._params_early = early
                 self._bucket_early = flat_grad_bucket(early)
             self.graph_a2 = torch.cuda.CUDAGraph()
-            with _no_gc(False), _lib.graph_capture(self.graph_a2, **mode):
+            with graphs.capture(self.graph_a2, self.plan, False, **options):
                 finish()
                 ids = {id(q) for q in early}
                 self._params = [q for q in with_grad(t._all_params()) if id(q) not in ids]
                 self._bucket = flat_grad_bucket(self._params)
             del pkg, finish
             self.graph_b = torch.cuda.CUDAGraph()
-            with _no_gc(False), _lib.graph_capture(self.graph_b, **mode):
+            with graphs.capture(self.graph_b, self.plan, False, **options):
                 with torch.no_grad():
                     if self.distributed:
                         self._bucket_early.mul_(1.0 / dist.get_world_size())
@@ -935,14 +871,14 @@ class GraphedStep:
                     t._step_optimizers()
                     t._zero_grad()
         else:
-            with _no_gc(cold), _lib.graph_capture(self.graph_a, **mode):
+            with graphs.capture(self.graph_a, self.plan, cold, **options):
                 pkg, loss, l1 = t._forward_backward(self.static, phase)
                 self._vs_grad, self._radii = pkg["viewspace_points"].grad, pkg["radii"]
                 self._params = with_grad(t._all_params())
                 self._bucket = flat_grad_bucket(self._params)
             del pkg
             self.graph_b = torch.cuda.CUDAGraph()
-            with _no_gc(False), _lib.graph_capture(self.graph_b, **mode):
+            with graphs.capture(self.graph_b, self.plan, False, **options):
                 with torch.no_grad():
                     if self.distributed:
                         # mean over ranks of the summed gradients
@@ -953,11 +889,7 @@ class GraphedStep:
                     t._zero_grad()
         if dot:
             self.graph_a.debug_dump(dot)
-        # detached: a retained loss would keep the captured step's autograd graph alive, and with it every parameter's
-        # AccumulateGrad node, bound to the capture stream -- the next backward on any other stream (an eager step, the
-        # instrumented pass of bench.py) then hops to the capture stream for every parameter
-        self.loss, self.l1 = loss.detach(), l1.detach()
-        del loss, l1
+        self.loss, self.l1 = loss.detach(), l1.detach()          # (detached, released after the capture: graphs.py)
         self.capacity = cap
 
     def replay(self, frame: Frame):
@@ -979,20 +911,6 @@ class GraphedStep:
             if self.distributed:
                 dist.all_reduce(self._bucket, op=dist.ReduceOp.SUM)       # the division by the world size is in graph B
             self.graph_b.replay()
-
-    def check_overflow(self):
-        """Host-side (synchronising) check that no replayed step exceeded the instance capacity (the device flag is
-        sticky: every step since the capture / the last clear counts)."""
-        return self.plan.overflowed()
-
-    def check_due(self) -> bool:
-        """True every CHECK_EVERY replays: the caller then reads the sticky overflow flags (FaceTrainer._overflow_decision:
-        one synchronising read per CHECK_EVERY steps -- a function of the replay count alone, hence the same step on every
-        rank)."""
-        if self._replays < self.CHECK_EVERY:
-            return False
-        self._replays = 0
-        return True
 
 
 def build_trainer(n_gaussians, device, sh_degree=1, seed=0, densify=False, encoder_cls=None, raw=None, schedule=None):

@@ -14,7 +14,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import graphs
 from .gaussian_model import GaussianModel, OptimizationParams, sh_to_rgb
 from .losses import l1_and_ssim
 from .train import Frame
@@ -107,82 +107,6 @@ def _combine(*optimizers):
     return None
 
 
-class GraphedStage:
-    """A stage trainer's whole step (forward, loss, backward, statistics, optimizers) captured once into a hipGraph
-    and replayed: ``body(frame) -> (outputs..., keepalive)`` must be free of host round trips; the rasterizer runs in
-    its capacity mode with one slot per rasterizer call of the step, sized from eager warm-up steps
-    (instag_amd/diff_gauss.py:CapacityPlan)."""
-
-    def __init__(self, body, example: Frame, device, headroom: float = 1.5, warmup_steps: int = 2, pre=None):
-        """``pre()`` = the host-side part of a step (iteration counter, learning-rate table): run before every
-        warm-up step, never captured."""
-        from . import diff_gauss
-        from .train import _no_gc
-        assert device.type == "cuda", "graph mode needs the GPU"
-        import sys
-        self.static = example.clone_static()
-        diff_gauss.set_capacity_plan(None)
-        counts = None
-        for _ in range(max(1, warmup_steps)):
-            diff_gauss.RENDERED_LOG.clear()
-            if pre is not None:
-                pre()
-            body(self.static)
-            got = list(diff_gauss.RENDERED_LOG)
-            counts = got if counts is None else [max(a, b) for a, b in zip(counts, got)]
-        self.capacities = [int(r * headroom) + 4096 for r in counts]
-        self.plan = diff_gauss.CapacityPlan(self.capacities, device)
-        diff_gauss.set_capacity_plan(self.plan)
-        side = _lib.warmup_stream(device)              # allocator / library warm-up in capacity mode
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self.plan.begin_step()
-                if pre is not None:
-                    pre()
-                body(self.static)
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.graph = torch.cuda.CUDAGraph()
-        self.plan.begin_step()
-        with _no_gc(), _lib.graph_capture(self.graph):
-            try:
-                out = body(self.static)
-            except BaseException:
-                # an operator that is not capturable raised: report it before the capture is torn down (ending an
-                # invalidated capture can crash the process on ROCm 7.2, which would hide the message)
-                import traceback
-                traceback.print_exc()
-                sys.stderr.flush()
-                raise
-        # body returns (..., keepalive): the render package stays referenced until the capture has ended (ROCm 7.2:
-        # releasing it inside the capture window intermittently crashes hipStreamEndCapture), then it is dropped
-        # (detached: a retained loss would keep the step's autograd graph -- and every parameter's AccumulateGrad node,
-        # bound to the capture stream -- alive into the next backward on another stream)
-        self.out = tuple(o.detach() if torch.is_tensor(o) else o for o in out[:-1])
-        del out
-
-    CHECK_EVERY = 64         # replays between two looks at the (sticky, device-side) overflow flags
-
-    def replay(self, frame: Frame):
-        self.static.copy_from(frame)
-        self.graph.replay()
-        self._replays = getattr(self, "_replays", 0) + 1
-        return self.out
-
-    def check_overflow(self):
-        return self.plan.overflowed()
-
-    def overflow_due(self):
-        """True every CHECK_EVERY replays if some rasterizer call of a replayed step needed more instances than its
-        capacity (the flag is sticky on the device, one synchronising read per CHECK_EVERY steps): the caller drops the
-        graph -- steps run eagerly, or are captured again with larger capacities."""
-        if getattr(self, "_replays", 0) < self.CHECK_EVERY:
-            return False
-        self._replays = 0
-        return bool(self.plan.poll_overflow())        # asynchronous: the answer of the previous poll, no device wait
-
-
 _ONE = {}
 
 
@@ -205,9 +129,7 @@ def _backward(loss, device):
 
 
 def _drop_graph(trainer):
-    if getattr(trainer, "_graph", None) is not None:
-        from . import diff_gauss
-        diff_gauss.set_capacity_plan(None)
+    graphs.drop_plan(trainer._graph)
     trainer._graph = None
     trainer._graph_key = None
 
@@ -377,7 +299,8 @@ class MouthTrainer:
 
         def body(frame):
             return self._body(frame, phase, self._k_dev, stats_on)
-        self._graph = GraphedStage(body, example, self.device, headroom, warmup_steps, pre=pre)
+        self._graph = graphs.GraphedStage(body, example, self.device,
+                                          lambda counts: graphs.stage_capacities(counts, headroom), warmup_steps, pre)
         self._graph_key = key
         return self._graph
 
@@ -402,9 +325,7 @@ class MouthTrainer:
             if self._graph.overflow_due():
                 _drop_graph(self)               # the scene outgrew the captured capacities: eager launches from here on
         else:
-            from . import diff_gauss
-            if diff_gauss._CAPACITY_PLAN is not None:
-                diff_gauss._CAPACITY_PLAN.begin_step()
+            graphs.begin_eager_step()
             pkg, loss, Ll1 = self.forward(frame, phase, k)
             _backward(loss, self.device)
             if self._stats_on(it):
@@ -481,7 +402,8 @@ class FuseTrainer:
         def pre():
             self.iteration += 1
             self._set_learning_rates(self.iteration)
-        self._graph = GraphedStage(self._body, example, self.device, headroom, warmup_steps, pre=pre)
+        self._graph = graphs.GraphedStage(self._body, example, self.device,
+                                          lambda counts: graphs.stage_capacities(counts, headroom), warmup_steps, pre)
         return self._graph
 
     def step(self, frame: Frame):
@@ -495,9 +417,7 @@ class FuseTrainer:
             if self._graph.overflow_due():
                 _drop_graph(self)
         elif it < self.opt.iterations:
-            from . import diff_gauss
-            if diff_gauss._CAPACITY_PLAN is not None:
-                diff_gauss._CAPACITY_PLAN.begin_step()
+            graphs.begin_eager_step()
             loss, Ll1, image = self._body(frame)[:3]
         else:
             out, loss, Ll1 = self.forward(frame)         # last iteration: no optimizer step (:242)

@@ -306,6 +306,26 @@ def test_face_phase_schedule_matches_reference_table():
     assert face_phase(6101).prior_depth
 
 
+def test_capture_capacity_rules():
+    """Instance capacities of the captured steps from recorded per-call instance counts of the eager warm-up steps
+    (one list per step, one entry per rasterizer call).  The capacity also picks the blend kernel, so these numbers
+    are behaviour: face = both slots from the largest LAST call, stages = per call, inference = every one of the 2K
+    slots from the largest last (mouth) call, scaled up to the larger scene."""
+    from instag_amd.graphs import face_capacity, inference_capacities, stage_capacities
+    face = [[1000, 5000], [1200, 4800], [900, 5100]]                   # the steps' calls differ
+    assert face_capacity(face, 1.4) == 11236                           # int(5100 * 1.4) + 4096
+    assert face_capacity(face, 1.5) == 11746
+    assert face_capacity(face, 1.4, min_capacity=20000) == 20000
+    assert face_capacity([[3000]], 1.4) == 8296
+    stages = [[30000, 8000, 513], [31000, 7000, 777]]
+    assert stage_capacities(stages, 1.5) == [50596, 16096, 5261]       # int(max_k * 1.5) + 4096 per call k
+    assert stage_capacities(stages, 1.4) == [47496, 15296, 5183]
+    renders = [[50000, 12000], [52000, 11000]]                         # (face, mouth) of the two warm-up renders
+    assert inference_capacities(renders, 1.5, 100000, 20000, 3) == [94096] * 6      # int(12000 * 1.5 * 5) + 4096
+    assert inference_capacities(renders, 1.5, 3000, 800, 3) == [71596] * 6
+    assert inference_capacities(renders, 1.5, 500, 800, 1) == [22096] * 2            # a smaller face: no scaling
+
+
 def test_normalize_and_sh_basis_match_reference_goldens():
     import numpy as np
     from instag_amd.gaussian_model import sh_basis, sh_to_rgb
