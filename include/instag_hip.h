@@ -603,6 +603,42 @@ int instag_adam_step_grads_ticketed(const void* tensors, const void* host_grads,
                                     int32_t* tickets, instag_stream_t stream);
 int instag_adam_step(const void* tensors, int32_t n_tensors, const void* groups, const float* lrs,
                      const int32_t* chunks, int32_t n_chunks, float* step, instag_stream_t stream);
+/* AdamW + EMA of the parameters in one launch (pretrain_face.py:187-193; torch_ema semantics: every tensor's shadow
+ * s -= (1 - d) * (s - p), d = min(ema_decay, (1 + n) / (10 + n)) for the n-th update, gradient or not).  tensors: device
+ * array of 48-byte records {float* p, float* m, float* v, float* s (shadow), int64 n, int32 group, int32 pad}; the
+ * gradients come as in instag_adam_step_grads_ticketed; ema: device int32[2] = (updates so far, ticket = 0). */
+int instag_adam_ema_step(const void* tensors, const void* host_grads, int32_t n_tensors, const void* groups,
+                         const float* lrs, const int32_t* chunks, int32_t n_chunks, float* step, int32_t* tickets,
+                         int32_t* ema, double ema_decay, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Pretraining of the universal motion field (csrc/pretrain.hip, pretrain_face.py:34-522).
+ *  pretrain_deform: render_motion(personalized=True, align=False) from h_u, h_p [N,11] (UMF / PMF head outputs) ->
+ *    means3D, scales, rotations, opacity, plus (reg_partials, may be NULL; instag_pretrain_deform_num_partials(N)
+ *    floats) per-workgroup partial sums of the eight 1e-5-weighted mean-|.| regularisers of both fields and of the
+ *    contrast term sum_j mean_n relu(sum_c (h_j[c]*1e-2) * (h_p[c]*1e-2)).  host_heads: HOST array of n_others device
+ *    pointers to the other identities' heads [N,11] (columns 0..2 are read), n_others <=
+ *    instag_pretrain_deform_max_others().  backward: g_reg (device scalar, may be NULL) = upstream gradient of the
+ *    partial sums; no gradient for the other heads.
+ *  window_mean: out[0:n_prev] = prev, out[n_prev] = w * x[ch, r0:r1, c0:c1].mean(), rect = device int32 (r0,r1,c0,c1);
+ *    backward writes dx [C,H,W] = g[0] * w / count inside the window, 0 elsewhere.
+ * ------------------------------------------------------------------------------------------ */
+int instag_pretrain_deform_max_others(void);
+int instag_pretrain_deform_num_partials(int32_t N);
+int instag_pretrain_deform_forward(const float* xyz, const float* scaling, const float* rotation, const float* opacity,
+                                   const float* h_u, const float* h_p, const void* host_heads, int32_t n_others,
+                                   float* means3D, float* scales, float* rotations, float* opac, float* reg_partials,
+                                   int32_t N, instag_stream_t stream);
+int instag_pretrain_deform_backward(const float* scaling, const float* rotation, const float* opacity,
+                                    const float* h_u, const float* h_p, const void* host_heads, int32_t n_others,
+                                    const float* g_means, const float* g_scales, const float* g_rots,
+                                    const float* g_opac, const float* g_reg, float* d_xyz, float* d_scaling,
+                                    float* d_rotation, float* d_opacity, float* d_hu, float* d_hp, int32_t N,
+                                    instag_stream_t stream);
+int instag_window_mean_forward(const float* x, int32_t C, int32_t H, int32_t W, int32_t ch, const int32_t* rect,
+                               float w, const float* prev, int32_t n_prev, float* out, instag_stream_t stream);
+int instag_window_mean_backward(int32_t C, int32_t H, int32_t W, int32_t ch, const int32_t* rect, float w,
+                                const float* g, float* dx, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named

@@ -294,6 +294,13 @@ _PROTOS = {
     "instag_adam_grads_max": (C.c_int, []),
     "instag_adam_step_grads": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp]),
     "instag_adam_step_grads_ticketed": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
+    "instag_adam_ema_step": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, C.c_double, vp]),
+    "instag_pretrain_deform_max_others": (C.c_int, []),
+    "instag_pretrain_deform_num_partials": (C.c_int, [i32]),
+    "instag_pretrain_deform_forward": (C.c_int, [vp] * 7 + [i32] + [vp] * 5 + [i32, vp]),
+    "instag_pretrain_deform_backward": (C.c_int, [vp] * 6 + [i32] + [vp] * 11 + [i32, vp]),
+    "instag_window_mean_forward": (C.c_int, [vp, i32, i32, i32, i32, vp, f32, vp, i32, vp, vp]),
+    "instag_window_mean_backward": (C.c_int, [i32, i32, i32, i32, vp, f32, vp, vp, vp]),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

@@ -45,6 +45,7 @@ SOURCES = {
     "knn.hip": [],
     "select.hip": [],
     "prior.hip": [],
+    "pretrain.hip": ["-ffp-contract=off"],
 }
 
 

@@ -137,6 +137,76 @@ adam_step_grads_kernel(const AdamTensor* __restrict__ tensors, AdamGrads grads, 
   }
 }
 
+// AdamW + exponential moving average of the parameters (pretrain_face.py:187-193: motion_optimizer.step(), then
+// ema_motion_net.update()) in one launch.  torch_ema semantics: the EMA runs over EVERY tensor of the table, with a
+// gradient this step or not, with decay d = min(decay, (1 + n) / (10 + n)) for the n-th update: s -= (1 - d) * (s - p).
+// The update counter lives in ema[0] (device), counted like the per-tensor steps: every workgroup reads it, and the
+// one that draws the launch's last ticket (ema[1]) stores n and clears the ticket.  A replayed graph advances it.
+struct AdamEmaTensor {  // one parameter tensor with its shadow (device pointers), 48 bytes
+  float* p;
+  float* m;
+  float* v;
+  float* s;
+  int64_t n;
+  int32_t group;
+  int32_t pad;
+};
+
+__global__ void __launch_bounds__(ADAM_BLOCK)
+adam_ema_step_kernel(const AdamEmaTensor* __restrict__ tensors, AdamGrads grads, const AdamGroup* __restrict__ groups,
+                     const float* __restrict__ lrs, const int2* __restrict__ chunks, float* step,
+                     int32_t* __restrict__ tickets, int32_t* ema, double ema_decay) {
+  const int2 ch = chunks[blockIdx.x];            // (tensor index, chunk index)
+  const float* __restrict__ tg = grads.g[ch.x];
+  const AdamEmaTensor t = tensors[ch.x];
+  const int32_t count = ema[0] + 1;
+  // (in double, rounded once: torch_ema forms 1 - d in Python floats)
+  const double dd = fmin(ema_decay, (1.0 + count) / (10.0 + count));
+  const float omd = (float)(1.0 - dd);
+  const int64_t base = (int64_t)ch.y * ADAM_CHUNK;
+  const int64_t end = min(t.n, base + ADAM_CHUNK);
+  float tstep = 0.f;
+  if (tg != nullptr) {
+    const AdamGroup gr = groups[t.group];
+    const float lr = lrs[t.group];
+    tstep = step[ch.x] + 1.0f;
+    const float bc1 = 1.0f - powf(gr.beta1, tstep);
+    const float bc2_sqrt = sqrtf(1.0f - powf(gr.beta2, tstep));
+    const float step_size = lr / bc1;
+    for (int64_t i = base + threadIdx.x; i < end; i += ADAM_BLOCK) {
+      float p = t.p[i], g = tg[i], m = t.m[i], v = t.v[i];
+      if (gr.decoupled) p *= 1.0f - lr * gr.weight_decay;
+      else if (gr.weight_decay != 0.f) g += gr.weight_decay * p;
+      m = gr.beta1 * m + (1.0f - gr.beta1) * g;
+      v = gr.beta2 * v + (1.0f - gr.beta2) * g * g;
+      const float denom = sqrtf(v) / bc2_sqrt + gr.eps;
+      p -= step_size * (m / denom);
+      t.p[i] = p; t.m[i] = m; t.v[i] = v;
+      const float s = t.s[i];
+      t.s[i] = __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p)));
+    }
+  } else {
+    for (int64_t i = base + threadIdx.x; i < end; i += ADAM_BLOCK) {
+      const float s = t.s[i];
+      t.s[i] = __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, t.p[i])));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (tg != nullptr) {
+      const int nchunks = (int)((t.n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+      if (atomicAdd(&tickets[ch.x], 1) == nchunks - 1) {
+        tickets[ch.x] = 0;
+        step[ch.x] = tstep;
+      }
+    }
+    if (atomicAdd(&ema[1], 1) == (int32_t)gridDim.x - 1) {
+      ema[1] = 0;
+      ema[0] = count;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace instag
 
@@ -203,6 +273,26 @@ int instag_adam_step_grads_ticketed(const void* tensors, const void* host_grads,
   memcpy(gr.g, host_grads, (size_t)n_tensors * sizeof(const float*));
   adam_step_grads_kernel<true><<<n_chunks, ADAM_BLOCK, 0, s>>>((const AdamTensor*)tensors, gr, (const AdamGroup*)groups,
                                                                lrs, (const int2*)chunks, step, tickets);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+/* As instag_adam_step_grads_ticketed, followed in the same launch by the EMA update of every tensor (see
+ * adam_ema_step_kernel).  tensors: device array of 48-byte records {p, m, v, s (shadow), int64 n, int32 group, int32 pad};
+ * ema: device int32[2] = (updates so far, ticket), the ticket zero before the first call and left zero by every call;
+ * chunks must list every chunk of every tensor exactly once. */
+int instag_adam_ema_step(const void* tensors, const void* host_grads, int32_t n_tensors, const void* groups,
+                         const float* lrs, const int32_t* chunks, int32_t n_chunks, float* step, int32_t* tickets,
+                         int32_t* ema, double ema_decay, instag_stream_t stream) {
+  INSTAG_REQUIRE(tensors && host_grads && groups && lrs && chunks && step && tickets && ema, "adam_ema_step: NULL argument");
+  INSTAG_REQUIRE(n_tensors <= ADAM_GRADS_MAX, "adam_ema_step: more tensors than instag_adam_grads_max()");
+  if (n_chunks <= 0 || n_tensors <= 0) return INSTAG_OK;
+  AdamGrads gr;
+  memset(&gr, 0, sizeof(gr));
+  memcpy(gr.g, host_grads, (size_t)n_tensors * sizeof(const float*));
+  adam_ema_step_kernel<<<n_chunks, ADAM_BLOCK, 0, (hipStream_t)stream>>>(
+      (const AdamEmaTensor*)tensors, gr, (const AdamGroup*)groups, lrs, (const int2*)chunks, step, tickets, ema,
+      ema_decay);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }

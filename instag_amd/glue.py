@@ -3,9 +3,11 @@ composition and the loss block.  Each replaces a chain of eager elementwise ops 
   motion_glue      scene/motion_net.py:291-306 / :679-692
   deform_activate  gaussian_renderer/__init__.py:200-235 (render_motion, personalized=False, align=True)
   motion_l1_reg    train_face.py:510-514
+  pretrain_deform  render_motion(personalized=True, align=False) + the per-Gaussian loss terms of pretrain_face.py
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import torch
@@ -253,6 +255,105 @@ def deform_activate(xyz, scaling, rotation, opacity, h, p, reg_weight=None):
     fifth output holds per-workgroup partial sums of reg_weight * motion_l1_reg(h, p) (train_face.py:510-514): feed it
     to ``losses.face_loss(extra=..., w_extra=1.0)``; its gradient comes back through this operator's backward."""
     return _DeformActivate.apply(xyz, scaling, rotation, opacity, h, p, reg_weight)
+
+
+class _PretrainDeform(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, scaling, rotation, opacity, h_u, h_p, with_reg, *others):
+        L = _lib.lib()
+        ctx.set_materialize_grads(False)
+        xyz, scaling, rotation, opacity, h_u, h_p = (_c(t) for t in (xyz, scaling, rotation, opacity, h_u, h_p))
+        others = [_c(t) for t in others]
+        N, dev = xyz.shape[0], xyz.device
+        means3D = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        rots = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        reg = torch.empty(L.instag_pretrain_deform_num_partials(N), dtype=torch.float32, device=dev) if with_reg else None
+        heads = (C.c_void_p * max(1, len(others)))(*[t.data_ptr() for t in others])
+        check(L.instag_pretrain_deform_forward(ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(h_u), ptr(h_p),
+                                               C.cast(heads, C.c_void_p), len(others), ptr(means3D), ptr(scales),
+                                               ptr(rots), ptr(opac), ptr(reg), N, _lib.current_stream()),
+              "pretrain_deform_forward")
+        ctx.save_for_backward(scaling, rotation, opacity, h_u, h_p, *others)
+        ctx.n_inputs = 7 + len(others)
+        if reg is None:
+            return means3D, scales, rots, opac
+        return means3D, scales, rots, opac, reg
+
+    @staticmethod
+    def backward(ctx, g_means, g_scales, g_rots, g_opac, g_reg=None):
+        L = _lib.lib()
+        scaling, rotation, opacity, h_u, h_p, *others = ctx.saved_tensors
+        N, dev = scaling.shape[0], scaling.device
+        gs = [None if g is None else _c(g) for g in (g_means, g_scales, g_rots, g_opac)]
+        # every partial sum feeds the same scalar: its upstream gradient is one number
+        g_reg1 = None if g_reg is None else g_reg.reshape(-1)[:1].contiguous().float()
+        d_xyz = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        d_scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        d_rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        d_op = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        d_hu = torch.empty(N, 11, dtype=torch.float32, device=dev)
+        d_hp = torch.empty(N, 11, dtype=torch.float32, device=dev)
+        heads = (C.c_void_p * max(1, len(others)))(*[t.data_ptr() for t in others])
+        check(L.instag_pretrain_deform_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h_u), ptr(h_p),
+                                                C.cast(heads, C.c_void_p), len(others), ptr(gs[0]), ptr(gs[1]),
+                                                ptr(gs[2]), ptr(gs[3]), ptr(g_reg1), ptr(d_xyz), ptr(d_scaling),
+                                                ptr(d_rot), ptr(d_op), ptr(d_hu), ptr(d_hp), N,
+                                                _lib.current_stream()), "pretrain_deform_backward")
+        return (d_xyz, d_scaling, d_rot, d_op, d_hu, d_hp, None) + (None,) * (ctx.n_inputs - 7)
+
+
+def pretrain_deform(xyz, scaling, rotation, opacity, h_u, h_p, others=(), with_reg=True):
+    """means3D, scales, rotations, opacity of render_motion(personalized=True, align=False) from the UMF / PMF head
+    outputs h_u, h_p [N,11] (csrc/pretrain.hip).  ``with_reg``: a fifth output holds per-workgroup partial sums of the
+    pretraining step's per-Gaussian loss terms -- the eight 1e-5-weighted mean-|.| regularisers of both fields (the UMF's
+    d_xyz / d_rot / d_scale after the reference's in-place additions of the PMF's values) and the contrast term against
+    ``others``, the other identities' PMF heads [N,11] evaluated without gradient.  Feed it to
+    ``losses.face_loss(extra=..., w_extra=1.0)``."""
+    L = _lib.lib()
+    if len(others) > L.instag_pretrain_deform_max_others():
+        raise ValueError(f"pretrain_deform: at most {L.instag_pretrain_deform_max_others()} other identities")
+    others = [t.detach() for t in others]
+    return _PretrainDeform.apply(xyz, scaling, rotation, opacity, h_u, h_p, bool(with_reg), *others)
+
+
+class _WindowMeanAppend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, prev, rect, channel, weight):
+        L = _lib.lib()
+        ctx.set_materialize_grads(False)
+        x = _c(x)
+        prev = _c(prev.reshape(-1))
+        rect = rect.reshape(-1).contiguous().to(torch.int32)
+        Cc, H, W = x.shape
+        out = torch.empty(prev.numel() + 1, dtype=torch.float32, device=x.device)
+        check(L.instag_window_mean_forward(ptr(x), Cc, H, W, int(channel), ptr(rect), float(weight), ptr(prev),
+                                           prev.numel(), ptr(out), _lib.current_stream()), "window_mean_forward")
+        ctx.save_for_backward(rect)
+        ctx.meta = (Cc, H, W, int(channel), float(weight), prev.numel())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        (rect,) = ctx.saved_tensors
+        Cc, H, W, channel, weight, n_prev = ctx.meta
+        # every entry feeds the same scalar sum: the first element's gradient is the gradient of all of them
+        g1 = g.reshape(-1)[:1].contiguous().float()
+        dx = torch.empty(Cc, H, W, dtype=torch.float32, device=g.device)
+        check(_lib.lib().instag_window_mean_backward(Cc, H, W, channel, ptr(rect), weight, ptr(g1), ptr(dx),
+                                                     _lib.current_stream()), "window_mean_backward")
+        return dx, g.reshape(-1)[:n_prev], None, None, None
+
+
+def window_mean_append(x, prev, rect, channel, weight):
+    """cat(prev, [weight * x[channel, r0:r1, c0:c1].mean()]) in one launch; rect = int32 (r0, r1, c0, c1) on the device.
+    The loss kernel reads the result as its ``extra`` array (the pretraining step's 5e-3 lips term of the
+    personalised attention map, pretrain_face.py:143-144, behind the deform operator's partial sums).  Its backward
+    assumes the entries are summed (their gradients are one number)."""
+    return _WindowMeanAppend.apply(x, prev, rect, channel, weight)
 
 
 class _MouthActivate(torch.autograd.Function):

@@ -182,9 +182,12 @@ FLAG_HAIR_TO_BG, FLAG_ALPHA, FLAG_HAIR_ATTN, FLAG_LIPS, FLAG_MOUTH, FLAG_PLAIN =
 
 
 def face_loss_torch(image, gt, face_mask, hair_mask, mouth_mask, bg, alpha=None, attn=None, lips_rect=None,
-                    extra=None, lambda_dssim=0.2, w_alpha=1e-3, w_attn=1e-4, w_extra=1e-5, hair_mask_iter=False):
+                    extra=None, lambda_dssim=0.2, w_alpha=1e-3, w_attn=1e-4, w_extra=1e-5, hair_mask_iter=False,
+                    w_lips=None):
     """Plain-torch statement of train_face.py:415-416, 426-456, 508-575 -> (loss, Ll1).  `alpha` / `attn` /
-    `extra` None drops the corresponding warm-stage terms.  lips_rect = (r0, r1, c0, c1) indexes attn[1, r0:r1, c0:c1]."""
+    `extra` None drops the corresponding warm-stage terms.  lips_rect = (r0, r1, c0, c1) indexes attn[1, r0:r1, c0:c1].
+    ``w_lips``: weight of the lips term (default: w_attn; pretrain_face.py:142 uses 5e-3, its hair terms 1e-4)."""
+    w_lips = w_attn if w_lips is None else w_lips
     head = face_mask | hair_mask
     bg3 = bg[:, None, None]
     keep = head & ~mouth_mask
@@ -202,7 +205,7 @@ def face_loss_torch(image, gt, face_mask, hair_mask, mouth_mask, bg, alpha=None,
     if attn is not None:
         if lips_rect is not None:
             r0, r1, c0, c1 = [int(v) for v in (lips_rect.tolist() if torch.is_tensor(lips_rect) else lips_rect)]
-            loss = loss + w_attn * attn[1, r0:r1, c0:c1].mean()
+            loss = loss + w_lips * attn[1, r0:r1, c0:c1].mean()
         if not hair_mask_iter:
             hair = hair_mask.to(attn.dtype)
             cnt = hair.sum().clamp_min(1.0)
@@ -312,17 +315,19 @@ class _FusedFaceLoss(torch.autograd.Function):
 
 
 def face_loss(image, gt, face_mask, hair_mask, mouth_mask, bg, alpha=None, attn=None, lips_rect=None, extra=None,
-              lambda_dssim=0.2, w_alpha=1e-3, w_attn=1e-4, w_extra=1e-5, hair_mask_iter=False):
-    """Loss block of the face branch -> (loss, Ll1); fused HIP kernels on the device, face_loss_torch otherwise."""
+              lambda_dssim=0.2, w_alpha=1e-3, w_attn=1e-4, w_extra=1e-5, hair_mask_iter=False, w_lips=None):
+    """Loss block of the face branch -> (loss, Ll1); fused HIP kernels on the device, face_loss_torch otherwise.
+    ``w_lips``: weight of the attention map's lips term (default: w_attn, the hair terms' weight)."""
     if not (image.is_cuda and image.dim() == 3 and image.shape[0] == 3):
         return face_loss_torch(image, gt, face_mask, hair_mask, mouth_mask, bg, alpha, attn, lips_rect, extra,
-                               lambda_dssim, w_alpha, w_attn, w_extra, hair_mask_iter)
+                               lambda_dssim, w_alpha, w_attn, w_extra, hair_mask_iter, w_lips)
     flags = (FLAG_HAIR_TO_BG if hair_mask_iter else 0) | (FLAG_ALPHA if alpha is not None else 0)
     if attn is not None:
         flags |= (FLAG_LIPS if lips_rect is not None else 0) | (0 if hair_mask_iter else FLAG_HAIR_ATTN)
     if lips_rect is not None and not torch.is_tensor(lips_rect):
         lips_rect = torch.tensor(list(lips_rect), dtype=torch.int32, device=image.device)
-    cfg = (flags, float(lambda_dssim), float(w_alpha), float(w_attn), float(w_attn), float(w_extra))
+    cfg = (flags, float(lambda_dssim), float(w_alpha), float(w_attn), float(w_attn if w_lips is None else w_lips),
+           float(w_extra))
     return _FusedFaceLoss.apply(image, alpha, attn, extra, gt, face_mask, hair_mask, mouth_mask, bg, lips_rect, cfg)
 
 

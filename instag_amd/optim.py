@@ -288,3 +288,58 @@ class CombinedAdam(MultiTensorAdam):
         self._layout_key = None
         for o in self.optimizers:
             o.invalidate()
+
+
+_EMA_TENSOR_DT = np.dtype([("p", "<u8"), ("m", "<u8"), ("v", "<u8"), ("s", "<u8"), ("n", "<i8"), ("group", "<i4"),
+                           ("pad", "<i4")])
+
+
+class MultiTensorAdamEMA(MultiTensorAdam):
+    """MultiTensorAdam whose launch also updates an exponential moving average of every parameter (pretrain_face.py:
+    187-193: motion_optimizer.step() and ema_motion_net.update() back to back, csrc/adam.hip adam_ema_step_kernel).
+    ``ema`` holds the shadows and the device-side update counter (pretrain.MotionEMA); every parameter of the groups
+    needs a shadow.  The counter lives on the device, so a replayed graph advances it."""
+
+    def __init__(self, params, ema, **kw):
+        super().__init__(params, **kw)
+        self.ema = ema
+        self._ema_key = None
+
+    def _ema_table(self, tensors):
+        if self._ema_key == self._layout_key:
+            return
+        shadow = {id(p): s for p, s in zip(self.ema.params, self.ema.shadow_params)}
+        arr = np.zeros(len(tensors), dtype=_EMA_TENSOR_DT)
+        for i, (p, _, m, v, gi) in enumerate(tensors):
+            s = shadow[id(p)]
+            assert s.is_contiguous() and s.shape == p.shape
+            arr[i] = (p.data_ptr(), m.data_ptr(), v.data_ptr(), s.data_ptr(), p.numel(), gi, 0)
+        self._ema_dev = torch.from_numpy(arr.view(np.uint8).copy()).to(self._dev)
+        self._ema_key = self._layout_key
+
+    @torch.no_grad()
+    def prepare(self):
+        tensors = self._gather()
+        if tensors:
+            self._layout(tensors)
+            self._ema_table(tensors)
+
+    @torch.no_grad()
+    def step(self, part=None):
+        assert part is None, "MultiTensorAdamEMA steps all of its tensors in one launch"
+        L = _lib.lib()
+        tensors = self._gather()
+        if not tensors:
+            return
+        if len(tensors) > L.instag_adam_grads_max():
+            raise RuntimeError("MultiTensorAdamEMA: more tensors than one launch's gradient table holds")
+        self._layout(tensors)
+        self._ema_table(tensors)
+        self._keep = [t[1] for t in tensors]
+        gh = self._grads_host
+        for i, t in enumerate(tensors):
+            gh[i] = 0 if t[1] is None else t[1].data_ptr()
+        check(L.instag_adam_ema_step(ptr(self._ema_dev), gh.ctypes.data, len(tensors), ptr(self._groups_dev),
+                                     ptr(self._lr_dev), ptr(self._chunks), self._chunks.shape[0], ptr(self._step),
+                                     ptr(self._tickets), ptr(self.ema.counter), float(self.ema.decay),
+                                     _lib.current_stream()), "adam_ema_step")

@@ -1,0 +1,440 @@
+"""Identity-free pretraining of the universal motion field (UMF) over K identities.
+
+Counterpart of /root/reference/pretrain_face.py:34-522 restricted to the step, as train.py is for train_face.py.  Each
+identity has its own Gaussians and personalised motion field (PMF); one UMF is shared by all of them and is what the
+stage produces: ``chkpnt_ema_face_latest.pth``, the file train_face.py:66-68 starts the face adaptation from
+(load_pretrained_motion).  An iteration trains the identity the caller picks (IdentitySampler mirrors the reference's
+``randint(0, K - 1)``):
+  render (static before warm_step, then render_motion(personalized=True, align=False, return_attn=True))
+  -> L1 + lambda * DSSIM with the mouth / hair painting of the face branch, and after warm_step: the regularisers of both
+     fields, the alpha term, the contrast of the identity's PMF against the other identities' PMFs, the attention terms
+  -> backward -> statistics / density control of that identity -> AdamW (UMF) + Adam (identity) -> EMA of the UMF.
+
+On the device the deformation, every per-Gaussian loss term and the contrast are one operator (glue.pretrain_deform),
+the personalised attention map's lips term rides in the loss kernel's extra array (glue.window_mean_append), and the
+EMA is part of the UMF's AdamW launch (optim.MultiTensorAdamEMA).  LPIPS (never reached: lpips_start = 99999999 K), the
+mouth-opening / AU frame curriculum, logging and validation renders are out of scope.
+"""
+from __future__ import annotations
+
+import contextlib
+import os
+import random
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import diff_gauss, graphs
+from .gaussian_model import GaussianModel, OptimizationParams
+from .losses import face_loss
+
+
+# ---- schedule (pretrain_face.py:48-67: every boundary scaled by the number of identities K) --------------------------
+@dataclass(frozen=True)
+class PretrainSchedule:
+    iterations: int           # opt.iterations * K
+    warm_step: int            # 1000 K
+    densify_until: int        # (opt.iterations - 1000) K
+    mouth_select_iter: int    # (opt.iterations - 10000) K
+    lpips_start: int          # 99999999 K (no LPIPS, no mouth-mask dilation)
+
+
+def pretrain_schedule(K: int, opt=OptimizationParams) -> PretrainSchedule:
+    return PretrainSchedule(iterations=opt.iterations * K, warm_step=1000 * K,
+                            densify_until=(opt.iterations - 1000) * K,
+                            mouth_select_iter=(opt.iterations - 10000) * K, lpips_start=99999999 * K)
+
+
+@dataclass(frozen=True)
+class PretrainPhase:
+    """What a pretraining iteration computes."""
+    motion: bool = True            # render_motion(personalized=True) instead of the static render (it >= warm_step)
+    warm: bool = True              # it > warm_step: regularisers, alpha, contrast and attention terms
+    hair_mask_iter: bool = False   # hair painted to background in image and target, hair attention terms off
+
+
+def pretrain_phase(iteration: int, K: int, opt=OptimizationParams, hair_mask_interval: int = 7) -> PretrainPhase:
+    s = pretrain_schedule(K, opt)
+    it = iteration
+    hair = (s.warm_step < it < s.lpips_start - 1000) and it % hair_mask_interval != 0
+    return PretrainPhase(motion=it >= s.warm_step, warm=it > s.warm_step, hair_mask_iter=hair)
+
+
+def motion_lr_lambda(i: int, K: int, opt=OptimizationParams) -> float:
+    """The UMF's LambdaLR factor (pretrain_face.py:42)."""
+    s = pretrain_schedule(K, opt)
+    return 0.5 ** (i / s.mouth_select_iter) if i < s.mouth_select_iter else 0.1 ** (i / s.iterations)
+
+
+class IdentitySampler:
+    """The identity of each iteration, ``randint(0, K - 1)`` from a seeded generator (pretrain_face.py:55)."""
+
+    def __init__(self, K: int, seed: int = 0):
+        self.K = int(K)
+        self.rng = random.Random(seed)
+
+    def __call__(self) -> int:
+        return self.rng.randint(0, self.K - 1)
+
+
+# ---- EMA of the UMF (torch_ema 0.3 ExponentialMovingAverage(parameters, decay=0.995)) ---------------------------------
+class MotionEMA:
+    """Shadows = clones of the parameters at construction; update(): n += 1, d = min(decay, (1 + n) / (10 + n)),
+    s -= (1 - d) (s - p) for EVERY tensor.  ``counter`` = int32 [n, ticket] on the parameters' device: on the GPU the
+    update is part of the UMF's AdamW launch (optim.MultiTensorAdamEMA), which advances n there; update() is the
+    host-side statement of the same arithmetic."""
+
+    def __init__(self, parameters, decay: float = 0.995):
+        self.params = list(parameters)
+        self.decay = float(decay)
+        self.shadow_params = [p.detach().clone().contiguous() for p in self.params]
+        self.counter = torch.zeros(2, dtype=torch.int32, device=self.params[0].device)
+
+    @property
+    def num_updates(self) -> int:
+        return int(self.counter[0])
+
+    @torch.no_grad()
+    def update(self):
+        n = self.num_updates + 1
+        self.counter[0] = n
+        one_minus_decay = 1.0 - min(self.decay, (1 + n) / (10 + n))
+        for s, p in zip(self.shadow_params, self.params):
+            tmp = s - p
+            tmp.mul_(one_minus_decay)
+            s.sub_(tmp)
+
+    @contextlib.contextmanager
+    def average_parameters(self):
+        """The parameters hold the shadows inside the block (in place: captured graphs stay valid) and their own values
+        again afterwards."""
+        backup = [p.detach().clone() for p in self.params]
+        with torch.no_grad():
+            for p, s in zip(self.params, self.shadow_params):
+                p.copy_(s)
+        try:
+            yield
+        finally:
+            with torch.no_grad():
+                for p, b in zip(self.params, backup):
+                    p.copy_(b)
+
+
+# ---- checkpoints in the reference's formats (pretrain_face.py:160-171) -------------------------------------------------
+def load_pretrained_motion(motion_net, path: str):
+    """train_face.py:66-68: ``(motion_params, _, _) = torch.load(pretrain_ckpt_path)``, loaded into the UMF."""
+    motion_params, _, _ = torch.load(path, map_location=next(motion_net.parameters()).device, weights_only=False)
+    motion_net.load_state_dict(motion_params)
+    return motion_net
+
+
+# ---- the other identities' personalised fields, without gradient ------------------------------------------------------
+@torch.no_grad()
+def other_pmf_heads(pmfs: Sequence[torch.nn.Module], xyz, audio, exp) -> List[torch.Tensor]:
+    """The deformation heads h_j [N,11] of the other identities' PMFs at the trained identity's positions
+    (pretrain_face.py:136): only ``_h`` -- the alignment head, whose output the contrast never reads, is skipped.  On
+    the device each is the forward-only tri-plane encode, shared attention MLPs and glue + sigma_net kernels."""
+    out = []
+    for net in pmfs:
+        enc_x = net.encode_x(xyz, bound=net.bound)
+        out.append(net._trunk(xyz, audio, exp, None, enc_x=enc_x)[3])
+    return out
+
+
+class PretrainFaceTrainer:
+    """K identities (GaussianModel with its PMF in ``neural_motion_grid``, each with its own training_setup optimizer)
+    and one UMF with AdamW(get_params(5e-3, 5e-4), betas (0.9, 0.99), eps 1e-8, weight decay 0.01: pretrain_face.py:135
+    passes none, so torch's default applies) and its EMA."""
+
+    def __init__(self, identities: Sequence[GaussianModel], motion_net, background, opt=OptimizationParams,
+                 names: Optional[Sequence[str]] = None, cameras_extent: float = 0.2, densify: bool = True,
+                 seed: int = 0, share_audio_net: bool = False):
+        if share_audio_net:
+            raise NotImplementedError(
+                "share_audio_net: the UMF's audio-net tensors would sit in the UMF's optimizer and in every identity's "
+                "optimizer, and one fused Adam launch over both would update the same tensors twice, racing")
+        self.ids = list(identities)
+        self.K = len(self.ids)
+        assert self.K >= 1
+        self.names = list(names) if names is not None else [f"id{i}" for i in range(self.K)]
+        self.motion_net = motion_net
+        self.bg = background
+        self.opt = opt
+        self.sched = pretrain_schedule(self.K, opt)
+        self.extent = cameras_extent
+        self.densify = densify
+        self.iteration = 0
+        dev = self.ids[0].get_xyz.device
+        self.device = dev
+        self.on_gpu = dev.type == "cuda"
+        self.gen = torch.Generator(device=dev).manual_seed(seed)
+        self.ema = MotionEMA(motion_net.parameters(), decay=0.995)
+        groups = motion_net.get_params(5e-3, 5e-4)
+        self._motion_base_lr = [float(g["lr"]) for g in groups]
+        if self.on_gpu:
+            from . import _lib
+            from .optim import MultiTensorAdamEMA
+            if self.K - 1 > _lib.lib().instag_pretrain_deform_max_others():
+                raise ValueError(f"at most {_lib.lib().instag_pretrain_deform_max_others() + 1} identities")
+            self.motion_optimizer = MultiTensorAdamEMA(groups, self.ema, lr=5e-3, betas=(0.9, 0.99), eps=1e-8,
+                                                       weight_decay=0.01, decoupled=True)
+        else:
+            self.motion_optimizer = torch.optim.AdamW(groups, lr=5e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01)
+        for g in self.ids:
+            g.training_setup(opt, fused=self.on_gpu)
+        self._set_motion_lr(0)
+        self.last = {}
+        self._graph_mode = None       # set by enable_graph
+        self._graph_cache = {}        # _key -> _PretrainGraph
+        self._pool = None             # one private memory pool for every capture of this trainer
+        self.captures = 0
+
+    # ---- learning rates --------------------------------------------------------------------------------------------
+    def _set_motion_lr(self, i):
+        f = motion_lr_lambda(i, self.K, self.opt)
+        for grp, base in zip(self.motion_optimizer.param_groups, self._motion_base_lr):
+            grp["lr"] = base * f
+        if hasattr(self.motion_optimizer, "set_lrs"):
+            self.motion_optimizer.set_lrs()
+
+    def _set_learning_rates(self, idx, it):
+        self._set_motion_lr(it - 1)             # LambdaLR: step `it` runs with lambda(it - 1)
+        g = self.ids[idx]
+        g.update_learning_rate(it)
+        if hasattr(g.optimizer, "set_lrs"):
+            g.optimizer.set_lrs()
+
+    # ---- forward + loss + backward ---------------------------------------------------------------------------------
+    def forward_loss(self, idx: int, frame, phase: PretrainPhase):
+        """-> (pkg, loss, Ll1) of identity ``idx`` on ``frame`` (no backward)."""
+        from .renderer import render, render_motion
+        g = self.ids[idx]
+        dev = self.device
+        td = frame.talking_dict
+        face, hair, mouth = td["face_mask"].to(dev), td["hair_mask"].to(dev), td["mouth_mask"].to(dev)
+        gt = frame.original_image.to(dev)
+        if not phase.motion:
+            pkg = render(frame, g, None, self.bg)
+            loss, l1 = face_loss(pkg["render"], gt, face, hair, mouth, self.bg, lambda_dssim=self.opt.lambda_dssim)
+            return pkg, loss, l1
+        heads = []
+        if phase.warm and self.K > 1:
+            heads = other_pmf_heads([o.neural_motion_grid for j, o in enumerate(self.ids) if j != idx], g.get_xyz,
+                                    td["auds"].to(dev), td["au_exp"].to(dev))
+        pkg = render_motion(frame, g, self.motion_net, None, self.bg, return_attn=True, personalized=True,
+                            align=False, pretrain_heads=heads, pretrain_reg=phase.warm)
+        if not phase.warm:
+            loss, l1 = face_loss(pkg["render"], gt, face, hair, mouth, self.bg, lambda_dssim=self.opt.lambda_dssim)
+            return pkg, loss, l1
+        from .glue import window_mean_append
+        lips = td["lips_rect"].to(dev)
+        extra = window_mean_append(pkg["p_attn"], pkg["motion_reg"], lips, 1, 5e-3)
+        loss, l1 = face_loss(pkg["render"], gt, face, hair, mouth, self.bg, alpha=pkg["alpha"], attn=pkg["attn"],
+                             lips_rect=lips, extra=extra, lambda_dssim=self.opt.lambda_dssim, w_alpha=1e-3,
+                             w_attn=1e-4, w_lips=5e-3, w_extra=1.0, hair_mask_iter=phase.hair_mask_iter)
+        return pkg, loss, l1
+
+    def _forward_backward(self, idx, frame, phase):
+        from .losses import defer_finalize
+        from .train_stages import _backward
+        with defer_finalize():          # (backward follows at once; the loss value is read after the step)
+            pkg, loss, l1 = self.forward_loss(idx, frame, phase)
+        _backward(loss, self.device)
+        return pkg, loss, l1
+
+    # ---- statistics, density control ------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _update_stats(self, g: GaussianModel, pkg):
+        from .glue import densify_stats
+        densify_stats(pkg["viewspace_points"].grad, pkg["radii"], g.max_radii2D, g.xyz_gradient_accum, g.denom, None)
+
+    def _density_due(self, it):
+        o = self.opt
+        return self.densify and it > o.densify_from_iter and it % o.densification_interval == 0
+
+    @torch.no_grad()
+    def _density_control(self, g: GaussianModel, it, frame):
+        """pretrain_face.py:172-186: densify_and_prune (before densify_until), then the green-Gaussian prune (no bound).
+        No opacity reset: pretrain_face.py has none."""
+        o, s = self.opt, self.sched
+        if it < s.densify_until:
+            size_threshold = 20 if it > o.opacity_reset_interval else None
+            g.densify_and_prune(o.densify_grad_threshold, 0.05 + 0.25 * it / s.densify_until, self.extent,
+                                size_threshold, generator=self.gen)
+        from .gaussian_model import sh_to_rgb
+        rgb = sh_to_rgb(g.active_sh_degree, g.get_features, g.get_xyz, frame.camera_center.to(self.device))
+        g.prune_points((rgb[:, 0] < 30 / 255) & (rgb[:, 1] > 225 / 255) & (rgb[:, 2] < 30 / 255))
+
+    # ---- one iteration ---------------------------------------------------------------------------------------------
+    def _body(self, idx, frame, phase, stats_on: bool, steps: bool, density_it: Optional[int] = None):
+        """One iteration of identity ``idx`` in the reference's order: forward, loss, backward, statistics, [density
+        control at iteration ``density_it``], optimizers (+ EMA).  Free of host round trips without density control
+        (the captured form)."""
+        g = self.ids[idx]
+        pkg, loss, l1 = self._forward_backward(idx, frame, phase)
+        with torch.no_grad():
+            if stats_on:
+                self._update_stats(g, pkg)
+            if density_it is not None:
+                self._density_control(g, density_it, frame)
+            if steps:
+                self.motion_optimizer.step()          # (+ the EMA update, same launch)
+                g.optimizer.step()
+            self.motion_optimizer.zero_grad(set_to_none=True)
+            g.optimizer.zero_grad(set_to_none=True)
+        return pkg, loss, l1
+
+    def _key(self, idx, it):
+        """What a captured step of identity ``idx`` at iteration ``it`` bakes in."""
+        return (idx, pretrain_phase(it, self.K, self.opt), it < self.sched.densify_until, it < self.sched.iterations,
+                self.ids[idx].active_sh_degree)
+
+    def step(self, idx: int, frame):
+        """One iteration on identity ``idx`` (pretrain_face.py:53-193, in its order).  In graph mode a step without a
+        density-control event replays the captured step of its (identity, phase) key, capturing it first if needed."""
+        if not self.on_gpu:
+            raise RuntimeError("PretrainFaceTrainer.step runs on the GPU (the pretraining operators are HIP kernels)")
+        self.iteration += 1
+        it = self.iteration
+        g = self.ids[idx]
+        phase = pretrain_phase(it, self.K, self.opt)
+        self._set_learning_rates(idx, it)
+        if it % 1000 == 0:
+            g.oneupSHdegree()
+        due = self._density_due(it)
+        stats_on, steps = it < self.sched.densify_until, it < self.sched.iterations
+        if self._graph_mode is not None and not due:
+            key = self._key(idx, it)
+            gs = self._graph_cache.get(key)
+            if gs is None:
+                gs = self._graph_cache[key] = self._capture(idx, frame, key)
+                self.captures += 1
+            gs.replay(frame)
+            loss, l1 = gs.loss, gs.l1
+            if gs.check_due() and gs.check_overflow():
+                # a replayed step needed more instances than its capacity (image truncated to the nearest Gaussians):
+                # captured again, sized from fresh counts, when the key comes back
+                del self._graph_cache[key]
+        else:
+            # eager launches in exact mode: another identity's plan must not size this step's rasterizer calls
+            diff_gauss.set_capacity_plan(None)
+            pkg, loss, l1 = self._body(idx, frame, phase, stats_on, steps, it if due else None)
+            del pkg
+            if due:
+                # identity idx's parameter set changed: its captured steps are stale (the others' are not -- they read
+                # only its personalised field, which density control leaves as it is)
+                self._graph_cache = {k: v for k, v in self._graph_cache.items() if k[0] != idx}
+        self.last = dict(loss=loss.detach(), l1=l1.detach(), identity=idx, num_points=g.num_points, phase=phase)
+        return self.last
+
+    # ---- graph mode --------------------------------------------------------------------------------------------------
+    def enable_graph(self, headroom: float = 1.5, warmup_steps: int = 2):
+        """Switch graph mode on.  Steps are captured lazily, one per (identity, phase, statistics on, optimizers on,
+        SH degree), all into one private memory pool (graphs.py protocol).  A capture does NOT consume iterations: its
+        warm-up steps run on the current state, which is put back before the capture (parameters, optimizer moments and
+        step counters, EMA shadows and counter, densification statistics).  Density-control iterations run eagerly and
+        drop the identity's captured steps; an overflow of a step's instance capacity drops that step."""
+        assert self.on_gpu, "graph mode needs the GPU"
+        if self._pool is None:
+            from . import _lib
+            self._pool = _lib.GraphPool(self.device)
+        self._graph_mode = dict(headroom=float(headroom), warmup_steps=max(1, int(warmup_steps)))
+
+    def disable_graph(self):
+        self._graph_cache = {}
+        self._graph_mode = None
+        diff_gauss.set_capacity_plan(None)
+
+    def _state_tensors(self, idx):
+        """Every tensor a step of identity ``idx`` writes that outlives the step (optimizer state created first)."""
+        g = self.ids[idx]
+        self.motion_optimizer.prepare()
+        g.optimizer.prepare()
+        ts = [p.data for p in self.motion_net.parameters()] + list(self.ema.shadow_params) + [self.ema.counter]
+        ts += [p.data for p in g._p.values()] + [p.data for p in g.neural_motion_grid.parameters()]
+        for o in (self.motion_optimizer, g.optimizer):
+            for grp in o.param_groups:
+                for p in grp["params"]:
+                    st = o.state.get(p)
+                    if st:
+                        ts += [st[k] for k in ("exp_avg", "exp_avg_sq", "step") if torch.is_tensor(st.get(k))]
+        return ts + [g.xyz_gradient_accum, g.denom, g.max_radii2D]
+
+    def _capture(self, idx, frame, key):
+        _, phase, stats_on, steps, _ = key
+        mode, dev, it = self._graph_mode, self.device, self.iteration
+        static = frame.clone_static()
+        ts = self._state_tensors(idx)
+        saved = [t.detach().clone() for t in ts]
+
+        def pre():
+            self._set_learning_rates(idx, it)
+
+        def one_step():
+            self._body(idx, static, phase, stats_on, steps)
+
+        counts = graphs.measure(one_step, mode["warmup_steps"], pre)
+        plan = graphs.install(graphs.stage_capacities(counts, mode["headroom"]), dev)
+        graphs.warm(plan, one_step, dev, pre)
+        with torch.no_grad():
+            for t, s in zip(ts, saved):
+                t.copy_(s)
+        del saved
+        self._set_learning_rates(idx, it)
+        graph = torch.cuda.CUDAGraph()
+        with graphs.capture(graph, plan, False, pool=self._pool.handle):
+            pkg, loss, l1 = self._body(idx, static, phase, stats_on, steps)
+        del pkg
+        return _PretrainGraph(graph, plan, static, loss.detach(), l1.detach())
+
+    # ---- checkpoints (pretrain_face.py:160-171) ----------------------------------------------------------------------
+    def save_checkpoints(self, root: str):
+        """<root>/chkpnt_face_latest.pth = (UMF state_dict, optimizer state_dict, iteration); chkpnt_ema_face_latest.pth =
+        the same with the EMA weights; <root>/<name>/chkpnt_face_{iteration,latest}.pth = (gaussians.capture(), UMF
+        state_dict, optimizer state_dict, iteration) per identity."""
+        it = self.iteration
+        os.makedirs(root, exist_ok=True)
+        torch.save((self.motion_net.state_dict(), self.motion_optimizer.state_dict(), it),
+                   os.path.join(root, "chkpnt_face_latest.pth"))
+        with self.ema.average_parameters():
+            # (state_dict() aliases the parameters: it is written while they hold the shadows)
+            torch.save((self.motion_net.state_dict(), self.motion_optimizer.state_dict(), it),
+                       os.path.join(root, "chkpnt_ema_face_latest.pth"))
+        for name, g in zip(self.names, self.ids):
+            d = os.path.join(root, name)
+            os.makedirs(d, exist_ok=True)
+            ckpt = (g.capture(), self.motion_net.state_dict(), self.motion_optimizer.state_dict(), it)
+            torch.save(ckpt, os.path.join(d, f"chkpnt_face_{it}.pth"))
+            torch.save(ckpt, os.path.join(d, "chkpnt_face_latest.pth"))
+
+
+class _PretrainGraph(graphs.CapturedStep):
+    """One captured pretraining step with its capacity plan, static frame and (detached) loss outputs."""
+
+    def __init__(self, graph, plan, static, loss, l1):
+        self.graph, self.plan, self.static, self.loss, self.l1 = graph, plan, static, loss, l1
+
+    def replay(self, frame):
+        self._replays += 1
+        self.static.copy_from(frame)
+        self.graph.replay()
+
+
+def build_pretrainer(K: int, n_gaussians: int, device, sh_degree: int = 1, seed: int = 0, opt=OptimizationParams,
+                     densify: bool = False) -> PretrainFaceTrainer:
+    """Synthetic K-identity pretrainer: K clouds of n_gaussians (different seeds) with their PMFs, one UMF."""
+    from types import SimpleNamespace
+    from .motion_net import MotionNetwork, PersonalizedMotionNetwork
+    from .scene_synth import synthetic_gaussians
+    torch.manual_seed(seed)
+    args = SimpleNamespace(audio_extractor="deepspeech", type="face")
+    ids = []
+    for k in range(K):
+        pmf = PersonalizedMotionNetwork(args=args).to(device)
+        g = GaussianModel(sh_degree, neural_motion_grid=pmf)
+        g.load_raw(synthetic_gaussians(n_gaussians, sh_degree=sh_degree, seed=seed + k), device)
+        ids.append(g)
+    umf = MotionNetwork(args=args).to(device)
+    bg = torch.tensor([0.0, 1.0, 0.0], device=device)
+    return PretrainFaceTrainer(ids, umf, bg, opt=opt, densify=densify, seed=seed)

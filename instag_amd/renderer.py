@@ -148,10 +148,15 @@ def _ones(like):
 
 
 def render_motion(viewpoint_camera, pc, motion_net, pipe=None, bg_color=None, scaling_modifier=1.0, frame_idx=None,
-                  return_attn=False, personalized=False, align=False, detach_motion=False, motion_reg_weight=None):
+                  return_attn=False, personalized=False, align=False, detach_motion=False, motion_reg_weight=None,
+                  pretrain_heads=None, pretrain_reg=True):
     """Render with the universal (motion_net) and personalised (pc.neural_motion_grid) motion fields.
     ``motion_reg_weight`` (extension): also return ``motion_reg`` = partial sums of weight * the motion regulariser of
-    train_face.py:510-514, computed inside the fused deform operator (None when that operator is not used)."""
+    train_face.py:510-514, computed inside the fused deform operator (None when that operator is not used).
+    ``pretrain_heads`` (extension, personalized=True and align=False only): the other identities' PMF head outputs
+    [N,11] of the pretraining step (pretrain_face.py); the deformation runs in the pretraining operator
+    (glue.pretrain_deform) and ``motion_reg`` holds partial sums of that step's regularisers and contrast term
+    (``pretrain_reg=False``: not computed, ``motion_reg`` is None)."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
                                               getattr(pipe, "debug", False)))
@@ -212,7 +217,28 @@ def render_motion(viewpoint_camera, pc, motion_net, pipe=None, bg_color=None, sc
     fused_pers = (align and personalized and not detach_motion and pc.get_xyz.is_cuda and motion_reg_weight is None
                   and motion_preds.get("_h") is not None and dict.get(p_motion_preds, "_p") is not None
                   and dict.get(p_motion_preds, "_h") is not None and motion_preds["_h"].shape[-1] == 11)
-    if fused_pers:
+    if pretrain_heads is not None:
+        if not (personalized and not align and not detach_motion and pc.get_xyz.is_cuda
+                and torch.is_tensor(motion_preds.get("_h")) and motion_preds["_h"].shape[-1] == 11
+                and dict.get(p_motion_preds, "_h") is not None):
+            raise RuntimeError("pretrain_heads: the pretraining deform operator needs personalized=True, align=False, "
+                               "both fields' fused heads and the GPU")
+        from .glue import pretrain_deform
+        h_u, h_p = motion_preds["_h"], p_motion_preds["_h"]
+        outs_d = pretrain_deform(xyz_route, pc._scaling, pc._rotation, pc._opacity, h_u, h_p, pretrain_heads,
+                                 with_reg=pretrain_reg)
+        means3D, scales, rotations, opacity = outs_d[:4]
+        motion_reg = outs_d[4] if pretrain_reg else None
+        # (the reference's in-place additions to the returned dictionary / motion_net.cache, rebuilt on access)
+        motion_preds["d_xyz"] = lambda: h_u[..., :3] * 1e-2 + h_p[..., :3] * 1e-2
+        motion_preds["d_scale"] = lambda: h_u[..., 8:11] + h_p[..., 8:11]
+        motion_preds["d_rot"] = lambda: h_u[..., 3:7] + h_p[..., 3:7]
+        if getattr(motion_net, "cache", None) is not None:
+            hd, pd = h_u.detach(), h_p.detach()
+            motion_net.cache["d_xyz"] = lambda: hd[..., :3] * 1e-2 + pd[..., :3] * 1e-2
+            motion_net.cache["d_scale"] = lambda: hd[..., 8:11] + pd[..., 8:11]
+            motion_net.cache["d_rot"] = lambda: hd[..., 3:7] + pd[..., 3:7]
+    elif fused_pers:
         from .glue import deform_activate
         h_sum = motion_preds["_h"] + p_motion_preds["_h"]
         p_ = p_route if p_route is not None else p_motion_preds["_p"]
