@@ -134,6 +134,31 @@ def _flush(jobs):
                 w.grad = dw if w.grad is None else w.grad.add_(dw)
 
 
+_ONE = {}
+
+
+def root_gradient(loss):
+    """The scalar one a backward pass starts from, cached per (device, dtype): no fill launch per step.  A tensor made
+    while a capture runs belongs to that graph's memory pool, so it is never cached."""
+    key = (loss.device, loss.dtype)
+    one = _ONE.get(key)
+    if one is None:
+        one = torch.ones((), dtype=loss.dtype, device=loss.device)
+        if not torch.cuda.is_current_stream_capturing():
+            _ONE[key] = one
+    return one
+
+
+def backward(loss, device):
+    """loss.backward() with the MLPs' weight-gradient GEMMs batched into one launch behind it; on the device the root
+    gradient is root_gradient(loss)."""
+    with deferred_grads(device if device.type == "cuda" else None):
+        if device.type == "cuda" and loss.dim() == 0:
+            loss.backward(gradient=root_gradient(loss))
+        else:
+            loss.backward()
+
+
 class deferred_grads:
     def __init__(self, device):
         self.device = None if device is None else torch.device(device)

@@ -98,6 +98,14 @@ def sh_to_rgb(deg: int, features: torch.Tensor, xyz: torch.Tensor, camera_center
     return torch.clamp_min(rgb + 0.5, 0.0)
 
 
+def green_mask(g: "GaussianModel", camera_center: torch.Tensor, thresholds) -> torch.Tensor:
+    """The Gaussians that took the background's green seen from camera_center (train_face.py:729-741): with
+    ``thresholds`` = (r, g, b) in 1/255, red below r, green above g and blue below b."""
+    r, gr, b = thresholds
+    rgb = sh_to_rgb(g.active_sh_degree, g.get_features, g.get_xyz, camera_center)
+    return (rgb[:, 0] < r / 255) & (rgb[:, 1] > gr / 255) & (rgb[:, 2] < b / 255)
+
+
 class OptimizationParams:
     """Hot-path values of /root/reference/arguments/__init__.py:79-99."""
     iterations = 10000

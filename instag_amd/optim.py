@@ -343,3 +343,62 @@ class MultiTensorAdamEMA(MultiTensorAdam):
                                      ptr(self._lr_dev), ptr(self._chunks), self._chunks.shape[0], ptr(self._step),
                                      ptr(self._tickets), ptr(self.ema.counter), float(self.ema.decay),
                                      _lib.current_stream()), "adam_ema_step")
+
+
+def make_motion_optimizer(motion_net, on_gpu: bool, ema=None):
+    """AdamW of a motion field over ``get_params(5e-3, 5e-4)`` (train_face.py:59, train_mouth.py:63, pretrain_face.py:135:
+    betas (0.9, 0.99), eps 1e-8, weight decay 0.01): one fused launch on the GPU -- with ``ema``, the launch that also
+    updates the EMA -- torch.optim.AdamW on the CPU."""
+    groups = motion_net.get_params(5e-3, 5e-4)
+    kw = dict(lr=5e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01)
+    if not on_gpu:
+        return torch.optim.AdamW(groups, **kw)
+    if ema is not None:
+        return MultiTensorAdamEMA(groups, ema, decoupled=True, **kw)
+    return MultiTensorAdam(groups, decoupled=True, **kw)
+
+
+def lambda_lr(optimizer, base_lrs, factor: float):
+    """LambdaLR's write: every group of ``optimizer`` runs at its base rate times ``factor``."""
+    for grp, base in zip(optimizer.param_groups, base_lrs):
+        grp["lr"] = base * factor
+
+
+class StepOptimizers:
+    """The optimizers one train step advances, in the order the reference steps them.  With ``combine`` and every member
+    fused, one CombinedAdam launches them together (and uploads their learning rates in one copy); ``partition`` is its
+    early / late split (CombinedAdam)."""
+
+    def __init__(self, *members, combine: bool = True, partition=None):
+        self.members = list(members)
+        fused = all(isinstance(o, MultiTensorAdam) for o in self.members)
+        self.combined = CombinedAdam(self.members, partition=partition) if combine and fused else None
+        self._launches = [self.combined] if self.combined is not None else self.members
+
+    def push_lrs(self):
+        """The groups' current learning rates to the device tables (one small copy per launch; none on the CPU)."""
+        for o in self._launches:
+            if hasattr(o, "set_lrs"):
+                o.set_lrs()
+
+    def step(self, part=None):
+        if self.combined is not None:
+            self.combined.step(part)
+            return
+        for o in self.members:
+            o.step()
+
+    def zero_grad(self):
+        for o in self.members:
+            o.zero_grad(set_to_none=True)
+
+    def prepare(self):
+        """Device-side tables brought up to date with the parameter set (no step): in front of a capture."""
+        for o in self._launches:
+            if hasattr(o, "prepare"):
+                o.prepare()
+
+    def states(self):
+        """The per-parameter state of every member (None where there is none yet) in a fixed order: members, groups,
+        parameters."""
+        return [o.state.get(p) for o in self.members for grp in o.param_groups for p in grp["params"]]

@@ -26,8 +26,11 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import diff_gauss, graphs
-from .gaussian_model import GaussianModel, OptimizationParams
+from .deferred import backward
+from .gaussian_model import GaussianModel, OptimizationParams, green_mask
 from .losses import face_loss
+from .optim import StepOptimizers, lambda_lr, make_motion_optimizer
+from .train import FACE_GREEN, densify_and_prune_at, restore_state, snapshot_state, update_densification_stats
 
 
 # ---- schedule (pretrain_face.py:48-67: every boundary scaled by the number of identities K) --------------------------
@@ -170,20 +173,17 @@ class PretrainFaceTrainer:
         self.on_gpu = dev.type == "cuda"
         self.gen = torch.Generator(device=dev).manual_seed(seed)
         self.ema = MotionEMA(motion_net.parameters(), decay=0.995)
-        groups = motion_net.get_params(5e-3, 5e-4)
-        self._motion_base_lr = [float(g["lr"]) for g in groups]
         if self.on_gpu:
             from . import _lib
-            from .optim import MultiTensorAdamEMA
             if self.K - 1 > _lib.lib().instag_pretrain_deform_max_others():
                 raise ValueError(f"at most {_lib.lib().instag_pretrain_deform_max_others() + 1} identities")
-            self.motion_optimizer = MultiTensorAdamEMA(groups, self.ema, lr=5e-3, betas=(0.9, 0.99), eps=1e-8,
-                                                       weight_decay=0.01, decoupled=True)
-        else:
-            self.motion_optimizer = torch.optim.AdamW(groups, lr=5e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01)
+        self.motion_optimizer = make_motion_optimizer(motion_net, self.on_gpu, ema=self.ema)
+        self._motion_base_lr = [float(g["lr"]) for g in self.motion_optimizer.param_groups]
         for g in self.ids:
             g.training_setup(opt, fused=self.on_gpu)
-        self._set_motion_lr(0)
+        # what a step of identity k advances: two launches, the UMF's AdamW + EMA, then the identity's Adam
+        self.optimizers = [StepOptimizers(self.motion_optimizer, g.optimizer, combine=False) for g in self.ids]
+        lambda_lr(self.motion_optimizer, self._motion_base_lr, motion_lr_lambda(0, self.K, opt))
         self.last = {}
         self._graph_mode = None       # set by enable_graph
         self._graph_cache = {}        # _key -> _PretrainGraph
@@ -191,19 +191,11 @@ class PretrainFaceTrainer:
         self.captures = 0
 
     # ---- learning rates --------------------------------------------------------------------------------------------
-    def _set_motion_lr(self, i):
-        f = motion_lr_lambda(i, self.K, self.opt)
-        for grp, base in zip(self.motion_optimizer.param_groups, self._motion_base_lr):
-            grp["lr"] = base * f
-        if hasattr(self.motion_optimizer, "set_lrs"):
-            self.motion_optimizer.set_lrs()
-
     def _set_learning_rates(self, idx, it):
-        self._set_motion_lr(it - 1)             # LambdaLR: step `it` runs with lambda(it - 1)
-        g = self.ids[idx]
-        g.update_learning_rate(it)
-        if hasattr(g.optimizer, "set_lrs"):
-            g.optimizer.set_lrs()
+        f = motion_lr_lambda(it - 1, self.K, self.opt)      # LambdaLR: step `it` runs with lambda(it - 1)
+        lambda_lr(self.motion_optimizer, self._motion_base_lr, f)
+        self.ids[idx].update_learning_rate(it)
+        self.optimizers[idx].push_lrs()
 
     # ---- forward + loss + backward ---------------------------------------------------------------------------------
     def forward_loss(self, idx: int, frame, phase: PretrainPhase):
@@ -237,18 +229,12 @@ class PretrainFaceTrainer:
 
     def _forward_backward(self, idx, frame, phase):
         from .losses import defer_finalize
-        from .train_stages import _backward
         with defer_finalize():          # (backward follows at once; the loss value is read after the step)
             pkg, loss, l1 = self.forward_loss(idx, frame, phase)
-        _backward(loss, self.device)
+        backward(loss, self.device)
         return pkg, loss, l1
 
-    # ---- statistics, density control ------------------------------------------------------------------------------
-    @torch.no_grad()
-    def _update_stats(self, g: GaussianModel, pkg):
-        from .glue import densify_stats
-        densify_stats(pkg["viewspace_points"].grad, pkg["radii"], g.max_radii2D, g.xyz_gradient_accum, g.denom, None)
-
+    # ---- density control ------------------------------------------------------------------------------------------
     def _density_due(self, it):
         o = self.opt
         return self.densify and it > o.densify_from_iter and it % o.densification_interval == 0
@@ -257,14 +243,9 @@ class PretrainFaceTrainer:
     def _density_control(self, g: GaussianModel, it, frame):
         """pretrain_face.py:172-186: densify_and_prune (before densify_until), then the green-Gaussian prune (no bound).
         No opacity reset: pretrain_face.py has none."""
-        o, s = self.opt, self.sched
-        if it < s.densify_until:
-            size_threshold = 20 if it > o.opacity_reset_interval else None
-            g.densify_and_prune(o.densify_grad_threshold, 0.05 + 0.25 * it / s.densify_until, self.extent,
-                                size_threshold, generator=self.gen)
-        from .gaussian_model import sh_to_rgb
-        rgb = sh_to_rgb(g.active_sh_degree, g.get_features, g.get_xyz, frame.camera_center.to(self.device))
-        g.prune_points((rgb[:, 0] < 30 / 255) & (rgb[:, 1] > 225 / 255) & (rgb[:, 2] < 30 / 255))
+        if it < self.sched.densify_until:
+            densify_and_prune_at(g, it, self.sched.densify_until, self.opt, self.extent, self.gen)
+        g.prune_points(green_mask(g, frame.camera_center.to(self.device), FACE_GREEN))
 
     # ---- one iteration ---------------------------------------------------------------------------------------------
     def _body(self, idx, frame, phase, stats_on: bool, steps: bool, density_it: Optional[int] = None):
@@ -275,14 +256,12 @@ class PretrainFaceTrainer:
         pkg, loss, l1 = self._forward_backward(idx, frame, phase)
         with torch.no_grad():
             if stats_on:
-                self._update_stats(g, pkg)
+                update_densification_stats(g, pkg["viewspace_points"].grad, pkg["radii"])
             if density_it is not None:
                 self._density_control(g, density_it, frame)
             if steps:
-                self.motion_optimizer.step()          # (+ the EMA update, same launch)
-                g.optimizer.step()
-            self.motion_optimizer.zero_grad(set_to_none=True)
-            g.optimizer.zero_grad(set_to_none=True)
+                self.optimizers[idx].step()          # (+ the EMA update, in the UMF's launch)
+            self.optimizers[idx].zero_grad()
         return pkg, loss, l1
 
     def _key(self, idx, it):
@@ -346,27 +325,17 @@ class PretrainFaceTrainer:
         self._graph_mode = None
         diff_gauss.set_capacity_plan(None)
 
-    def _state_tensors(self, idx):
-        """Every tensor a step of identity ``idx`` writes that outlives the step (optimizer state created first)."""
-        g = self.ids[idx]
-        self.motion_optimizer.prepare()
-        g.optimizer.prepare()
-        ts = [p.data for p in self.motion_net.parameters()] + list(self.ema.shadow_params) + [self.ema.counter]
-        ts += [p.data for p in g._p.values()] + [p.data for p in g.neural_motion_grid.parameters()]
-        for o in (self.motion_optimizer, g.optimizer):
-            for grp in o.param_groups:
-                for p in grp["params"]:
-                    st = o.state.get(p)
-                    if st:
-                        ts += [st[k] for k in ("exp_avg", "exp_avg_sq", "step") if torch.is_tensor(st.get(k))]
-        return ts + [g.xyz_gradient_accum, g.denom, g.max_radii2D]
-
     def _capture(self, idx, frame, key):
         _, phase, stats_on, steps, _ = key
         mode, dev, it = self._graph_mode, self.device, self.iteration
         static = frame.clone_static()
-        ts = self._state_tensors(idx)
-        saved = [t.detach().clone() for t in ts]
+        # every tensor a step of identity idx writes that outlives the step (the optimizer state created first)
+        g, opts = self.ids[idx], self.optimizers[idx]
+        opts.prepare()
+        ts = [p.data for p in self.motion_net.parameters()] + list(self.ema.shadow_params) + [self.ema.counter]
+        ts += [p.data for p in g._p.values()] + [p.data for p in g.neural_motion_grid.parameters()]
+        stats = (g.xyz_gradient_accum, g.denom, g.max_radii2D)
+        saved = snapshot_state(ts, opts, stats)
 
         def pre():
             self._set_learning_rates(idx, it)
@@ -377,9 +346,7 @@ class PretrainFaceTrainer:
         counts = graphs.measure(one_step, mode["warmup_steps"], pre)
         plan = graphs.install(graphs.stage_capacities(counts, mode["headroom"]), dev)
         graphs.warm(plan, one_step, dev, pre)
-        with torch.no_grad():
-            for t, s in zip(ts, saved):
-                t.copy_(s)
+        restore_state(saved, ts, opts, stats)
         del saved
         self._set_learning_rates(idx, it)
         graph = torch.cuda.CUDAGraph()

@@ -31,8 +31,10 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, graphs
-from .gaussian_model import GaussianModel, OptimizationParams
+from .deferred import backward, deferred_grads, root_gradient
+from .gaussian_model import GaussianModel, OptimizationParams, green_mask
 from .losses import face_loss
+from .optim import StepOptimizers, lambda_lr, make_motion_optimizer
 
 
 @dataclass
@@ -229,6 +231,7 @@ class FacePhase:
 
 
 C3_PHASE = FacePhase()             # the phase config C3 / bench.py measures (warm_step < iteration <= warm_step + 2000)
+FACE_GREEN = (30, 225, 30)         # green_mask thresholds of the face branch (train_face.py:735, pretrain_face.py:183)
 
 
 def face_phase(iteration: int, opt=OptimizationParams, warm_step: int = 3000, hair_mask_interval: int = 7,
@@ -240,6 +243,74 @@ def face_phase(iteration: int, opt=OptimizationParams, warm_step: int = 3000, ha
     priors = (not mode_long) and iteration > warm_step + 2000
     return FacePhase(align=align, warm=iteration > warm_step, hair_mask_iter=hair, priors=priors,
                      prior_depth=priors and iteration % opt.opacity_reset_interval > 100)
+
+
+def motion_lr_factor(i: int, warm_step: int, iterations: int) -> float:
+    """The motion field's LambdaLR factor after ``i`` scheduler steps (train_face.py:60, train_mouth.py:64): x0.1 during
+    warm-up, then 0.5^(i / iterations)."""
+    return 0.1 if i < warm_step else 0.5 ** (i / iterations)
+
+
+@torch.no_grad()
+def update_densification_stats(g: GaussianModel, vs_grad, radii, grad_add=None):
+    """Densification statistics of one rendered frame (train_face.py:670-671; scene/gaussian_model.py:683-685): the
+    densify_stats kernel, torch operators where its layout does not hold.  With several ranks they stay LOCAL sums /
+    maxima and are exchanged once, when a densification reads them (FaceTrainer.sync_densification_stats): sum and max
+    commute with the per-step accumulation."""
+    if vs_grad.is_cuda and g.max_radii2D.dtype == torch.float32 and radii.dtype == torch.int32 \
+            and vs_grad.is_contiguous():
+        from .glue import densify_stats
+        densify_stats(vs_grad, radii, g.max_radii2D, g.xyz_gradient_accum, g.denom, grad_add)
+        return
+    if grad_add is not None:
+        vs_grad.add_(grad_add)
+    vis = radii > 0
+    rmax = torch.where(vis, radii.to(g.max_radii2D.dtype), torch.zeros_like(g.max_radii2D))
+    g.max_radii2D.copy_(torch.max(g.max_radii2D, rmax))
+    g.add_densification_stats(vs_grad, vis)
+
+
+@torch.no_grad()
+def densify_and_prune_at(g: GaussianModel, it: int, until: int, opt, extent: float, generator):
+    """The reference's densify_and_prune call at iteration ``it`` of a schedule that densifies until ``until``
+    (train_face.py:675-678, train_mouth.py:268-271, pretrain_face.py:176-179)."""
+    size_threshold = 20 if it > opt.opacity_reset_interval else None
+    g.densify_and_prune(opt.densify_grad_threshold, 0.05 + 0.25 * it / until, extent, size_threshold,
+                        generator=generator)
+
+
+_MOMENTS = ("exp_avg", "exp_avg_sq", "step")
+
+
+@torch.no_grad()
+def snapshot_state(tensors, optimizers: StepOptimizers, stats):
+    """Copies of a training state: ``tensors`` (parameters and whatever else a step writes), the optimizers' moments
+    and step counters, the densification statistics ``stats``."""
+    opt = [None if not st else {k: st[k].detach().clone() for k in _MOMENTS if torch.is_tensor(st.get(k))}
+           for st in optimizers.states()]
+    return dict(params=[t.detach().clone() for t in tensors], opt=opt, stats=[t.detach().clone() for t in stats])
+
+
+@torch.no_grad()
+def restore_state(snap, tensors, optimizers: StepOptimizers, stats):
+    """Copy a snapshot_state() back IN PLACE (same parameter set required), so captured graphs stay valid.  Optimizer
+    state that did not exist yet at the snapshot (no step had run) goes back to zero moments and a zero step count,
+    which is what a first step starts from."""
+    assert len(tensors) == len(snap["params"]), "the parameter set changed since the snapshot"
+    for t, src in zip(tensors, snap["params"]):
+        assert t.shape == src.shape, "the parameter set changed since the snapshot"
+        t.copy_(src)
+    for st, saved in zip(optimizers.states(), snap["opt"]):
+        if not st:
+            continue
+        for k in _MOMENTS:
+            if torch.is_tensor(st.get(k)):
+                if saved and k in saved:
+                    st[k].copy_(saved[k])
+                else:
+                    st[k].zero_()
+    for dst, src in zip(stats, snap["stats"]):
+        dst.copy_(src)
 
 
 _DENSITY_WARM = set()
@@ -256,7 +327,6 @@ def warm_density_control(device, sh_degree: int = 1, opt=OptimizationParams):
     if key in _DENSITY_WARM or device.type != "cuda":
         return
     _DENSITY_WARM.add(key)
-    from .gaussian_model import sh_to_rgb
     g = GaussianModel(sh_degree).create_random(256, device, seed=0)
     g.training_setup(opt, fused=True)
     gen = torch.Generator(device=device).manual_seed(0)
@@ -268,8 +338,7 @@ def warm_density_control(device, sh_degree: int = 1, opt=OptimizationParams):
         g._p["scaling"].data[: n // 2] -= 3.0                        # both the clone and the split selection non-empty
         g.densify_and_prune(0.5, 0.005, 0.2, 20, generator=gen)
         g.reset_opacity()
-        rgb = sh_to_rgb(g.active_sh_degree, g.get_features, g.get_xyz, torch.zeros(3, device=device))
-        g.prune_points((rgb[:, 0] < 30 / 255) & (rgb[:, 1] > 225 / 255) & (rgb[:, 2] < 30 / 255))
+        g.prune_points(green_mask(g, torch.zeros(3, device=device), FACE_GREEN))
         g.prune_points(g.get_xyz[:, -1] < -0.07)
     torch.cuda.synchronize(device)
 
@@ -280,9 +349,11 @@ class FaceTrainer:
     iteration-dependent phases (face_phase) and its densification order."""
 
     def __init__(self, gaussians: GaussianModel, motion_net, background, opt=OptimizationParams,
-                 cameras_extent: float = 0.2, densify: bool = True, seed: int = 0, schedule: Optional[str] = None):
+                 cameras_extent: float = 0.2, densify: bool = True, seed: int = 0, schedule: Optional[str] = None,
+                 warm_step: int = 3000):
         assert schedule in (None, "reference")
         self.schedule = schedule
+        self.warm_step = warm_step
         self.g = gaussians
         self.motion_net = motion_net
         self.bg = background
@@ -294,8 +365,16 @@ class FaceTrainer:
         self.device = dev
         self.gen = torch.Generator(device=dev).manual_seed(seed)     # identical on every rank
         self.on_gpu = dev.type == "cuda"
-        # train_face.py:59-60: AdamW(betas .9/.99, eps 1e-8, wd .01), lr x0.1 during warm-up then 0.5^(it/iters)
-        self._setup_optimizers()
+        # learning rates are device scalars on the GPU, so that a captured step can be replayed
+        self.motion_optimizer = make_motion_optimizer(motion_net, self.on_gpu)
+        self._motion_base_lr = [float(g["lr"]) for g in self.motion_optimizer.param_groups]
+        self.g.training_setup(self.opt, fused=self.on_gpu)
+        # on the GPU one launch steps both (train_face.py:781-788 steps them back to back); step("early") / step("late")
+        # = the same step as two launches (GraphedStep's single-graph form): the per-Gaussian parameters whose gradients
+        # are final when the backward pass reaches the motion fields (_forward_backward_cut) are stepped beside the rest
+        # of the pass, positions and networks behind it
+        early = lambda q: any(q is v for k, v in self.g._p.items() if k != "xyz")
+        self.optimizers = StepOptimizers(self.motion_optimizer, self.g.optimizer, partition=early)
         self.last = {}
         self._graph = None            # the captured step replayed last
         self._graph_cache = {}        # phase -> captured step
@@ -305,48 +384,12 @@ class FaceTrainer:
         self.recapture_seconds = 0.0  # host time of the re-captures
         self.density_seconds = 0.0    # host time of the density-control events (they synchronise)
 
-    # ---- optimizers: learning rates are device scalars on the GPU so a captured step can be replayed -------
-    def _setup_optimizers(self):
-        groups = self.motion_net.get_params(5e-3, 5e-4)
-        self._motion_base_lr = [float(g["lr"]) for g in groups]
-        if self.on_gpu:
-            from .optim import MultiTensorAdam
-            self.motion_optimizer = MultiTensorAdam(groups, lr=5e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01,
-                                                    decoupled=True)
-        else:
-            self.motion_optimizer = torch.optim.AdamW(groups, lr=5e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01)
-        self.g.training_setup(self.opt, fused=self.on_gpu)
-        self._combined = None
-        if self.on_gpu:
-            from .optim import CombinedAdam, MultiTensorAdam
-            if isinstance(self.g.optimizer, MultiTensorAdam):
-                # one launch steps both optimizers (train_face.py:781-788 steps them back to back)
-                # step("early") / step("late") = the same step as two launches (GraphedStep's single-graph form): the
-                # per-Gaussian parameters whose gradients are final when the backward pass reaches the motion fields
-                # (_forward_backward_cut) are stepped beside the rest of the pass, positions and networks behind it
-                early = lambda q: any(q is v for k, v in self.g._p.items() if k != "xyz")
-                self._combined = CombinedAdam([self.motion_optimizer, self.g.optimizer], partition=early)
-
-    def _step_optimizers(self, part=None):
-        if self._combined is not None:
-            self._combined.step(part)
-        else:
-            self.motion_optimizer.step()
-            self.g.optimizer.step()
-
-    def _motion_lr_factor(self, it):
-        warm_step, iters = 3000, self.opt.iterations
-        return 0.1 if it < warm_step else 0.5 ** (it / iters)
-
     def _set_learning_rates(self, it):
         """Per-step schedules (train_face.py:60, scene/gaussian_model.py:421-427) written into the lr slots."""
-        f = self._motion_lr_factor(it - 1)      # LambdaLR: step `it` runs with lambda(it - 1)
-        for grp, base in zip(self.motion_optimizer.param_groups, self._motion_base_lr):
-            grp["lr"] = base * f
+        f = motion_lr_factor(it - 1, self.warm_step, self.opt.iterations)      # LambdaLR: step `it` runs with lambda(it - 1)
+        lambda_lr(self.motion_optimizer, self._motion_base_lr, f)
         self.g.update_learning_rate(it)
-        for opt_ in ((self._combined,) if self._combined is not None else (self.motion_optimizer, self.g.optimizer)):
-            if hasattr(opt_, "set_lrs"):
-                opt_.set_lrs()          # one small copy into the device-side learning-rate table
+        self.optimizers.push_lrs()          # one small copy into the device-side learning-rate table
 
     def _all_params(self):
         ps = self.g.per_gaussian_parameters()
@@ -357,7 +400,7 @@ class FaceTrainer:
 
     # ---- loss block (train_face.py:450-456, 508-540) --------------------------------------------------------
     def phase_of(self, it: int) -> FacePhase:
-        return face_phase(it, self.opt) if self.schedule == "reference" else C3_PHASE
+        return face_phase(it, self.opt, self.warm_step) if self.schedule == "reference" else C3_PHASE
 
     def loss_fn(self, frame: Frame, pkg, warm: bool, hair_mask_iter: bool = False, priors: bool = False,
                 prior_depth: bool = False):
@@ -400,22 +443,13 @@ class FaceTrainer:
         with (nullcontext() if phase.priors else defer_finalize()):
             loss, Ll1 = self.loss_fn(frame, pkg, warm=phase.warm, hair_mask_iter=phase.hair_mask_iter,
                                      priors=phase.priors, prior_depth=phase.prior_depth)
-        from .deferred import deferred_grads
         from . import diff_gauss
         # fold_aux (only callers that run _stats_and_optimizers(pkg) next): the auxiliary image's share of the screen-space
         # gradient is added by the statistics kernel instead of by a launch of its own at the end of backward
         fold = bool(fold_aux and self.on_gpu)
         diff_gauss.FOLD_AUX_M2D = fold
         try:
-            with deferred_grads(self.device if self.on_gpu else None):
-                # the MLPs' weight gradients are batched into one launch at the end (deferred.py); the root gradient is
-                # a cached constant (no fill launch per step)
-                if self.on_gpu:
-                    if getattr(self, "_one", None) is None:
-                        self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
-                    loss.backward(gradient=self._one)
-                else:
-                    loss.backward()
+            backward(loss, self.device)
         except BaseException:
             diff_gauss.reset_aux_state()       # a failed backward must not withhold the NEXT step's aux share
             raise
@@ -435,7 +469,6 @@ class FaceTrainer:
         -> (pkg, loss, Ll1, early_params, finish)"""
         from . import renderer
         from .renderer import render_motion
-        from .deferred import deferred_grads
         from . import diff_gauss
         assert self.on_gpu
         renderer.MARK_BACKWARD_CUT = True
@@ -457,12 +490,10 @@ class FaceTrainer:
         cut = [c for c in cut if c is not None and c.requires_grad]
         vs = pkg["viewspace_points"]
         early = [q for k, q in self.g._p.items() if k != "xyz" and q.requires_grad]
-        if getattr(self, "_one", None) is None:
-            self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
         diff_gauss.FOLD_AUX_M2D = "always" if fold_aux else False    # (see _forward_backward)
         try:
             with deferred_grads(self.device):
-                got = torch.autograd.grad(loss, cut + early + [vs], grad_outputs=self._one, allow_unused=True,
+                got = torch.autograd.grad(loss, cut + early + [vs], grad_outputs=root_gradient(loss), allow_unused=True,
                                           retain_graph=False)
         except BaseException:
             diff_gauss.reset_aux_state()
@@ -489,24 +520,6 @@ class FaceTrainer:
         return pkg, loss, Ll1, have, finish
 
     @torch.no_grad()
-    def _update_stats(self, vs_grad, radii, grad_add=None):
-        """Densification statistics of this rank's frame (train_face.py:670-671; scene/gaussian_model.py:683-685).
-        With several ranks they stay LOCAL sums / maxima and are exchanged once, when a densification reads them
-        (sync_densification_stats): sum and max commute with the per-step accumulation."""
-        g = self.g
-        if vs_grad.is_cuda and g.max_radii2D.dtype == torch.float32 and radii.dtype == torch.int32 \
-                and vs_grad.is_contiguous():
-            from .glue import densify_stats
-            densify_stats(vs_grad, radii, g.max_radii2D, g.xyz_gradient_accum, g.denom, grad_add)
-            return
-        if grad_add is not None:
-            vs_grad.add_(grad_add)
-        vis = radii > 0
-        rmax = torch.where(vis, radii.to(g.max_radii2D.dtype), torch.zeros_like(g.max_radii2D))
-        g.max_radii2D.copy_(torch.max(g.max_radii2D, rmax))
-        g.add_densification_stats(vs_grad, vis)
-
-    @torch.no_grad()
     def sync_densification_stats(self):
         """Several ranks: every replica gets the statistics of all ranks' frames (sum of the gradient norms and
         visibility counts, maximum of the screen radii) before a densification decides on them."""
@@ -524,16 +537,15 @@ class FaceTrainer:
     def _stats_and_optimizers(self, pkg, distributed: bool, it: Optional[int] = None, frame: Optional[Frame] = None):
         """Everything of an iteration behind loss.backward(), in the reference's order (train_face.py:667-788):
         statistics -> [gradient exchange] -> [densify / prune / opacity reset] -> optimizers."""
-        self._update_stats(pkg["viewspace_points"].grad, pkg["radii"], dict.get(pkg, "_m2d_aux"))
+        update_densification_stats(self.g, pkg["viewspace_points"].grad, pkg["radii"], dict.get(pkg, "_m2d_aux"))
         if distributed:
             allreduce_gradients(self._all_params())
         if it is not None:
             self._maybe_densify(it, frame)
-        self._step_optimizers()
+        self.optimizers.step()
 
     def _zero_grad(self):
-        self.motion_optimizer.zero_grad(set_to_none=True)
-        self.g.optimizer.zero_grad(set_to_none=True)
+        self.optimizers.zero_grad()
 
     def _densify_due(self, it):
         o = self.opt
@@ -558,17 +570,12 @@ class FaceTrainer:
         if it < o.densify_until_iter:
             if interval_hit:
                 self.sync_densification_stats()
-                size_threshold = 20 if it > o.opacity_reset_interval else None
-                self.g.densify_and_prune(o.densify_grad_threshold, 0.05 + 0.25 * it / o.densify_until_iter,
-                                         self.extent, size_threshold, generator=self.gen)
+                densify_and_prune_at(self.g, it, o.densify_until_iter, o, self.extent, self.gen)
             if it % o.opacity_reset_interval == 0:
                 self.g.reset_opacity()
         if self.schedule == "reference" and interval_hit:
             # train_face.py:729-746: Gaussians that took the background's green, and the ones behind z = -0.07
-            from .gaussian_model import sh_to_rgb
-            center = frame.camera_center.to(self.device)
-            rgb = sh_to_rgb(self.g.active_sh_degree, self.g.get_features, self.g.get_xyz, center)
-            green = (rgb[:, 0] < 30 / 255) & (rgb[:, 1] > 225 / 255) & (rgb[:, 2] < 30 / 255)
+            green = green_mask(self.g, frame.camera_center.to(self.device), FACE_GREEN)
             # (two prunes in the reference; both tests are per Gaussian, so one rebuild with the union removes the same rows)
             self.g.prune_points(green | (self.g.get_xyz[:, -1] < -0.07))
         self._drop_graph(keep_mode=True)          # (graph mode stays on: the next iteration captures its step again)
@@ -583,12 +590,6 @@ class FaceTrainer:
         self._graph_cache = {}
         if not keep_mode:
             self._graph_mode = None
-
-    def _prepare_optimizers(self):
-        """Device-side tables of the fused optimizers brought up to date with the parameter set (no step)."""
-        for o in ((self._combined,) if self._combined is not None else (self.motion_optimizer, self.g.optimizer)):
-            if hasattr(o, "prepare"):
-                o.prepare()
 
     def _recapture(self, frame: Frame, phase: FacePhase, min_capacity: int = 0):
         """Capture the step of ``phase`` again WITHOUT running a single train step: graph mode is on (enable_graph was
@@ -663,51 +664,16 @@ class FaceTrainer:
         return self.last
 
     # ---- state snapshot (benchmark windows start from the same state; in place, so captured graphs stay valid) ----
-    def _optimizer_states(self):
-        """[(optimizer state dict of one parameter)] in a fixed order (motion optimizer first, groups, parameters)."""
-        out = []
-        for opt_ in (self.motion_optimizer, self.g.optimizer):
-            for grp in opt_.param_groups:
-                for p in grp["params"]:
-                    out.append(opt_.state.get(p) if hasattr(opt_.state, "get") else None)
-        return out
+    def _stats(self):
+        return self.g.xyz_gradient_accum, self.g.denom, self.g.max_radii2D
 
-    def _state_tensors(self):
-        ts = [p.data for p in self._all_params()]
-        for st in self._optimizer_states():
-            if st:
-                ts += [st[k] for k in ("exp_avg", "exp_avg_sq", "step") if torch.is_tensor(st.get(k))]
-        ts += [self.g.xyz_gradient_accum, self.g.denom, self.g.max_radii2D]
-        return ts
-
-    @torch.no_grad()
     def snapshot(self):
-        opt = [None if not st else {k: st[k].detach().clone() for k in ("exp_avg", "exp_avg_sq", "step")
-                                     if torch.is_tensor(st.get(k))} for st in self._optimizer_states()]
-        return dict(iteration=self.iteration, params=[p.data.detach().clone() for p in self._all_params()], opt=opt,
-                    stats=[t.detach().clone() for t in (self.g.xyz_gradient_accum, self.g.denom, self.g.max_radii2D)])
+        return dict(iteration=self.iteration,
+                    **snapshot_state([p.data for p in self._all_params()], self.optimizers, self._stats()))
 
-    @torch.no_grad()
     def restore(self, snap):
-        """Copy a snapshot() back IN PLACE (same parameter set required: no densification in between), so captured
-        graphs stay valid.  Optimizer state that did not exist yet at the snapshot (no step had run) goes back to
-        zero moments and a zero step count, which is what a first step starts from."""
-        params = self._all_params()
-        assert len(params) == len(snap["params"]), "the parameter set changed since the snapshot"
-        for p, src in zip(params, snap["params"]):
-            assert p.shape == src.shape, "the parameter set changed since the snapshot"
-            p.data.copy_(src)
-        for st, saved in zip(self._optimizer_states(), snap["opt"]):
-            if not st:
-                continue
-            for k in ("exp_avg", "exp_avg_sq", "step"):
-                if torch.is_tensor(st.get(k)):
-                    if saved and k in saved:
-                        st[k].copy_(saved[k])
-                    else:
-                        st[k].zero_()
-        for dst, src in zip((self.g.xyz_gradient_accum, self.g.denom, self.g.max_radii2D), snap["stats"]):
-            dst.copy_(src)
+        """Copy a snapshot() back IN PLACE (restore_state); no densification in between."""
+        restore_state(snap, [p.data for p in self._all_params()], self.optimizers, self._stats())
         self.iteration = snap["iteration"]
 
     # ---- graph mode --------------------------------------------------------------------------------------------
@@ -763,7 +729,7 @@ class GraphedStep(graphs.CapturedStep):
         # on every rank -- takes the two-graph form)
         self.early = split_for_allreduce == "early" and bool(phase.align)
         self.split = bool(split_for_allreduce)
-        self.early_optimizer = (not self.split and bool(phase.align) and t._combined is not None
+        self.early_optimizer = (not self.split and bool(phase.align) and t.optimizers.combined is not None
                                 and os.environ.get("INSTAG_EARLY_OPTIMIZER", "0") == "1")
         self.static = example.clone_static()
         cold = warmup_steps > 0
@@ -782,7 +748,7 @@ class GraphedStep(graphs.CapturedStep):
         else:
             assert min_capacity > 0, "a warm capture needs the capacity of an earlier one"
             cap = int(min_capacity)
-            t._prepare_optimizers()          # tables of the new parameter set: allocations / uploads outside the capture
+            t.optimizers.prepare()           # tables of the new parameter set: allocations / uploads outside the capture
             from . import renderer
             renderer.prepare_screenspace(t.g)      # (likewise the zeros behind the screen-space gradient carrier)
         self.plan = graphs.install([cap, cap], dev)
@@ -819,8 +785,9 @@ class GraphedStep(graphs.CapturedStep):
                 def early_launches():
                     side.wait_stream(torch.cuda.current_stream(dev))
                     with torch.cuda.stream(side), torch.no_grad():
-                        t._update_stats(pkg["viewspace_points"].grad, pkg["radii"], dict.get(pkg, "_m2d_aux"))
-                        t._step_optimizers("early")
+                        update_densification_stats(t.g, pkg["viewspace_points"].grad, pkg["radii"],
+                                                   dict.get(pkg, "_m2d_aux"))
+                        t.optimizers.step("early")
 
                 # where the side launches start: beside the largest MLP's backward they cost it 9 us and take 65 us
                 # themselves (24 alone); behind it they run beside the heads' and the encoder's backward
@@ -837,7 +804,7 @@ class GraphedStep(graphs.CapturedStep):
                     deferred.clear_milestones()
                 main.wait_stream(side)
                 with torch.no_grad():
-                    t._step_optimizers("late")
+                    t.optimizers.step("late")
                 t._zero_grad()
             del pkg, finish
         elif not self.split:
@@ -867,8 +834,8 @@ class GraphedStep(graphs.CapturedStep):
                         self._bucket.mul_(1.0 / dist.get_world_size())
                     scatter_grad_bucket(self._params_early, self._bucket_early)
                     scatter_grad_bucket(self._params, self._bucket)
-                    t._update_stats(self._vs_grad, self._radii)
-                    t._step_optimizers()
+                    update_densification_stats(t.g, self._vs_grad, self._radii)
+                    t.optimizers.step()
                     t._zero_grad()
         else:
             with graphs.capture(self.graph_a, self.plan, cold, **options):
@@ -884,8 +851,8 @@ class GraphedStep(graphs.CapturedStep):
                         # mean over ranks of the summed gradients
                         self._bucket.mul_(1.0 / dist.get_world_size())
                     scatter_grad_bucket(self._params, self._bucket)
-                    t._update_stats(self._vs_grad, self._radii)        # local; exchanged when a densification reads them
-                    t._step_optimizers()
+                    update_densification_stats(t.g, self._vs_grad, self._radii)    # local until a densification
+                    t.optimizers.step()
                     t._zero_grad()
         if dot:
             self.graph_a.debug_dump(dot)

@@ -437,6 +437,100 @@ def test_dp_densification_stats_are_exchanged_when_read_gloo_world2():
     assert torch.equal(r0["rad"], want)
 
 
+def _cpu_face_trainer():
+    from oracle.grid_torch import GridEncoder as CpuGrid
+    from instag_amd.train import build_trainer
+    return build_trainer(64, torch.device("cpu"), seed=0, encoder_cls=CpuGrid)
+
+
+def test_step_optimizers_order_and_lambda_lr():
+    """The optimizer bundle of a CPU FaceTrainer: torch.optim members (the motion field's AdamW first, then the
+    Gaussians' Adam), no combined launch; step() and zero_grad() go through the members in that order; the motion
+    field's LambdaLR writes base * lambda(it - 1) with the trainer's warm_step."""
+    from instag_amd.optim import lambda_lr
+    tr = _cpu_face_trainer()
+    bundle = tr.optimizers
+    motion, gauss = tr.motion_optimizer, tr.g.optimizer
+    assert bundle.combined is None and bundle.members == [motion, gauss]
+    assert type(motion) is torch.optim.AdamW
+    d = motion.defaults
+    assert (d["betas"], d["eps"], d["weight_decay"]) == ((0.9, 0.99), 1e-8, 0.01)
+    base = [grp["lr"] for grp in motion.param_groups]
+    assert base == tr._motion_base_lr and max(base) == 5e-3
+
+    calls = []
+    for name, o in (("motion", motion), ("gauss", gauss)):
+        def wrap(fn, what, name=name):
+            return lambda *a, **k: (calls.append((what, name)), fn(*a, **k))[1]
+        o.step, o.zero_grad = wrap(o.step, "step"), wrap(o.zero_grad, "zero")
+    params = tr._all_params()
+    for p in params:
+        p.grad = torch.ones_like(p)
+    before = [p.detach().clone() for p in params]
+    bundle.push_lrs()
+    bundle.prepare()
+    assert calls == []
+    bundle.step()
+    assert calls == [("step", "motion"), ("step", "gauss")]
+    assert all(not torch.equal(p, b) for p, b in zip(params, before))
+    bundle.zero_grad()
+    assert calls[2:] == [("zero", "motion"), ("zero", "gauss")] and all(p.grad is None for p in params)
+    states = bundle.states()
+    assert len(states) == sum(len(grp["params"]) for o in (motion, gauss) for grp in o.param_groups)
+    assert states[0] is motion.state[motion.param_groups[0]["params"][0]]
+    assert states[-1] is gauss.state[gauss.param_groups[-1]["params"][-1]]
+
+    lambda_lr(motion, base, 0.25)
+    assert [grp["lr"] for grp in motion.param_groups] == [b * 0.25 for b in base]
+    tr.warm_step = 10
+    tr._set_learning_rates(10)                       # step 10 runs with lambda(9): still warming up
+    assert [grp["lr"] for grp in motion.param_groups] == [b * 0.1 for b in base]
+    tr._set_learning_rates(11)
+    f = 0.5 ** (10 / tr.opt.iterations)
+    assert [grp["lr"] for grp in motion.param_groups] == [b * f for b in base]
+
+
+def test_face_trainer_snapshot_restore_roundtrip():
+    """FaceTrainer.snapshot() / restore(): parameters, Adam moments and step counters and the densification
+    statistics come back bit for bit and in place; optimizer state that did not exist at the snapshot goes back to
+    zero moments and step 0."""
+    tr = _cpu_face_trainer()
+    params = tr._all_params()
+    ptrs = [p.data_ptr() for p in params]
+
+    def train(seed):
+        gen = torch.Generator().manual_seed(seed)
+        for p in params:
+            p.grad = torch.randn(p.shape, generator=gen)
+        tr.optimizers.step()
+        tr._zero_grad()
+        with torch.no_grad():
+            for t in (tr.g.xyz_gradient_accum, tr.g.denom, tr.g.max_radii2D):
+                t.add_(torch.rand(t.shape, generator=gen))
+        tr.iteration += 1
+
+    fresh = tr.snapshot()
+    assert all(st is None for st in fresh["opt"])
+    train(1)
+    snap = tr.snapshot()
+    assert snap["iteration"] == 1 and sum(st is not None for st in snap["opt"]) >= len(params)
+    train(2)
+    assert not torch.equal(params[0], snap["params"][0])
+    tr.restore(snap)
+    assert tr.iteration == 1 and [p.data_ptr() for p in params] == ptrs
+    assert all(torch.equal(p, s) for p, s in zip(params, snap["params"]))
+    for st, saved in zip(tr.optimizers.states(), snap["opt"]):
+        assert (st is None) == (saved is None) and all(torch.equal(st[k], saved[k]) for k in (saved or ()))
+    assert all(torch.equal(t, s) for t, s in zip((tr.g.xyz_gradient_accum, tr.g.denom, tr.g.max_radii2D),
+                                                    snap["stats"]))
+    tr.restore(fresh)
+    assert tr.iteration == 0 and all(torch.equal(p, s) for p, s in zip(params, fresh["params"]))
+    for st in tr.optimizers.states():
+        assert st is None or all(float(st[k].abs().max()) == 0.0 for k in ("exp_avg", "exp_avg_sq", "step"))
+    assert all(torch.equal(t, s) for t, s in zip((tr.g.xyz_gradient_accum, tr.g.denom, tr.g.max_radii2D),
+                                                    fresh["stats"]))
+
+
 def test_gaussian_model_small_api_surface():
     """get_identity / get_covariance / oneupSHdegree (scene/gaussian_model.py:189-203): the covariance is
     R S S^T R^T (fp64 check), the SH degree saturates at max_sh_degree."""
