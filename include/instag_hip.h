@@ -162,6 +162,14 @@ int instag_raster_forward_stage1(const instag_raster_args* a, void* geom, size_t
                                  int32_t* radii, int64_t* num_rendered /* (host) */,
                                  instag_stream_t stream);
 /* stage 2: outputs color [3,H,W], depth [1,H,W], normal [3,H,W], alpha [1,H,W], extra [E,H,W] (NULL if E==0).
+ * COLOUR-ONLY forward: out_depth == NULL && out_normal == NULL && out_extra == NULL (here and in
+ * instag_raster_forward_capacity).  The forward blend then neither blends, checkpoints nor stores depth, normal and
+ * extra -- one 16-byte and one 8-byte LDS read and three packed FMAs per (Gaussian, wave) instead of three 16-byte
+ * reads and six -- while out_color, out_alpha, out_aux, radii and all the state the rgb / aux backward reads are
+ * bit-identical to the full call's.  out_depth and out_normal go together (one NULL, the other not: INSTAG_E_ARG), and
+ * a colour-only call takes no out_extra.  The state remembers the variant: instag_raster_backward over a colour-only
+ * state with a depth / normal / extra gradient returns INSTAG_E_ARG (inside a stream capture, where the host cannot
+ * look at the state, such a call writes no gradient rows instead: every gradient comes back zero).
  * aux_colors [N,3] / out_aux [3,H,W] (both NULL or both set): a second colour set blended over the SAME instances
  * with the same alpha and transmittance, out_aux = sum c_aux alpha T + T_final bg.  It equals the colour image
  * of a second rasterizer call with colors_precomp = aux_colors on the same (detached) geometry, which is how the
@@ -236,6 +244,15 @@ int instag_raster_debug_export(const void* geom, size_t geom_bytes, const void* 
                                int32_t* ranges /*[tiles,2]*/, uint32_t* n_contrib /*[H*W]*/,
                                float* final_T /*[H*W]*/, float* rec2d /*[N,16]*/,
                                instag_stream_t stream);
+
+/* The backward blend's work list as the forward blend left it (device copies on `stream`, R > 0 only): count [1] =
+ * number of (tile, segment) pairs, pairs [2 * max_pairs] = the first min(max_pairs, R / 128 + tiles + 2) slots of the
+ * list (the order of the pairs is that of the tiles' atomic appends: compare it as a set).  blend_mode [1] (may be
+ * NULL): 0 = the forward blended every channel, 1 = it was colour-only. */
+int instag_raster_debug_export_work_list(const void* binning, size_t binning_bytes, const void* image,
+                                         size_t image_bytes, int64_t R, int32_t image_height, int32_t image_width,
+                                         uint32_t* count, uint32_t* pairs, int64_t max_pairs, uint32_t* blend_mode,
+                                         instag_stream_t stream);
 
 /* Per-Gaussian flag word of the forward state (device copy on `stream`): bits 0-2 SH clamp, 3-4 normal axis, 5 normal
  * sign, 6-7 cov2D clamp, bits 16-31 = HEIGHT of the Gaussian's tile rectangle.  Together with rec2d[15] (min x |

@@ -228,6 +228,7 @@ _PROTOS = {
     "instag_raster_debug_export": (C.c_int, [vp, sz, vp, sz, vp, sz, i32, i64, i32, i32,
                                              vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "instag_raster_debug_export_flags": (C.c_int, [vp, sz, i32, vp, vp]),
+    "instag_raster_debug_export_work_list": (C.c_int, [vp, sz, vp, sz, i64, i32, i32, vp, vp, i64, vp, vp]),
     "instag_debug_depth_sort": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, vp, vp]),
     "instag_debug_depth_sort_blocks": (C.c_uint32, [i32]),
     "instag_raster_sort_stalls": (C.c_int, [vp, i32, vp]),

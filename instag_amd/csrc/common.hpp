@@ -101,6 +101,8 @@ GeomLayout geom_layout(int32_t N);
 struct ImageLayout {
   size_t ranges, n_contrib, final_T;
   size_t tile_rounds;                        // u32 per tile: segments of its list the forward blend walked
+  size_t blend_mode;                         // u32: 0 = the forward blended every channel, 1 = colour-only (no depth /
+                                             // normal / extra image, planes 4-8 of the segment slots not written)
   size_t total;
 };
 ImageLayout image_layout(int32_t H, int32_t W);

@@ -200,6 +200,7 @@ ImageLayout image_layout(int32_t H, int32_t W) {
   L.n_contrib = o; o = align_up(o + P * sizeof(uint32_t), 256);
   L.final_T = o; o = align_up(o + P * sizeof(float), 256);
   L.tile_rounds = o; o = align_up(o + tiles * sizeof(uint32_t), 256);
+  L.blend_mode = o; o = align_up(o + sizeof(uint32_t), 256);
   L.total = o;
   return L;
 }
@@ -364,7 +365,12 @@ static int forward_tail(const instag_raster_args* a, void* geom, size_t geom_byt
                         size_t binning_bytes, void* image, size_t image_bytes, int64_t R,
                         float* out_color, float* out_depth, float* out_normal, float* out_alpha, float* out_extra,
                         const float* aux_colors, float* out_aux, int32_t* status, hipStream_t s) {
-  INSTAG_REQUIRE(out_color && out_depth && out_normal && out_alpha, "output images must not be NULL");
+  INSTAG_REQUIRE(out_color && out_alpha, "output images must not be NULL");
+  INSTAG_REQUIRE((out_depth == nullptr) == (out_normal == nullptr),
+                 "out_depth and out_normal go together: both set, or both NULL (with out_extra NULL) for a colour-only forward");
+  INSTAG_REQUIRE(out_depth != nullptr || out_extra == nullptr, "a colour-only forward (out_depth / out_normal NULL) takes no out_extra");
+  // (E > 0 and no out_extra beside depth / normal: as before, the extra channel is blended and not stored)
+  const bool colour_only = out_depth == nullptr;
   INSTAG_REQUIRE((aux_colors == nullptr) == (out_aux == nullptr), "aux_colors and out_aux go together");
   INSTAG_REQUIRE(R >= 0 && R < (int64_t)1 << 30, "instance count out of range (2^30 - 1 at most)");
   const GeomLayout GL = geom_layout(a->N);
@@ -440,7 +446,8 @@ static int forward_tail(const instag_raster_args* a, void* geom, size_t geom_byt
                               a->E > 0 ? out_extra : nullptr, aux_colors, out_aux, (uint32_t*)(bb + BL.seg_queue),
                               (uint32_t*)(bb + BL.seg_count), (float*)(bb + BL.seg_state),
                               (uint32_t*)(ib + IL.tile_rounds), R > 0 ? (uint32_t*)(bb + BL.fwd_sync) : nullptr,
-                              (uint32_t*)(bb + BL.seg_flag), a->walk_hints, R, s);
+                              (uint32_t*)(bb + BL.seg_flag), a->walk_hints, R, colour_only,
+                              (uint32_t*)(ib + IL.blend_mode), s);
 }
 
 int instag_raster_forward_stage2(const instag_raster_args* a, void* geom, size_t geom_bytes, void* binning,
@@ -507,6 +514,23 @@ int instag_raster_backward(const instag_raster_args* a, const void* geom, size_t
   // the auxiliary image rides along the main pass when that is an rgb-only pass (its gradients use the row slots of
   // the depth / normal / extra channels); otherwise it gets its own blend launch over the same state, below
   const bool fused_aux = aux_colors != nullptr && !full;
+  if (full) {
+    // the forward says in its state which channels it blended; a colour-only one left nothing to differentiate depth /
+    // normal / extra against.  (Not while the stream is being captured -- no copy to the host may be waited for there;
+    // the all-channel blend kernel looks at the word itself and writes no gradient row.)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    INSTAG_CHECK_HIP(hipStreamIsCapturing(s, &cs));
+    if (cs == hipStreamCaptureStatusNone) {
+      uint32_t mode = 0;
+      INSTAG_CHECK_HIP(hipMemcpyAsync(&mode, ib + IL.blend_mode, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      INSTAG_CHECK_HIP(hipStreamSynchronize(s));
+      if (mode != 0) {
+        set_error("rasterizer backward: a depth / normal / extra gradient was passed, but the forward call of this state "
+                  "was colour-only (out_depth / out_normal / out_extra NULL) and kept no such channels");
+        return INSTAG_E_ARG;
+      }
+    }
+  }
   INSTAG_REQUIRE(!aux_colors_only || fused_aux, "aux_colors_only needs aux_colors and an rgb-only main pass");
   if (R > 0) {
     if (int e = launch_blend_backward(c, (const int32_t*)(ib + IL.ranges), (const uint32_t*)(bb + BL.point_list),
@@ -517,7 +541,8 @@ int instag_raster_backward(const instag_raster_args* a, const void* geom, size_t
                                       fused_aux ? (aux_colors_only ? 2 : 1) : 0,
                                       (const uint32_t*)(bb + BL.seg_queue), (const uint32_t*)(bb + BL.seg_count),
                                       (const float*)(bb + BL.seg_state), (const uint32_t*)(ib + IL.tile_rounds),
-                                      (uint32_t)BL.seg_slots, (uint8_t*)const_cast<char*>(bb + BL.row_flag) + 0 * BL.row_flag_stride, s)) return e;
+                                      (uint32_t)BL.seg_slots, (uint8_t*)const_cast<char*>(bb + BL.row_flag) + 0 * BL.row_flag_stride,
+                                      (const uint32_t*)(ib + IL.blend_mode), s)) return e;
   }
   if (int e = launch_preprocess_backward(c, a, (const float*)(gb + GL.rec2d), (const float*)(gb + GL.cov3d),
                                          (const uint32_t*)(gb + GL.tiles_touched), (const uint32_t*)(gb + GL.flags),
@@ -535,7 +560,8 @@ int instag_raster_backward(const instag_raster_args* a, const void* geom, size_t
                                         nullptr, nullptr, nullptr, nullptr, inst_grad, aux_colors, nullptr, nullptr, 0,
                                         (const uint32_t*)(bb + BL.seg_queue), (const uint32_t*)(bb + BL.seg_count),
                                       (const float*)(bb + BL.seg_state), (const uint32_t*)(ib + IL.tile_rounds),
-                                      (uint32_t)BL.seg_slots, (uint8_t*)const_cast<char*>(bb + BL.row_flag) + 0 * BL.row_flag_stride, s))
+                                      (uint32_t)BL.seg_slots, (uint8_t*)const_cast<char*>(bb + BL.row_flag) + 0 * BL.row_flag_stride,
+                                      (const uint32_t*)(ib + IL.blend_mode), s))
         return e;
     }
     return launch_aux_backward_reduce(c, (const float*)(gb + GL.rec2d), (const uint32_t*)(gb + GL.tiles_touched), radii,
@@ -574,7 +600,8 @@ int instag_raster_aux_backward(const instag_raster_args* a, const void* geom, si
                                       dL_daux_colors == nullptr ? 3 : 0,          // no colour gradient wanted: mean-only pass
                                       (const uint32_t*)(bb + BL.seg_queue), (const uint32_t*)(bb + BL.seg_count),
                                       (const float*)(bb + BL.seg_state), (const uint32_t*)(ib + IL.tile_rounds),
-                                      (uint32_t)BL.seg_slots, (uint8_t*)const_cast<char*>(bb + BL.row_flag) + 1 * BL.row_flag_stride, s))
+                                      (uint32_t)BL.seg_slots, (uint8_t*)const_cast<char*>(bb + BL.row_flag) + 1 * BL.row_flag_stride,
+                                      (const uint32_t*)(ib + IL.blend_mode), s))
       return e;
   }
   return launch_aux_backward_reduce(c, (const float*)(gb + GL.rec2d), (const uint32_t*)(gb + GL.tiles_touched), radii,
@@ -618,6 +645,25 @@ int instag_raster_debug_export(const void* geom, size_t geom_bytes, const void* 
     INSTAG_CHECK_HIP(cp(n_contrib, ib + IL.n_contrib, P * 4));
     INSTAG_CHECK_HIP(cp(final_T, ib + IL.final_T, P * 4));
   }
+  return INSTAG_OK;
+}
+
+int instag_raster_debug_export_work_list(const void* binning, size_t binning_bytes, const void* image, size_t image_bytes,
+                                         int64_t R, int32_t H, int32_t W, uint32_t* count, uint32_t* pairs,
+                                         int64_t max_pairs, uint32_t* blend_mode, instag_stream_t stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  const BinningLayout BL = binning_layout(R, H, W);
+  const ImageLayout IL = image_layout(H, W);
+  INSTAG_REQUIRE(binning != nullptr && image != nullptr && count != nullptr, "debug_export_work_list: NULL pointer");
+  INSTAG_REQUIRE(max_pairs >= 0 && (pairs != nullptr || max_pairs == 0), "debug_export_work_list: pairs / max_pairs");
+  if (binning_bytes < BL.total) { set_error("binning buffer too small"); return INSTAG_E_SPACE; }
+  if (image_bytes < IL.total) { set_error("image buffer too small"); return INSTAG_E_SPACE; }
+  const char *bb = (const char*)binning, *ib = (const char*)image;
+  INSTAG_CHECK_HIP(hipMemcpyAsync(count, bb + BL.seg_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  const size_t n = std::min<size_t>((size_t)max_pairs, BL.seg_slots);
+  if (n > 0) INSTAG_CHECK_HIP(hipMemcpyAsync(pairs, bb + BL.seg_queue, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  if (blend_mode)
+    INSTAG_CHECK_HIP(hipMemcpyAsync(blend_mode, ib + IL.blend_mode, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   return INSTAG_OK;
 }
 

@@ -56,7 +56,19 @@ __device__ uint32_t* g_stall_host;            // (pinned host memory: readable w
 __device__ uint32_t g_blend_dbg[4096 * 8];
 #endif
 
-template <bool AUX>
+//
+// GEO = false, the colour-only variant: depth, normal and extra are neither blended, checkpointed nor stored (a caller
+// that reads only the image, alpha and the attention map -- the training step outside its geometry-prior phase -- asks
+// for it by passing no depth / normal / extra image).  A record then is 6 floats (r g b + aux r g b): one ds_read_b128
+// and one ds_read_b64 per Gaussian instead of three ds_read_b128, three packed FMAs instead of six.  Every kept channel
+// sees the same fp32 operations in the same order as in the full variant (fma(c, w, acc) per Gaussian, fma(P, local, acc)
+// per segment), so the image, alpha, aux, T, n_contrib, the work list and the kept state planes (0, 1-3, 9-11, and
+// 12 / 13 of a shared tile) are bit-identical; planes 4-8 of a segment slot are NOT WRITTEN.  The launch says which
+// variant ran in `blend_mode` (a word of the image buffer): the backward pass refuses depth / normal / extra gradients
+// over a colour-only state.
+constexpr uint32_t MODE_FULL = 0u, MODE_COLOUR_ONLY = 1u;
+
+template <bool AUX, bool GEO>
 __global__ void __launch_bounds__(BLOCK)
 blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                      const float* __restrict__ rec2d, uint32_t* __restrict__ n_contrib,
@@ -65,15 +77,19 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
                      float* __restrict__ out_alpha, float* __restrict__ out_extra,
                      const float* __restrict__ aux_colors, float* __restrict__ out_aux,
                      uint32_t* __restrict__ seg_queue, uint32_t* __restrict__ seg_count,
-                     float* __restrict__ seg_state, uint32_t* __restrict__ tile_rounds) {
+                     float* __restrict__ seg_state, uint32_t* __restrict__ tile_rounds,
+                     uint32_t* __restrict__ blend_mode) {
   // One LDS array per read of the inner loop, each read a whole ds_read_b128 (4 LDS cycles per wave) or ds_read_b64
   // (2): the LDS array, shared by every wave of the CU, is the forward pass's scarcest resource -- a record read as
   // 64-bit halves of neighbouring float4 (what the compiler makes of an array of structs) costs twice as much.
   __shared__ float4 s_geo[BLOCK];                  // x y A' C'
   __shared__ float2 s_bo[BLOCK];                   // B' opacity
-  __shared__ float4 s_c0[BLOCK], s_c1[BLOCK];      // r g b depth | nx ny nz extra
-  __shared__ float4 s_c2[AUX ? BLOCK : 1];         // aux r g b -
+  __shared__ float4 s_c0[BLOCK];                   // r g b depth          (colour-only: r g b aux-r)
+  __shared__ float4 s_c1[GEO ? BLOCK : 1];         // nx ny nz extra
+  __shared__ float4 s_c2[AUX && GEO ? BLOCK : 1];  // aux r g b -
+  __shared__ float2 s_cx[AUX && !GEO ? BLOCK : 1]; // (colour-only) aux-g aux-b
   const int tile = blockIdx.x;
+  if (tile == 0 && threadIdx.x == 0) *blend_mode = GEO ? MODE_FULL : MODE_COLOUR_ONLY;
   const int tx = tile % c.grid_x, ty = tile / c.grid_x;
   const int tid = threadIdx.x;
   const int pxi = tx * TILE_X + (tid & 15), pyi = ty * TILE_Y + (tid >> 4);
@@ -127,9 +143,14 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
   for (int i = 0; i < rounds; ++i, toDo -= BLOCK) {
     if (__syncthreads_count(pix.x > 0.5f * FAR_PIXEL) == BLOCK) break;
     s_geo[tid] = nrec0; s_bo[tid] = make_float2(nrec1.x, nrec1.y);
-    s_c0[tid] = make_float4(nrec1.z, nrec1.w, nrec2.x, nrec2.y);
-    s_c1[tid] = make_float4(nrec2.z, nrec2.w, nrec3.x, nrec3.y);
-    if (AUX) s_c2[tid] = make_float4(nrec3.z, nrec3.w, nauxb, 0.f);
+    if constexpr (GEO) {
+      s_c0[tid] = make_float4(nrec1.z, nrec1.w, nrec2.x, nrec2.y);
+      s_c1[tid] = make_float4(nrec2.z, nrec2.w, nrec3.x, nrec3.y);
+      if (AUX) s_c2[tid] = make_float4(nrec3.z, nrec3.w, nauxb, 0.f);
+    } else {
+      s_c0[tid] = make_float4(nrec1.z, nrec1.w, nrec2.x, AUX ? nrec3.z : 0.f);
+      if (AUX) s_cx[tid] = make_float2(nrec3.w, nauxb);
+    }
     __syncthreads();
     fetch((i + 1) * BLOCK + tid);
     const int groups = (min(BLOCK, toDo) + 3) >> 2;
@@ -186,24 +207,31 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float4 c0 = s_c0[4 * g + k];
-          const float4 c1 = s_c1[4 * g + k];
           const f32x2 w2 = {w[k], w[k]};
           acc2[0] = __builtin_elementwise_fma(f32x2{c0.x, c0.y}, w2, acc2[0]);
-          acc2[1] = __builtin_elementwise_fma(f32x2{c0.z, c0.w}, w2, acc2[1]);
-          acc2[2] = __builtin_elementwise_fma(f32x2{c1.x, c1.y}, w2, acc2[2]);
-          acc2[3] = __builtin_elementwise_fma(f32x2{c1.z, c1.w}, w2, acc2[3]);
-          if (AUX) {
-            const float4 c2 = s_c2[4 * g + k];
-            xacc2 = __builtin_elementwise_fma(f32x2{c2.x, c2.y}, w2, xacc2);
-            xacc3 = __builtin_elementwise_fma(f32x2{c2.z, c2.w}, w2, xacc3);   // (.w: a 12-byte read costs two 16-byte ones)
+          acc2[1] = __builtin_elementwise_fma(f32x2{c0.z, c0.w}, w2, acc2[1]);   // (colour-only: b, aux r)
+          if constexpr (GEO) {
+            const float4 c1 = s_c1[4 * g + k];
+            acc2[2] = __builtin_elementwise_fma(f32x2{c1.x, c1.y}, w2, acc2[2]);
+            acc2[3] = __builtin_elementwise_fma(f32x2{c1.z, c1.w}, w2, acc2[3]);
+            if (AUX) {
+              const float4 c2 = s_c2[4 * g + k];
+              xacc2 = __builtin_elementwise_fma(f32x2{c2.x, c2.y}, w2, xacc2);
+              xacc3 = __builtin_elementwise_fma(f32x2{c2.z, c2.w}, w2, xacc3);   // (.w: a 12-byte read costs two 16-byte ones)
+            }
+          } else if (AUX) {
+            const float2 cx = s_cx[4 * g + k];
+            xacc2 = __builtin_elementwise_fma(f32x2{cx.x, cx.y}, w2, xacc2);     // (aux g, aux b)
           }
         }
       }
       float* ck = seg_state + (size_t)(slot0 + i * SUBS + h) * (SEG_FLOATS * TILE_PIX) + tid;
       ck[0] = T;
 #pragma unroll
-      for (int k = 0; k < NCH / 2; ++k) { ck[(1 + 2 * k) * TILE_PIX] = acc2[k].x; ck[(2 + 2 * k) * TILE_PIX] = acc2[k].y; }
-      ck[9 * TILE_PIX] = xacc2.x; ck[10 * TILE_PIX] = xacc2.y; ck[11 * TILE_PIX] = xacc3.x;
+      for (int k = 0; k < (GEO ? NCH : 3); ++k) ck[(1 + k) * TILE_PIX] = (k & 1) ? acc2[k / 2].y : acc2[k / 2].x;
+      ck[9 * TILE_PIX] = GEO ? xacc2.x : acc2[1].y;
+      ck[10 * TILE_PIX] = GEO ? xacc2.y : xacc2.x;
+      ck[11 * TILE_PIX] = GEO ? xacc3.x : xacc2.y;
       walked = i * SUBS + h + 1;
     }
   }
@@ -239,7 +267,7 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
     }
   }
   const float acc[NCH] = {acc2[0].x, acc2[0].y, acc2[1].x, acc2[1].y, acc2[2].x, acc2[2].y, acc2[3].x, acc2[3].y};
-  const float xacc[3] = {xacc2.x, xacc2.y, xacc3.x};
+  const float xacc[3] = {GEO ? xacc2.x : acc2[1].y, GEO ? xacc2.y : xacc2.x, GEO ? xacc3.x : xacc2.y};
   if (inside) {
     const size_t P = (size_t)c.H * c.W;
     const size_t pix_i = (size_t)pyi * c.W + pxi;
@@ -248,12 +276,14 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
     out_color[pix_i] = acc[0] + T * c.bg[0];
     out_color[P + pix_i] = acc[1] + T * c.bg[1];
     out_color[2 * P + pix_i] = acc[2] + T * c.bg[2];
-    out_depth[pix_i] = acc[3];
-    out_normal[pix_i] = acc[4];
-    out_normal[P + pix_i] = acc[5];
-    out_normal[2 * P + pix_i] = acc[6];
+    if constexpr (GEO) {
+      out_depth[pix_i] = acc[3];
+      out_normal[pix_i] = acc[4];
+      out_normal[P + pix_i] = acc[5];
+      out_normal[2 * P + pix_i] = acc[6];
+      if (out_extra) out_extra[pix_i] = acc[7];
+    }
     out_alpha[pix_i] = 1.0f - T;
-    if (out_extra) out_extra[pix_i] = acc[7];
     if (AUX) {
       out_aux[pix_i] = xacc[0] + T * c.bg[0];
       out_aux[P + pix_i] = xacc[1] + T * c.bg[1];
@@ -334,11 +364,13 @@ struct FwdSums {
   bool alive;
 };
 
+// (GEO = false: only r g b of `loc` / `acc` exist)
+template <bool GEO>
 __device__ __forceinline__ void fold_segment(FwdSums& r, int q, float T_after, const float* loc /*[NCH]*/,
                                              const float* xloc /*[3]*/, float tseg, uint32_t last_local) {
   if (r.alive) {
 #pragma unroll
-    for (int k = 0; k < NCH; ++k) r.acc[k] = __builtin_fmaf(r.P, loc[k], r.acc[k]);
+    for (int k = 0; k < (GEO ? NCH : 3); ++k) r.acc[k] = __builtin_fmaf(r.P, loc[k], r.acc[k]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) r.xacc[k] = __builtin_fmaf(r.P, xloc[k], r.xacc[k]);
     r.Tf = T_after;
@@ -347,7 +379,7 @@ __device__ __forceinline__ void fold_segment(FwdSums& r, int q, float T_after, c
   chain_step(r.P, r.alive, tseg);
 }
 
-template <bool AUX>
+template <bool AUX, bool GEO>
 #ifdef FWD_CAP128
 __global__ void __launch_bounds__(BLOCK, 4)
 #else
@@ -363,17 +395,21 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
                            const float* __restrict__ aux_colors, float* __restrict__ out_aux,
                            uint32_t* __restrict__ seg_queue, uint32_t* __restrict__ seg_count,
                            float* seg_state, uint32_t* __restrict__ tile_rounds, uint32_t* tile_sync,
-                           uint32_t* seg_flag, uint32_t* walk_hints, uint32_t* stalls, int ntiles, int share_all) {
+                           uint32_t* seg_flag, uint32_t* walk_hints, uint32_t* stalls, int ntiles, int share_all,
+                           uint32_t* __restrict__ blend_mode) {
   // two sets of record arrays: an unshared tile's workgroup stages segment s + 1 into the other set while slower waves
   // still read segment s -- ONE workgroup barrier per segment, and "is any pixel unfinished" rides on it (a flag per
   // wave instead of __syncthreads_or: the voting barriers cost the short tiles 10 % of their walk)
   __shared__ float4 s_geo[2 * SEG_LEN];            // x y A' C'   (one LDS array per read of the inner loop, see above)
   __shared__ float2 s_bo[2 * SEG_LEN];             // B' opacity
-  __shared__ float4 s_c0[2 * SEG_LEN], s_c1[2 * SEG_LEN];  // r g b depth | nx ny nz extra
-  __shared__ float4 s_c2[AUX ? 2 * SEG_LEN : 1];   // aux r g b -
+  __shared__ float4 s_c0[2 * SEG_LEN];             // r g b depth          (colour-only: r g b aux-r)
+  __shared__ float4 s_c1[GEO ? 2 * SEG_LEN : 1];   // nx ny nz extra
+  __shared__ float4 s_c2[AUX && GEO ? 2 * SEG_LEN : 1];    // aux r g b -
+  __shared__ float2 s_cx[AUX && !GEO ? 2 * SEG_LEN : 1];   // (colour-only) aux-g aux-b
   __shared__ uint32_t s_word[2];
   __shared__ uint32_t s_alive[2][BLOCK / 64];
   const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && tid == 0) *blend_mode = GEO ? MODE_FULL : MODE_COLOUR_ONLY;
   // The tiles' own workgroups come first in block order, the helpers behind them: at 128 registers all 1,024 of C3's
   // tiles are resident at once, a third of them are empty and leave within a microsecond, and the helpers take those
   // slots (helpers in FRONT delay every tile's start by the dispatch of 3 x tiles blocks that mostly leave: +6 us)
@@ -484,9 +520,14 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
     if (fetched != seg) fetch(seg);
     if (tid < SEG_LEN) {
       s_geo[lds0 + tid] = nrec0; s_bo[lds0 + tid] = make_float2(nrec1.x, nrec1.y);
-      s_c0[lds0 + tid] = make_float4(nrec1.z, nrec1.w, nrec2.x, nrec2.y);
-      s_c1[lds0 + tid] = make_float4(nrec2.z, nrec2.w, nrec3.x, nrec3.y);
-      if (AUX) s_c2[lds0 + tid] = make_float4(nrec3.z, nrec3.w, nauxb, 0.f);
+      if constexpr (GEO) {
+        s_c0[lds0 + tid] = make_float4(nrec1.z, nrec1.w, nrec2.x, nrec2.y);
+        s_c1[lds0 + tid] = make_float4(nrec2.z, nrec2.w, nrec3.x, nrec3.y);
+        if (AUX) s_c2[lds0 + tid] = make_float4(nrec3.z, nrec3.w, nauxb, 0.f);
+      } else {
+        s_c0[lds0 + tid] = make_float4(nrec1.z, nrec1.w, nrec2.x, AUX ? nrec3.z : 0.f);
+        if (AUX) s_cx[lds0 + tid] = make_float2(nrec3.w, nauxb);
+      }
     }
     bool all_posted = true;
     if (direct) {
@@ -628,16 +669,21 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float4 c0 = s_c0[lds0 + 4 * g + k];
-        const float4 c1 = s_c1[lds0 + 4 * g + k];
         const f32x2 w2 = {w[k], w[k]};
         acc2[0] = __builtin_elementwise_fma(f32x2{c0.x, c0.y}, w2, acc2[0]);
-        acc2[1] = __builtin_elementwise_fma(f32x2{c0.z, c0.w}, w2, acc2[1]);
-        acc2[2] = __builtin_elementwise_fma(f32x2{c1.x, c1.y}, w2, acc2[2]);
-        acc2[3] = __builtin_elementwise_fma(f32x2{c1.z, c1.w}, w2, acc2[3]);
-        if (AUX) {
-          const float4 c2 = s_c2[lds0 + 4 * g + k];
-          xacc2 = __builtin_elementwise_fma(f32x2{c2.x, c2.y}, w2, xacc2);
-          xacc3 = __builtin_elementwise_fma(f32x2{c2.z, c2.w}, w2, xacc3);
+        acc2[1] = __builtin_elementwise_fma(f32x2{c0.z, c0.w}, w2, acc2[1]);     // (colour-only: b, aux r)
+        if constexpr (GEO) {
+          const float4 c1 = s_c1[lds0 + 4 * g + k];
+          acc2[2] = __builtin_elementwise_fma(f32x2{c1.x, c1.y}, w2, acc2[2]);
+          acc2[3] = __builtin_elementwise_fma(f32x2{c1.z, c1.w}, w2, acc2[3]);
+          if (AUX) {
+            const float4 c2 = s_c2[lds0 + 4 * g + k];
+            xacc2 = __builtin_elementwise_fma(f32x2{c2.x, c2.y}, w2, xacc2);
+            xacc3 = __builtin_elementwise_fma(f32x2{c2.z, c2.w}, w2, xacc3);
+          }
+        } else if (AUX) {
+          const float2 cx = s_cx[lds0 + 4 * g + k];
+          xacc2 = __builtin_elementwise_fma(f32x2{cx.x, cx.y}, w2, xacc2);       // (aux g, aux b)
         }
       }
     }
@@ -646,22 +692,23 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
     const bool stopped = alive && !(pix.x < 0.5f * FAR_PIXEL);
     const float tseg = (alive && !stopped) ? T : 0.0f;
     const float loc[NCH] = {acc2[0].x, acc2[0].y, acc2[1].x, acc2[1].y, acc2[2].x, acc2[2].y, acc2[3].x, acc2[3].y};
-    const float xloc[3] = {xacc2.x, xacc2.y, xacc3.x};
+    const float xloc[3] = {GEO ? xacc2.x : acc2[1].y, GEO ? xacc2.y : xacc2.x, GEO ? xacc3.x : xacc2.y};
+    constexpr int NKEPT = GEO ? NCH : 3;               // channel planes 1 .. NKEPT of a slot exist
     if (direct) {
       // the tile is this workgroup's alone: the running sums stay in registers, the state behind the segment is stored
       // in the form the backward pass reads
-      fold_segment(sums, seg, P * T, loc, xloc, tseg, alive ? last_local : 0u);
+      fold_segment<GEO>(sums, seg, P * T, loc, xloc, tseg, alive ? last_local : 0u);
       P = sums.P; alive = sums.alive;
       st[0] = sums.Tf;
 #pragma unroll
-      for (int k = 0; k < NCH; ++k) st[(1 + k) * TILE_PIX] = sums.acc[k];
+      for (int k = 0; k < NKEPT; ++k) st[(1 + k) * TILE_PIX] = sums.acc[k];
 #pragma unroll
       for (int k = 0; k < 3; ++k) st[(9 + k) * TILE_PIX] = sums.xacc[k];
       continue;
     }
     st_agent(&st[0], P * T);
 #pragma unroll
-    for (int k = 0; k < NCH; ++k) st_agent(&st[(1 + k) * TILE_PIX], loc[k]);
+    for (int k = 0; k < NKEPT; ++k) st_agent(&st[(1 + k) * TILE_PIX], loc[k]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) st_agent(&st[(9 + k) * TILE_PIX], xloc[k]);
     if (all_posted) st_agent(&st[12 * TILE_PIX], tseg);   // (else: posted by the transmittance pass -- same verdict for the chain)
@@ -694,12 +741,12 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
       float* sq = seg_state + (size_t)(slot0 + q) * SLOT + tid;
       float v[SEG_FLOATS];
 #pragma unroll
-      for (int k = 0; k < SEG_FLOATS; ++k) v[k] = ld_agent(sq + k * TILE_PIX);
-      fold_segment(sums, q, v[0], v + 1, v + 9, v[12], __float_as_uint(v[13]));
+      for (int k = 0; k < SEG_FLOATS; ++k) v[k] = (GEO || k < 4 || k > 8) ? ld_agent(sq + k * TILE_PIX) : 0.f;
+      fold_segment<GEO>(sums, q, v[0], v + 1, v + 9, v[12], __float_as_uint(v[13]));
       // the state after segment q as the backward pass reads it: T, the sums so far
       sq[0] = sums.Tf;
 #pragma unroll
-      for (int k = 0; k < NCH; ++k) sq[(1 + k) * TILE_PIX] = sums.acc[k];
+      for (int k = 0; k < (GEO ? NCH : 3); ++k) sq[(1 + k) * TILE_PIX] = sums.acc[k];
 #pragma unroll
       for (int k = 0; k < 3; ++k) sq[(9 + k) * TILE_PIX] = sums.xacc[k];
     }
@@ -747,12 +794,14 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
     out_color[pix_i] = sums.acc[0] + Tf * c.bg[0];
     out_color[Pn + pix_i] = sums.acc[1] + Tf * c.bg[1];
     out_color[2 * Pn + pix_i] = sums.acc[2] + Tf * c.bg[2];
-    out_depth[pix_i] = sums.acc[3];
-    out_normal[pix_i] = sums.acc[4];
-    out_normal[Pn + pix_i] = sums.acc[5];
-    out_normal[2 * Pn + pix_i] = sums.acc[6];
+    if constexpr (GEO) {
+      out_depth[pix_i] = sums.acc[3];
+      out_normal[pix_i] = sums.acc[4];
+      out_normal[Pn + pix_i] = sums.acc[5];
+      out_normal[2 * Pn + pix_i] = sums.acc[6];
+      if (out_extra) out_extra[pix_i] = sums.acc[7];
+    }
     out_alpha[pix_i] = 1.0f - Tf;
-    if (out_extra) out_extra[pix_i] = sums.acc[7];
     if (AUX) {
       out_aux[pix_i] = sums.xacc[0] + Tf * c.bg[0];
       out_aux[Pn + pix_i] = sums.xacc[1] + Tf * c.bg[1];
@@ -1096,7 +1145,10 @@ blend_backward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32
                       const float* __restrict__ aux_colors, const float* __restrict__ dL_daux,
                       const uint32_t* __restrict__ seg_queue, const uint32_t* __restrict__ seg_count,
                       const float* __restrict__ seg_state, const uint32_t* __restrict__ tile_rounds,
-                      uint8_t* __restrict__ row_flag) {
+                      uint8_t* __restrict__ row_flag, const uint32_t* __restrict__ blend_mode) {
+  // a colour-only forward left no depth / normal / extra planes: the host refuses such a call where it can look at the
+  // word (instag_raster_backward); inside a stream capture it cannot, and the pass then writes no gradient row at all
+  if (FULL && *blend_mode != MODE_FULL) return;
   const uint32_t count = *seg_count;
   for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
     blend_backward_segment<FULL, AUX, XONLY>((int)seg_queue[2 * item], (int)seg_queue[2 * item + 1], c, ranges, point_list,
@@ -1114,9 +1166,13 @@ int launch_blend_forward(const Camera& c, const int32_t* ranges, const uint32_t*
                          float* out_depth, float* out_normal, float* out_alpha, float* out_extra,
                          const float* aux_colors, float* out_aux, uint32_t* seg_queue, uint32_t* seg_count,
                          float* seg_state, uint32_t* tile_rounds, uint32_t* tile_sync, uint32_t* seg_flag,
-                         uint32_t* walk_hints, int64_t instances, hipStream_t s) {
+                         uint32_t* walk_hints, int64_t instances, bool colour_only, uint32_t* blend_mode,
+                         hipStream_t s) {
   const int tiles = c.grid_x * c.grid_y;
   if (tiles == 0) return INSTAG_OK;
+  // which channel set (template parameter GEO): 0 = all, 1 = colour-only; x 2 for the aux colour set
+  const int variant = (aux_colors ? 2 : 0) | (colour_only ? 1 : 0);
+  if (!aux_colors) out_aux = nullptr;
   // Which forward kernel: the segment-wise one pays where tiles walk far (its helpers cut those chains); on a small
   // scene -- the mouth's 20k Gaussians -- every tile is short and its bookkeeping costs 5 %.  By the instance count, so
   // that the eager and the captured form of one scene run the same arithmetic.  INSTAG_BLEND_FWD=tile / segment forces
@@ -1136,27 +1192,29 @@ int launch_blend_forward(const Camera& c, const int32_t* ranges, const uint32_t*
 #endif
     const int grid = (walk_hints || share_all) ? tiles * (1 + FWD_HELPERS) : tiles;
     uint32_t* stalls = sort_stalls_device_ptr();
-    if (aux_colors)
-      blend_forward_claim_kernel<true><<<grid, BLOCK, 0, s>>>(c, ranges, point_list, rec2d, n_contrib, final_T, out_color,
-                                                              out_depth, out_normal, out_alpha, out_extra, aux_colors,
-                                                              out_aux, seg_queue, seg_count, seg_state, tile_rounds,
-                                                              tile_sync, seg_flag, walk_hints, stalls, tiles, share_all);
-    else
-      blend_forward_claim_kernel<false><<<grid, BLOCK, 0, s>>>(c, ranges, point_list, rec2d, n_contrib, final_T, out_color,
-                                                               out_depth, out_normal, out_alpha, out_extra, nullptr,
-                                                               nullptr, seg_queue, seg_count, seg_state, tile_rounds,
-                                                               tile_sync, seg_flag, walk_hints, stalls, tiles, share_all);
+#define INSTAG_BF(A, G)                                                                                                 \
+  blend_forward_claim_kernel<A, G><<<grid, BLOCK, 0, s>>>(c, ranges, point_list, rec2d, n_contrib, final_T, out_color,   \
+                                                          out_depth, out_normal, out_alpha, out_extra, aux_colors,      \
+                                                          out_aux, seg_queue, seg_count, seg_state, tile_rounds,        \
+                                                          tile_sync, seg_flag, walk_hints, stalls, tiles, share_all,    \
+                                                          blend_mode)
+    if (variant == 3) INSTAG_BF(true, false);
+    else if (variant == 2) INSTAG_BF(true, true);
+    else if (variant == 1) INSTAG_BF(false, false);
+    else INSTAG_BF(false, true);
+#undef INSTAG_BF
     INSTAG_CHECK_LAUNCH();
     return INSTAG_OK;
   }
-  if (aux_colors)
-    blend_forward_kernel<true><<<tiles, BLOCK, 0, s>>>(c, ranges, point_list, rec2d, n_contrib, final_T, out_color,
-                                                       out_depth, out_normal, out_alpha, out_extra, aux_colors, out_aux,
-                                                       seg_queue, seg_count, seg_state, tile_rounds);
-  else
-    blend_forward_kernel<false><<<tiles, BLOCK, 0, s>>>(c, ranges, point_list, rec2d, n_contrib, final_T, out_color,
-                                                        out_depth, out_normal, out_alpha, out_extra, nullptr, nullptr,
-                                                        seg_queue, seg_count, seg_state, tile_rounds);
+#define INSTAG_BF(A, G)                                                                                                 \
+  blend_forward_kernel<A, G><<<tiles, BLOCK, 0, s>>>(c, ranges, point_list, rec2d, n_contrib, final_T, out_color,        \
+                                                     out_depth, out_normal, out_alpha, out_extra, aux_colors, out_aux,  \
+                                                     seg_queue, seg_count, seg_state, tile_rounds, blend_mode)
+  if (variant == 3) INSTAG_BF(true, false);
+  else if (variant == 2) INSTAG_BF(true, true);
+  else if (variant == 1) INSTAG_BF(false, false);
+  else INSTAG_BF(false, true);
+#undef INSTAG_BF
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
@@ -1167,7 +1225,8 @@ int launch_blend_backward(const Camera& c, const int32_t* ranges, const uint32_t
                           const float* dL_dalpha, const float* dL_dextra, float* inst_grad,
                           const float* color_override, const float* aux_colors, const float* dL_daux, int aux_mode,
                           const uint32_t* seg_queue, const uint32_t* seg_count, const float* seg_state,
-                          const uint32_t* tile_rounds, uint32_t seg_slots, uint8_t* row_flag, hipStream_t s) {
+                          const uint32_t* tile_rounds, uint32_t seg_slots, uint8_t* row_flag,
+                          const uint32_t* blend_mode, hipStream_t s) {
   // aux_mode: 0 none, 1 whole aux image in this launch, 2 aux colours' gradient only, 3 mean-only pass over
   // `color_override` (rows carry dx, dy)
   const int tiles = c.grid_x * c.grid_y;
@@ -1188,7 +1247,8 @@ int launch_blend_backward(const Camera& c, const int32_t* ranges, const uint32_t
 #define INSTAG_BB(F, A, X, d, n, e, ax, dax)                                                                            \
   blend_backward_kernel<F, A, X><<<grid, BLOCK, 0, s>>>(c, ranges, point_list, slot_list, rec2d, n_contrib, final_T,     \
                                                        dL_dcolor, d, n, dL_dalpha, e, inst_grad, color_override, ax,    \
-                                                       dax, seg_queue, seg_count, seg_state, tile_rounds, row_flag)
+                                                       dax, seg_queue, seg_count, seg_state, tile_rounds, row_flag,     \
+                                                       blend_mode)
   if (aux_mode == 1) INSTAG_BB(false, 1, false, nullptr, nullptr, nullptr, aux_colors, dL_daux);
   else if (aux_mode == 2) INSTAG_BB(false, 2, false, nullptr, nullptr, nullptr, aux_colors, dL_daux);
   else if (aux_mode == 3) INSTAG_BB(false, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr);

@@ -94,14 +94,17 @@ int launch_blend_forward(const Camera& c, const int32_t* ranges, const uint32_t*
                          const float* aux_colors, float* out_aux, uint32_t* seg_queue, uint32_t* seg_count,
                          float* seg_state, uint32_t* tile_rounds, uint32_t* tile_sync /* zeroed, or NULL */,
                          uint32_t* seg_flag /* zeroed */, uint32_t* walk_hints /* persistent, or NULL */,
-                         int64_t instances, hipStream_t s);
+                         int64_t instances, bool colour_only /* no depth / normal / extra image */,
+                         uint32_t* blend_mode /* ImageLayout::blend_mode: written with the variant that ran */,
+                         hipStream_t s);
 int launch_blend_backward(const Camera& c, const int32_t* ranges, const uint32_t* point_list,
                           const uint32_t* slot_list, const float* rec2d, const uint32_t* n_contrib, const float* final_T,
                           const float* dL_dcolor, const float* dL_ddepth, const float* dL_dnormal,
                           const float* dL_dalpha, const float* dL_dextra, float* inst_grad,
                           const float* color_override, const float* aux_colors, const float* dL_daux, int aux_mode,
                           const uint32_t* seg_queue, const uint32_t* seg_count, const float* seg_state,
-                          const uint32_t* tile_rounds, uint32_t seg_slots, uint8_t* row_flag, hipStream_t s);
+                          const uint32_t* tile_rounds, uint32_t seg_slots, uint8_t* row_flag,
+                          const uint32_t* blend_mode, hipStream_t s);
 
 // raster_backward.hip
 int launch_preprocess_backward(const Camera& c, const instag_raster_args* a, const float* rec2d,

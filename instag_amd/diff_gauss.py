@@ -154,7 +154,8 @@ def set_capacity_plan(plan):
 
 class _State:
     """Opaque device buffers kept between forward and backward (geom / binning / image)."""
-    __slots__ = ("args", "keep", "geom", "binning", "image", "R", "radii", "N", "H", "W", "E", "M", "aux", "split_sh")
+    __slots__ = ("args", "keep", "geom", "binning", "image", "R", "radii", "N", "H", "W", "E", "M", "aux", "split_sh",
+                 "geometry")
 
 
 def _make_args(s: GaussianRasterizationSettings, means3D, shs, colors, opac, scales, rots, cov3D, extra):
@@ -182,9 +183,12 @@ def _make_args(s: GaussianRasterizationSettings, means3D, shs, colors, opac, sca
     return a, keep, N, M, E
 
 
-def rasterize_forward(settings, means3D, shs, colors, opac, scales, rots, cov3D, extra, aux_colors=None):
+def rasterize_forward(settings, means3D, shs, colors, opac, scales, rots, cov3D, extra, aux_colors=None,
+                      geometry=True):
     """Run the forward (two-stage with one host round trip, or sync-free under a CapacityPlan).
-    Returns (outputs, state); with aux_colors [N,3] the outputs carry a 7th image [3,H,W]."""
+    Returns (outputs, state); with aux_colors [N,3] the outputs carry a 7th image [3,H,W].
+    ``geometry=False``: the colour-only forward blend -- depth, normal and extra are neither blended nor allocated and
+    come back as None; image, alpha, aux and the state the rgb / aux backward reads are bit-identical."""
     L = _lib.lib()
     dev = means3D.device
     a, keep, N, M, E = _make_args(settings, means3D, shs, colors, opac, scales, rots, cov3D, extra)
@@ -194,10 +198,10 @@ def rasterize_forward(settings, means3D, shs, colors, opac, scales, rots, cov3D,
     radii = torch.empty(N, dtype=torch.int32, device=dev)
     image = torch.empty(L.instag_raster_image_bytes(H, W), dtype=torch.uint8, device=dev)
     color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-    depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-    normal = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+    depth = torch.empty(1, H, W, dtype=torch.float32, device=dev) if geometry else None
+    normal = torch.empty(3, H, W, dtype=torch.float32, device=dev) if geometry else None
     alpha = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-    extra_img = torch.empty(E, H, W, dtype=torch.float32, device=dev)
+    extra_img = torch.empty(E, H, W, dtype=torch.float32, device=dev) if geometry else None
     aux_img = torch.empty(3, H, W, dtype=torch.float32, device=dev) if aux_colors is not None else None
     if _CAPACITY_PLAN is not None:
         R, status, hints = _CAPACITY_PLAN.next_slot()
@@ -207,8 +211,8 @@ def rasterize_forward(settings, means3D, shs, colors, opac, scales, rots, cov3D,
         check(L.instag_raster_forward_capacity(C.byref(a), ptr(geom), geom.numel(), ptr(binning), binning.numel(),
                                                ptr(image), image.numel(), R, ptr(radii), ptr(status), ptr(color),
                                                ptr(depth), ptr(normal), ptr(alpha),
-                                               ptr(extra_img) if E > 0 else None, ptr(aux_colors), ptr(aux_img),
-                                               stream), "rasterize_gaussians")
+                                               ptr(extra_img) if (E > 0 and geometry) else None, ptr(aux_colors),
+                                               ptr(aux_img), stream), "rasterize_gaussians")
     else:
         Rc = C.c_int64(0)
         check(L.instag_raster_forward_stage1(C.byref(a), ptr(geom), geom.numel(), ptr(radii), C.byref(Rc), stream),
@@ -220,13 +224,14 @@ def rasterize_forward(settings, means3D, shs, colors, opac, scales, rots, cov3D,
         binning = torch.empty(L.instag_raster_binning_bytes(R, H, W), dtype=torch.uint8, device=dev)
         check(L.instag_raster_forward_stage2(C.byref(a), ptr(geom), geom.numel(), ptr(binning), binning.numel(),
                                              ptr(image), image.numel(), R, ptr(color), ptr(depth), ptr(normal),
-                                             ptr(alpha), ptr(extra_img) if E > 0 else None, ptr(aux_colors),
+                                             ptr(alpha), ptr(extra_img) if (E > 0 and geometry) else None, ptr(aux_colors),
                                              ptr(aux_img), stream),
               "rasterize_gaussians")
     st = _State()
     st.args, st.keep, st.geom, st.binning, st.image = a, keep, geom, binning, image
     st.R, st.radii, st.N, st.H, st.W, st.E, st.M = R, radii, N, H, W, E, M
     st.aux = aux_colors
+    st.geometry = bool(geometry)
     st.split_sh = isinstance(shs, (tuple, list)) and shs[1].shape[1] > 0
     if KEEP_LAST_STATE:
         LAST_STATS["state"] = st
@@ -320,6 +325,9 @@ def rasterize_backward(st: _State, g_color, g_depth, g_normal, g_alpha, g_extra,
     dev = st.geom.device
     N, M = st.N, st.M
     stream = _lib.current_stream()
+    if not st.geometry and (g_depth is not None or g_normal is not None or (g_extra is not None and st.E > 0)):
+        raise RuntimeError("rasterize_gaussians_backward: a depth / normal / extra gradient over a colour-only forward "
+                           "(geometry=False), which kept no such channels")
 
     def buf(flag, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=dev) if flag else None
@@ -357,7 +365,7 @@ def rasterize_backward(st: _State, g_color, g_depth, g_normal, g_alpha, g_extra,
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                extra_attrs, raster_settings, aux_colors=None, sh_rest=None):
+                extra_attrs, raster_settings, aux_colors=None, sh_rest=None, geometry=True):
         _require_cuda(means3D=means3D)
         ctx.set_materialize_grads(False)      # unused outputs (depth / normal / extra) stay NULL in backward
         m3, shs, col = _f32c(means3D), _f32c(sh), _f32c(colors_precomp)
@@ -370,7 +378,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                       rotations=ro, cov3Ds_precomp=cov, extra_attrs=ex, aux_colors=aux)
         if aux is not None and tuple(aux.shape) != (m3.shape[0], 3):
             raise RuntimeError("aux_colors must be [N,3]")
-        outs, st = rasterize_forward(raster_settings, m3, shs, col, op, sc, ro, cov, ex, aux)
+        outs, st = rasterize_forward(raster_settings, m3, shs, col, op, sc, ro, cov, ex, aux, geometry=geometry)
         ctx.state = st
         ctx.shapes = (opacities.shape, None if extra_attrs is None else extra_attrs.shape)
         ctx.means2D_leaf = means2D if (means2D is not None and means2D.is_leaf and means2D.requires_grad) else None
@@ -452,16 +460,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_op = None if g["opacities"] is None else g["opacities"].reshape(op_shape)
         g_ex = None if g["extra"] is None else g["extra"].reshape(ex_shape)
         return (g["means3D"], g["means2D"], g["shs"], g["colors"], g_op, g["scales"], g["rotations"],
-                g["cov3D"], g_ex, None, d_aux, g.get("shs_rest"))
+                g["cov3D"], g_ex, None, d_aux, g.get("shs_rest"), None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        extra_attrs, raster_settings, aux_colors=None):
+                        extra_attrs, raster_settings, aux_colors=None, geometry=True):
     sh_rest = None
     if isinstance(sh, (tuple, list)):
         sh, sh_rest = sh
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, extra_attrs, raster_settings, aux_colors, sh_rest)
+                                     cov3Ds_precomp, extra_attrs, raster_settings, aux_colors, sh_rest, bool(geometry))
 
 
 class GaussianRasterizer(nn.Module):
@@ -477,12 +485,15 @@ class GaussianRasterizer(nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3Ds_precomp=None, extra_attrs=None, aux_colors=None):
+                cov3Ds_precomp=None, extra_attrs=None, aux_colors=None, geometry=True):
         """Same call and 6-tuple as the reference's rasterizer.  Extension: ``aux_colors`` [N,3] appends a 7th
         output, the image a second call with ``colors_precomp=aux_colors`` on the detached geometry would
         return (gradients reach aux_colors and means2D only), at the cost of three more blend channels.
         ``shs`` may also be the pair (features_dc [N,1,3], features_rest [N,M-1,3]) the Gaussian model stores
-        (scene/gaussian_model.py:183-186 concatenates them on every call): same result without the copy."""
+        (scene/gaussian_model.py:183-186 concatenates them on every call): same result without the copy.
+        Extension: ``geometry=False`` runs the colour-only forward blend for a caller that reads neither depth, normal
+        nor extra: those three come back as None (and so can carry no gradient); every other output and gradient is
+        bit-identical to the full call's."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3Ds_precomp is None) or \
@@ -491,37 +502,59 @@ class GaussianRasterizer(nn.Module):
         if extra_attrs is not None and extra_attrs.dim() > 1 and extra_attrs.shape[1] > 1:
             raise RuntimeError("extra_attrs: only [N] / [N,1] is supported by the MI355X rasterizer")
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3Ds_precomp, extra_attrs, self.raster_settings, aux_colors)
+                                   cov3Ds_precomp, extra_attrs, self.raster_settings, aux_colors, geometry)
 
 
-def debug_export(st: _State):
-    """Integer / per-Gaussian state of a forward pass as torch tensors (bit-exact parity tests)."""
+def debug_export(st: _State, lists: bool = True):
+    """Integer / per-Gaussian state of a forward pass as torch tensors (bit-exact parity tests).
+    ``lists=False``: only what every state holds in full -- the per-pixel and per-tile words and the backward blend's
+    work list.  (A capacity-mode state has R = the capacity: the instance lists behind the binned count are not data.)"""
     L = _lib.lib()
     dev = st.geom.device
     N, R, H, W = st.N, st.R, st.H, st.W
     tiles = ((W + 15) // 16) * ((H + 15) // 16)
     out = dict(
-        tiles_touched=torch.zeros(N, dtype=torch.int32, device=dev),
-        point_offsets=torch.zeros(N, dtype=torch.int32, device=dev),
-        keys=torch.zeros(R, dtype=torch.int64, device=dev),
-        point_list=torch.zeros(R, dtype=torch.int32, device=dev),
         ranges=torch.zeros(tiles, 2, dtype=torch.int32, device=dev),
         n_contrib=torch.zeros(H, W, dtype=torch.int32, device=dev),
         final_T=torch.zeros(H, W, dtype=torch.float32, device=dev),
-        rec2d=torch.zeros(N, 16, dtype=torch.float32, device=dev),
     )
-    check(L.instag_raster_debug_export(ptr(st.geom), st.geom.numel(), ptr(st.binning), st.binning.numel(),
+    if lists:
+        out.update(
+            tiles_touched=torch.zeros(N, dtype=torch.int32, device=dev),
+            point_offsets=torch.zeros(N, dtype=torch.int32, device=dev),
+            keys=torch.zeros(R, dtype=torch.int64, device=dev),
+            point_list=torch.zeros(R, dtype=torch.int32, device=dev),
+            rec2d=torch.zeros(N, 16, dtype=torch.float32, device=dev),
+        )
+    check(L.instag_raster_debug_export(ptr(st.geom) if lists else None, st.geom.numel(),
+                                       ptr(st.binning) if lists else None, st.binning.numel(),
                                        ptr(st.image), st.image.numel(), N, R, H, W,
-                                       ptr(out["tiles_touched"]), ptr(out["point_offsets"]), ptr(out["keys"]),
-                                       ptr(out["point_list"]), ptr(out["ranges"]), ptr(out["n_contrib"]),
-                                       ptr(out["final_T"]), ptr(out["rec2d"]), _lib.current_stream()),
+                                       ptr(out.get("tiles_touched")), ptr(out.get("point_offsets")), ptr(out.get("keys")),
+                                       ptr(out.get("point_list")), ptr(out["ranges"]), ptr(out["n_contrib"]),
+                                       ptr(out["final_T"]), ptr(out.get("rec2d")), _lib.current_stream()),
           "debug_export")
-    flags = torch.zeros(N, dtype=torch.int32, device=dev)
-    check(L.instag_raster_debug_export_flags(ptr(st.geom), st.geom.numel(), N, ptr(flags), _lib.current_stream()),
-          "debug_export_flags")
-    rect = out["rec2d"][:, 15].contiguous().view(torch.int32)
-    # bounding tile rectangle (min x, min y, width, height) of the published binning; defined where radii > 0
-    out["rect"] = torch.stack([rect & 1023, (rect >> 10) & 1023, (rect >> 20) & 4095, (flags >> 16) & 0xFFFF], dim=1)
+    if lists:
+        flags = torch.zeros(N, dtype=torch.int32, device=dev)
+        check(L.instag_raster_debug_export_flags(ptr(st.geom), st.geom.numel(), N, ptr(flags), _lib.current_stream()),
+              "debug_export_flags")
+        rect = out["rec2d"][:, 15].contiguous().view(torch.int32)
+        # bounding tile rectangle (min x, min y, width, height) of the published binning; defined where radii > 0
+        out["rect"] = torch.stack([rect & 1023, (rect >> 10) & 1023, (rect >> 20) & 4095, (flags >> 16) & 0xFFFF], dim=1)
     out["R"] = R
     out["radii"] = st.radii
+    # False: the forward was colour-only.  It kept no depth / normal / extra channels: the segment slots' planes of
+    # those channels hold no data and are not exported in any form
+    out["geometry"] = st.geometry
+    if R > 0 and N > 0:
+        # the backward blend's work list, as sorted (tile << 20 | segment) codes (the list's own order is that of atomics)
+        slots = R // 128 + tiles + 2
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        mode = torch.zeros(1, dtype=torch.int32, device=dev)
+        pairs = torch.zeros(slots, 2, dtype=torch.int32, device=dev)
+        check(L.instag_raster_debug_export_work_list(ptr(st.binning), st.binning.numel(), ptr(st.image), st.image.numel(),
+                                                     R, H, W, ptr(count), ptr(pairs), slots, ptr(mode),
+                                                     _lib.current_stream()), "debug_export_work_list")
+        pairs = pairs[:min(max(int(count.item()), 0), slots)].long()
+        out["work_list"] = torch.sort(pairs[:, 0] * (1 << 20) + pairs[:, 1]).values
+        out["blend_mode"] = int(mode.item())
     return out

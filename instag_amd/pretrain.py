@@ -215,7 +215,8 @@ class PretrainFaceTrainer:
             heads = other_pmf_heads([o.neural_motion_grid for j, o in enumerate(self.ids) if j != idx], g.get_xyz,
                                     td["auds"].to(dev), td["au_exp"].to(dev))
         pkg = render_motion(frame, g, self.motion_net, None, self.bg, return_attn=True, personalized=True,
-                            align=False, pretrain_heads=heads, pretrain_reg=phase.warm)
+                            align=False, pretrain_heads=heads, pretrain_reg=phase.warm,
+                            need_geometry=False)      # (no loss term of this step reads depth / normal)
         if not phase.warm:
             loss, l1 = face_loss(pkg["render"], gt, face, hair, mouth, self.bg, lambda_dssim=self.opt.lambda_dssim)
             return pkg, loss, l1

@@ -149,14 +149,16 @@ def _ones(like):
 
 def render_motion(viewpoint_camera, pc, motion_net, pipe=None, bg_color=None, scaling_modifier=1.0, frame_idx=None,
                   return_attn=False, personalized=False, align=False, detach_motion=False, motion_reg_weight=None,
-                  pretrain_heads=None, pretrain_reg=True):
+                  pretrain_heads=None, pretrain_reg=True, need_geometry=True):
     """Render with the universal (motion_net) and personalised (pc.neural_motion_grid) motion fields.
     ``motion_reg_weight`` (extension): also return ``motion_reg`` = partial sums of weight * the motion regulariser of
     train_face.py:510-514, computed inside the fused deform operator (None when that operator is not used).
     ``pretrain_heads`` (extension, personalized=True and align=False only): the other identities' PMF head outputs
     [N,11] of the pretraining step (pretrain_face.py); the deformation runs in the pretraining operator
     (glue.pretrain_deform) and ``motion_reg`` holds partial sums of that step's regularisers and contrast term
-    (``pretrain_reg=False``: not computed, ``motion_reg`` is None)."""
+    (``pretrain_reg=False``: not computed, ``motion_reg`` is None).
+    ``need_geometry=False`` (extension): the caller reads neither ``depth`` nor ``normal`` -- both are None and the
+    rasterizer runs its colour-only forward blend; everything else is bit-identical."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
                                               getattr(pipe, "debug", False)))
@@ -348,7 +350,7 @@ def render_motion(viewpoint_camera, pc, motion_net, pipe=None, bg_color=None, sc
     outs = rasterizer(
         means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=opacity,
         scales=scales, rotations=rotations, cov3Ds_precomp=None, extra_attrs=ones,
-        **({"aux_colors": aux} if shared else {}))
+        **({"aux_colors": aux} if shared else {}), **({} if need_geometry else {"geometry": False}))
     image, depth, normal, alpha, radii, extra = outs[:6]
     if shared:
         rendered_attn = outs[6]

@@ -434,8 +434,10 @@ class FaceTrainer:
     # ---- one step ---------------------------------------------------------------------------------------------
     def _forward_backward(self, frame: Frame, phase: FacePhase = C3_PHASE, fold_aux: bool = False):
         from .renderer import render_motion
+        # (depth and normal are read by the prior terms alone: outside that phase the forward blend is colour-only)
         pkg = render_motion(frame, self.g, self.motion_net, None, self.bg, return_attn=True, personalized=False,
-                            align=phase.align, motion_reg_weight=1e-5 if phase.warm else None)
+                            align=phase.align, motion_reg_weight=1e-5 if phase.warm else None,
+                            need_geometry=phase.priors)
         from contextlib import nullcontext
         from .losses import defer_finalize
         # (backward follows at once and the loss value is read after the step: the loss block's scalar stage rides in
@@ -474,7 +476,8 @@ class FaceTrainer:
         renderer.MARK_BACKWARD_CUT = True
         try:
             pkg = render_motion(frame, self.g, self.motion_net, None, self.bg, return_attn=True, personalized=False,
-                                align=phase.align, motion_reg_weight=1e-5 if phase.warm else None)
+                                align=phase.align, motion_reg_weight=1e-5 if phase.warm else None,
+                                need_geometry=phase.priors)
         finally:
             renderer.MARK_BACKWARD_CUT = False
         from contextlib import nullcontext
