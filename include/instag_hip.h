@@ -658,6 +658,48 @@ int instag_window_mean_backward(int32_t C, int32_t H, int32_t W, int32_t ch, con
                                 const float* g, float* dx, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LPIPS patch loss (csrc/lpips.hip): the `lpips` package's criterion with net='alex' in eval mode
+ * (lpipsPyTorch/modules/{lpips,networks,utils}.py) on the square patches that
+ * F.unfold(img[None], p, stride=p) cuts (utils/loss_utils.py:22-24), as train_face.py:596-620 and
+ * train_fuse_con.py:186-193 use it.  fp32, forward and the gradient with respect to the image.
+ *
+ *  image, gt: [3,H,W] in [0,1] (n_stack == 0; patches are addressed in place, `* 2 - 1` and the
+ *    shift / scale are applied on the fly, the remainder rows and columns are dropped), or
+ *    [n_stack,3,p,p] stacks of patches in [-1,1], the criterion's own input (n_stack > 0,
+ *    p_min == p_max == p; H, W and rect are not read).
+ *  p_dev: the patch size, a device int32.  Buffers and grids are sized for the declared range
+ *    [p_min, p_max] (p_min >= 31), so one captured launch sequence serves every size of the range;
+ *    p_host >= 0 is the same value on the host and is validated, p_host < 0 = not known (the kernels
+ *    then do nothing for a value outside the range).
+ *  rect: device int32 (r0, r1, c0, c1) or NULL; image[:, r0:r1, c0:c1] and the same window of gt
+ *    read as bg[c] (train_face.py:606-607), and the gradient is zero there.
+ *  weights: wf[l] = conv l's weight as [K padded to a multiple of 32][Cout] with k = (cin, ky, kx);
+ *    bias[l]; wb[0] = conv1's weight as stored [64,3,11,11], wb[l >= 1] = [(cout, ky, kx)][Cin] of
+ *    the weight flipped in ky, kx; lin[l] = the 1x1 convolution's [C] weights.
+ *  forward: per_patch [instag_lpips_max_patches] (entries beyond the live count are zero),
+ *    mean_out (may be NULL) = mean over the live patches.  The workspace keeps what backward reads.
+ *  backward: g = the gradient of the mean (g_per_patch == 0) or one per patch; dimage like image,
+ *    exact zeros in the dropped remainder and inside rect.
+ * Every sum has a fixed order (no float atomics): repeated runs and graph replays give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_lpips_weights {
+  const float* wf[5];
+  const float* bias[5];
+  const float* wb[5];
+  const float* lin[5];
+} instag_lpips_weights;
+size_t instag_lpips_workspace_bytes(int32_t H, int32_t W, int32_t p_min, int32_t p_max, int32_t n_stack);
+int instag_lpips_max_patches(int32_t H, int32_t W, int32_t p_min, int32_t p_max, int32_t n_stack);
+int instag_lpips_forward(const instag_lpips_weights* w, const float* image, const float* gt, const int32_t* p_dev,
+                         int32_t p_host, const int32_t* rect, const float* bg, int32_t H, int32_t W, int32_t p_min,
+                         int32_t p_max, int32_t n_stack, void* workspace, size_t workspace_bytes, float* per_patch,
+                         float* mean_out, instag_stream_t stream);
+int instag_lpips_backward(const instag_lpips_weights* w, const int32_t* p_dev, int32_t p_host, const int32_t* rect,
+                          const float* g, int32_t g_per_patch, int32_t H, int32_t W, int32_t p_min, int32_t p_max,
+                          int32_t n_stack, void* workspace, size_t workspace_bytes, float* dimage,
+                          instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named
  * kernel with hipEvents on the launch stream; instag_prof_read synchronises those events and
  * returns accumulated milliseconds and launch count since the last reset.

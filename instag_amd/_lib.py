@@ -29,6 +29,11 @@ class FaceLossCfg(C.Structure):
                 ("w_attn_hair", f32), ("w_attn_lips", f32), ("w_extra", f32)]
 
 
+class LpipsWeights(C.Structure):
+    """struct instag_lpips_weights (include/instag_hip.h)."""
+    _fields_ = [("wf", vp * 5), ("bias", vp * 5), ("wb", vp * 5), ("lin", vp * 5)]
+
+
 class WgradJob(C.Structure):
     """struct instag_wgrad_job (include/instag_hip.h)."""
     _fields_ = [("dz", vp), ("inp", vp), ("dw", vp), ("N", i32), ("O", i32), ("K", i32)]
@@ -302,6 +307,12 @@ _PROTOS = {
     "instag_pretrain_deform_backward": (C.c_int, [vp] * 6 + [i32] + [vp] * 11 + [i32, vp]),
     "instag_window_mean_forward": (C.c_int, [vp, i32, i32, i32, i32, vp, f32, vp, i32, vp, vp]),
     "instag_window_mean_backward": (C.c_int, [i32, i32, i32, i32, vp, f32, vp, vp, vp]),
+    "instag_lpips_workspace_bytes": (sz, [i32] * 5),
+    "instag_lpips_max_patches": (C.c_int, [i32] * 5),
+    "instag_lpips_forward": (C.c_int, [C.POINTER(LpipsWeights), vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, sz,
+                                       vp, vp, vp]),
+    "instag_lpips_backward": (C.c_int, [C.POINTER(LpipsWeights), vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz,
+                                        vp, vp]),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

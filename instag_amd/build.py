@@ -46,6 +46,7 @@ SOURCES = {
     "select.hip": [],
     "prior.hip": [],
     "pretrain.hip": ["-ffp-contract=off"],
+    "lpips.hip": [],
 }
 
 

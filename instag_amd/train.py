@@ -4,7 +4,8 @@ Counterpart of /root/reference/train_face.py:110-788 restricted to the hot path:
 (:346-350) -> L1 + 0.2*(1-SSIM) (:450-456) + regularisers (:508-540) -> backward (:625) ->
 densification statistics / density control (:667-746) -> AdamW / Adam steps (:781-788), in the reference's
 iteration-dependent phases (face_phase: alignment, warm terms, hair iterations, monocular normal / depth
-priors :458-504).  LPIPS and logging are out of scope.
+priors :458-504, the late phase's LPIPS patch term :333-335, 596-620 with ``FaceTrainer(..., lpips=LPIPSWeights)``).
+Logging is out of scope.
 
 Two execution modes with identical arithmetic:
   * eager  -- every operator is launched from Python (one host round trip per rasterizer pass);
@@ -27,6 +28,7 @@ from types import SimpleNamespace
 from typing import List, Optional
 
 import os
+import random
 import torch
 import torch.distributed as dist
 
@@ -350,7 +352,10 @@ class FaceTrainer:
 
     def __init__(self, gaussians: GaussianModel, motion_net, background, opt=OptimizationParams,
                  cameras_extent: float = 0.2, densify: bool = True, seed: int = 0, schedule: Optional[str] = None,
-                 warm_step: int = 3000):
+                 warm_step: int = 3000, lpips=None):
+        """``lpips`` (instag_amd.lpips.LPIPSWeights): with ``schedule="reference"`` the iterations above
+        densify_until_iter - 1500 close the mouth mask and add 0.01 * PatchLPIPS(image_white, gt_image_white, p,
+        lips_rect, bg), p = 2 * randint(32, 48) (train_face.py:333-335, 596-620)."""
         assert schedule in (None, "reference")
         self.schedule = schedule
         self.warm_step = warm_step
@@ -380,9 +385,38 @@ class FaceTrainer:
         self._graph_cache = {}        # phase -> captured step
         self._graph_mode = None       # set by enable_graph: headroom / split / sticky capacity of the captured steps
         self._pool = None             # one private memory pool for every capture of this trainer (re-captures reuse it)
+        self.lpips = lpips
+        self.rng = random.Random(seed)                                  # patch size, train_face.py:609
+        self._patch_op = None
+        # the LPIPS patch size of the step being run: a host int (eager launches), "device" (a captured step reads
+        # _p_dev, which rides on the learning-rate upload like MouthTrainer._k_dev), None = the term is off
+        self._lpips_p = None
+        self._p_own = None
+        if lpips is not None and self.on_gpu:
+            self._p_own = torch.full((1,), 64, dtype=torch.int64, device=dev)
+            if self.optimizers.combined is not None:
+                self.optimizers.combined.reserve_extra_i64(1)
         self.recaptures = 0
         self.recapture_seconds = 0.0  # host time of the re-captures
         self.density_seconds = 0.0    # host time of the density-control events (they synchronise)
+
+    @property
+    def _p_dev(self):
+        combined = self.optimizers.combined
+        view = combined.extra_i64() if (combined is not None and self.lpips is not None) else None
+        return view if view is not None else self._p_own
+
+    def _stage_p(self, p):
+        """Call in FRONT of _set_learning_rates (whose upload carries the value)."""
+        combined = self.optimizers.combined
+        if combined is not None and combined.extra_i64() is not None:
+            combined.set_extra_i64([p])
+        else:
+            self._p_own.fill_(p)
+
+    def lpips_on(self, it: int) -> bool:
+        from .lpips import face_lpips_on
+        return self.lpips is not None and self.schedule == "reference" and face_lpips_on(it, self.opt)
 
     def _set_learning_rates(self, it):
         """Per-step schedules (train_face.py:60, scene/gaussian_model.py:421-427) written into the lr slots."""
@@ -403,11 +437,16 @@ class FaceTrainer:
         return face_phase(it, self.opt, self.warm_step) if self.schedule == "reference" else C3_PHASE
 
     def loss_fn(self, frame: Frame, pkg, warm: bool, hair_mask_iter: bool = False, priors: bool = False,
-                prior_depth: bool = False):
+                prior_depth: bool = False, lpips_p=None):
         """-> (loss, Ll1).  `warm` = iteration > warm_step: motion regularisers, alpha and attention terms;
-        `priors` / `prior_depth`: the monocular normal / depth terms of train_face.py:458-504."""
+        `priors` / `prior_depth`: the monocular normal / depth terms of train_face.py:458-504; `lpips_p`: the patch
+        size of the late phase's LPIPS term (:333-335 closed mouth mask, :596-620), None = off."""
         dev = self.bg.device
         td = frame.talking_dict
+        mouth_mask = td["mouth_mask"].to(dev)
+        if lpips_p is not None:
+            from .lpips import close_mask
+            mouth_mask = close_mask(mouth_mask)
         extra = alpha = attn = lips = None
         w_extra = 1e-5
         if warm:
@@ -421,15 +460,29 @@ class FaceTrainer:
                          + m["d_scale"].abs().mean() + pm["p_xyz"].abs().mean())
             alpha, attn, lips = pkg["alpha"], pkg["attn"], td["lips_rect"].to(dev)
         loss, Ll1 = face_loss(pkg["render"], frame.original_image.to(dev), td["face_mask"].to(dev),
-                              td["hair_mask"].to(dev), td["mouth_mask"].to(dev), self.bg, alpha=alpha, attn=attn,
+                              td["hair_mask"].to(dev), mouth_mask, self.bg, alpha=alpha, attn=attn,
                               lips_rect=lips, extra=extra, lambda_dssim=self.opt.lambda_dssim, w_extra=w_extra,
                               hair_mask_iter=hair_mask_iter)
         if priors:
             from .losses import geometry_prior_loss
             loss = loss + geometry_prior_loss(pkg["normal"], pkg["depth"], td["normal"].to(dev),
                                               td["depth"].to(dev) if prior_depth else None, td["face_mask"].to(dev),
-                                              td["hair_mask"].to(dev), td["mouth_mask"].to(dev), use_depth=prior_depth)
+                                              td["hair_mask"].to(dev), mouth_mask, use_depth=prior_depth)
+        if lpips_p is not None:
+            from .lpips import FACE_LPIPS_WEIGHT, FACE_PATCH_RANGE, PatchLPIPS
+            gt = frame.original_image.to(dev)
+            keep = (td["face_mask"].to(dev) | td["hair_mask"].to(dev)) & ~mouth_mask
+            if hair_mask_iter:
+                keep = keep & ~td["hair_mask"].to(dev)
+            gt_white = torch.where(keep[None], gt, self.bg[:, None, None].expand_as(gt))
+            if self._patch_op is None:
+                self._patch_op = PatchLPIPS(self.lpips, gt.shape[-2], gt.shape[-1], *FACE_PATCH_RANGE)
+            loss = loss + FACE_LPIPS_WEIGHT * self._patch_op(pkg["render"], gt_white, lpips_p, td["lips_rect"].to(dev),
+                                                             self.bg)
         return loss, Ll1
+
+    def _lpips_arg(self):
+        return self._p_dev if isinstance(self._lpips_p, str) else self._lpips_p
 
     # ---- one step ---------------------------------------------------------------------------------------------
     def _forward_backward(self, frame: Frame, phase: FacePhase = C3_PHASE, fold_aux: bool = False):
@@ -442,9 +495,10 @@ class FaceTrainer:
         from .losses import defer_finalize
         # (backward follows at once and the loss value is read after the step: the loss block's scalar stage rides in
         # its backward launch -- unless the prior terms are ADDED to the value here, which needs it now)
-        with (nullcontext() if phase.priors else defer_finalize()):
+        lpips_p = self._lpips_arg()
+        with (nullcontext() if (phase.priors or lpips_p is not None) else defer_finalize()):
             loss, Ll1 = self.loss_fn(frame, pkg, warm=phase.warm, hair_mask_iter=phase.hair_mask_iter,
-                                     priors=phase.priors, prior_depth=phase.prior_depth)
+                                     priors=phase.priors, prior_depth=phase.prior_depth, lpips_p=lpips_p)
         from . import diff_gauss
         # fold_aux (only callers that run _stats_and_optimizers(pkg) next): the auxiliary image's share of the screen-space
         # gradient is added by the statistics kernel instead of by a launch of its own at the end of backward
@@ -484,9 +538,10 @@ class FaceTrainer:
         from .losses import defer_finalize
         # (backward follows at once and the loss value is read after the step: the loss block's scalar stage rides in
         # its backward launch -- unless the prior terms are ADDED to the value here, which needs it now)
-        with (nullcontext() if phase.priors else defer_finalize()):
+        lpips_p = self._lpips_arg()
+        with (nullcontext() if (phase.priors or lpips_p is not None) else defer_finalize()):
             loss, Ll1 = self.loss_fn(frame, pkg, warm=phase.warm, hair_mask_iter=phase.hair_mask_iter,
-                                     priors=phase.priors, prior_depth=phase.prior_depth)
+                                     priors=phase.priors, prior_depth=phase.prior_depth, lpips_p=lpips_p)
         cut = dict.get(pkg, "_cut")
         if not cut:
             raise RuntimeError("the three-segment step needs render_motion's fused path (align=True on the GPU)")
@@ -594,7 +649,7 @@ class FaceTrainer:
         if not keep_mode:
             self._graph_mode = None
 
-    def _recapture(self, frame: Frame, phase: FacePhase, min_capacity: int = 0):
+    def _recapture(self, frame: Frame, phase: FacePhase, min_capacity: int = 0, lpips: bool = False):
         """Capture the step of ``phase`` again WITHOUT running a single train step: graph mode is on (enable_graph was
         called once, its warm-up steps warmed every library and measured the instance counts) and only the parameter
         set (densify / prune / opacity reset) or the needed capacity changed since.  The capacity follows the Gaussian
@@ -605,9 +660,9 @@ class FaceTrainer:
         mode = self._graph_mode
         n = max(1, self.g.num_points)
         cap = max(int(mode["capacity"] * max(1.0, n / mode["capacity_n"])), int(min_capacity))
-        g = GraphedStep(self, frame, mode["headroom"], 0, mode["split"], phase, min_capacity=cap)
+        g = GraphedStep(self, frame, mode["headroom"], 0, mode["split"], phase, min_capacity=cap, lpips=lpips)
         mode["capacity"], mode["capacity_n"] = g.capacity, n
-        self._graph_cache[phase] = g
+        self._graph_cache[(phase, True) if lpips else phase] = g
         self.recaptures += 1
         self.recapture_seconds += time.perf_counter() - t0
         return g
@@ -628,6 +683,14 @@ class FaceTrainer:
     def step(self, frame: Frame):
         self.iteration += 1
         it = self.iteration
+        lp = self.lpips_on(it)
+        patch = None
+        if lp:
+            from .lpips import draw_face_patch
+            patch = draw_face_patch(self.rng)
+            if self._graph_mode is not None:
+                self._stage_p(patch)                # (travels with the learning rates; one graph serves every size)
+        self._lpips_p = patch
         self._set_learning_rates(it)
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         phase = self.phase_of(it)
@@ -640,9 +703,9 @@ class FaceTrainer:
         elif mode is not None:
             # one captured step per phase (FacePhase): the schedule alternates between a few of them (the hair
             # iterations toggle six times out of seven)
-            g = self._graph_cache.get(phase)
+            g = self._graph_cache.get((phase, True) if lp else phase)      # (the phase key gains the LPIPS flag)
             if g is None and mode["auto"]:
-                g = self._recapture(frame, phase)
+                g = self._recapture(frame, phase, lpips=lp)
             if g is None:
                 graphs.drop_plan(self._graph)          # a phase nobody captured (auto off): eager launches
             self._graph = g
@@ -664,6 +727,8 @@ class FaceTrainer:
             self._stats_and_optimizers(pkg, distributed, it, frame)
             self._zero_grad()
         self.last = dict(loss=loss.detach(), l1=Ll1.detach(), num_points=self.g.num_points, phase=phase)
+        if self.lpips is not None:
+            self.last["patch"] = patch
         return self.last
 
     # ---- state snapshot (benchmark windows start from the same state; in place, so captured graphs stay valid) ----
@@ -671,13 +736,18 @@ class FaceTrainer:
         return self.g.xyz_gradient_accum, self.g.denom, self.g.max_radii2D
 
     def snapshot(self):
-        return dict(iteration=self.iteration,
+        snap = dict(iteration=self.iteration,
                     **snapshot_state([p.data for p in self._all_params()], self.optimizers, self._stats()))
+        if self.lpips is not None:
+            snap["rng"] = self.rng.getstate()
+        return snap
 
     def restore(self, snap):
         """Copy a snapshot() back IN PLACE (restore_state); no densification in between."""
         restore_state(snap, [p.data for p in self._all_params()], self.optimizers, self._stats())
         self.iteration = snap["iteration"]
+        if "rng" in snap:
+            self.rng.setstate(snap["rng"])
 
     # ---- graph mode --------------------------------------------------------------------------------------------
     def enable_graph(self, example_frame: Frame, headroom: float = 1.4, warmup_steps: int = 3,
@@ -692,15 +762,16 @@ class FaceTrainer:
         ``auto_recapture`` step() then captures the step it needs again by itself, without warm-up steps and without
         touching the training state (_recapture); without it such a step launches eagerly."""
         self._graph = None
+        after = self.iteration + (0 if keep_state else max(1, warmup_steps) + 2) + 1
+        lp = self.lpips_on(after)
         if phase is None:
-            after = self.iteration + (0 if keep_state else max(1, warmup_steps) + 2) + 1
             phase = self.phase_of(after)                                       # the iteration right after capture
         snap = self.snapshot() if keep_state else None
         if self.densify and self.on_gpu:
             warm_density_control(self.device, self.g.max_sh_degree, self.opt)
         self._graph = GraphedStep(self, example_frame, headroom, max(1, warmup_steps), split_for_allreduce, phase,
-                                  min_capacity=min_capacity, restore=snap)
-        self._graph_cache[phase] = self._graph
+                                  min_capacity=min_capacity, restore=snap, lpips=lp)
+        self._graph_cache[(phase, True) if lp else phase] = self._graph
         prev = self._graph_mode
         self._graph_mode = dict(headroom=headroom, split=self._graph.split, auto=bool(auto_recapture),
                                 capacity=max(self._graph.capacity, prev["capacity"] if prev else 0),
@@ -711,10 +782,19 @@ class FaceTrainer:
 class GraphedStep(graphs.CapturedStep):
     def __init__(self, trainer: FaceTrainer, example: Frame, headroom: float, warmup_steps: int,
                  split_for_allreduce: Optional[bool] = None, phase: FacePhase = C3_PHASE, min_capacity: int = 0,
-                 restore=None):
+                 restore=None, lpips: bool = False):
         """``warmup_steps`` > 0: the cold path (eager steps measure the instance count and warm every library; with
         ``restore`` = a trainer.snapshot() the training state is put back afterwards).  0: the warm path of
         FaceTrainer._recapture -- nothing runs, ``min_capacity`` is the capacity."""
+        # (``lpips``: the step carries the late phase's LPIPS term and reads its patch size from the trainer's device
+        # scalar; the trainer's field says so while the step is measured, warmed and captured, and is put back afterwards)
+        prev, trainer._lpips_p = trainer._lpips_p, ("device" if lpips else None)
+        try:
+            self._build(trainer, example, headroom, warmup_steps, split_for_allreduce, phase, min_capacity, restore, lpips)
+        finally:
+            trainer._lpips_p = prev
+
+    def _build(self, trainer, example, headroom, warmup_steps, split_for_allreduce, phase, min_capacity, restore, lpips):
         self.phase = phase
         t = self.trainer = trainer
         dev = t.device
@@ -739,6 +819,9 @@ class GraphedStep(graphs.CapturedStep):
 
         def pre():
             t.iteration += 1
+            if lpips:
+                from .lpips import draw_face_patch
+                t._stage_p(draw_face_patch(t.rng))
             t._set_learning_rates(t.iteration)
 
         def eager_step():

@@ -3,8 +3,10 @@
 Counterparts of /root/reference/train_mouth.py:106-293 and /root/reference/train_fuse_con.py:75-245 restricted to
 the hot path (render -> loss -> backward -> statistics / density control -> optimizers).  Same kernels as the face
 branch behind other callers: ``render_motion_mouth_con`` / ``render_motion`` of
-instag_amd/renderer.py, the fused L1+SSIM operator, the single-launch Adam.  Frame selection by AU25, LPIPS,
-logging and checkpoint cadence are the reference's data pipeline / control plane and stay out.
+instag_amd/renderer.py, the fused L1+SSIM operator, the single-launch Adam.  Frame selection by AU25, logging and
+checkpoint cadence are the reference's data pipeline / control plane and stay out.  The fuse stage's LPIPS patch term
+(train_fuse_con.py:186-193) is opt-in: ``FuseTrainer(..., lpips=LPIPSWeights)``; the mouth branch's exists only under
+``mode_long``, which the trainers do not carry.
 """
 from __future__ import annotations
 
@@ -284,7 +286,9 @@ class FuseTrainer:
     FROZEN_MOUTH = ("xyz", "opacity", "scaling", "rotation")
 
     def __init__(self, gaussians: GaussianModel, motion_net, gaussians_mouth: GaussianModel, motion_net_mouth,
-                 background, opt=OptimizationParams, seed: int = 0):
+                 background, opt=OptimizationParams, seed: int = 0, lpips=None):
+        """``lpips`` (instag_amd.lpips.LPIPSWeights): from iteration > iterations // 2 the step adds
+        0.05 * PatchLPIPS(image, gt_image, p), p = 2 * randint(16, 21) (train_fuse_con.py:186-193)."""
         self.g, self.motion_net = gaussians, motion_net
         self.g_mouth, self.motion_net_mouth = gaussians_mouth, motion_net_mouth
         self.bg, self.opt = background, opt
@@ -304,45 +308,107 @@ class FuseTrainer:
         self._graph = None
         self._graph_key = None
         self.last = {}
+        self.lpips = lpips
+        self.rng = random.Random(seed)                                       # patch size, train_fuse_con.py:192
+        self._patch_op = None
+        # the patch size of a captured step lives on the device and rides on the learning-rate upload (MouthTrainer._k_dev)
+        self._p_own = None
+        if lpips is not None and self.on_gpu:
+            self._p_own = torch.full((1,), 32, dtype=torch.int64, device=self.device)
+            if self.optimizers.combined is not None:
+                self.optimizers.combined.reserve_extra_i64(1)
 
-    def forward(self, frame: Frame):
+    @property
+    def _p_dev(self):
+        combined = self.optimizers.combined
+        view = combined.extra_i64() if (combined is not None and self.lpips is not None) else None
+        return view if view is not None else self._p_own
+
+    def _stage_p(self, p):
+        """Call in FRONT of _set_learning_rates (whose upload carries the value)."""
+        combined = self.optimizers.combined
+        if combined is not None and combined.extra_i64() is not None:
+            combined.set_extra_i64([p])
+        else:
+            self._p_own.fill_(p)
+
+    def _lpips_on(self, it) -> bool:
+        from .lpips import fuse_lpips_on
+        return self.lpips is not None and fuse_lpips_on(it, self.opt)
+
+    def _draw_patch(self, it):
+        """The iteration's patch size (None before the term starts; the generator is drawn from only when it is on)."""
+        from .lpips import draw_fuse_patch
+        return draw_fuse_patch(self.rng) if self._lpips_on(it) else None
+
+    def forward(self, frame: Frame, p=None):
+        """``p``: the LPIPS patch size of this iteration (an int, or the device scalar of a captured step); None = off."""
         from .renderer import render_fuse
         dev = self.device
         scene_bg = frame.talking_dict.get("background")
         out = render_fuse(frame, self.g, self.motion_net, self.g_mouth, self.motion_net_mouth, None, self.bg,
                           scene_background=None if scene_bg is None else scene_bg.to(dev))
-        loss, Ll1 = fuse_loss(out["image"], frame.original_image.to(dev), self.opt.lambda_dssim)
+        gt = frame.original_image.to(dev)
+        loss, Ll1 = fuse_loss(out["image"], gt, self.opt.lambda_dssim)
+        if p is not None:
+            from .lpips import FUSE_LPIPS_WEIGHT, FUSE_PATCH_RANGE, PatchLPIPS
+            if self._patch_op is None:
+                self._patch_op = PatchLPIPS(self.lpips, gt.shape[-2], gt.shape[-1], *FUSE_PATCH_RANGE)
+            loss = loss + FUSE_LPIPS_WEIGHT * self._patch_op(out["image"], gt, p)
         return out, loss, Ll1
 
     def _set_learning_rates(self, it):
         self.g.update_learning_rate(it)           # train_fuse_con.py:85 (the mouth model keeps its initial rates)
         self.optimizers.push_lrs()
 
-    def _body(self, frame: Frame):
+    def _body(self, frame: Frame, p=None):
+        from contextlib import nullcontext
         from .losses import defer_finalize
-        with defer_finalize():          # (backward follows at once; the loss value is read after the step)
-            out, loss, Ll1 = self.forward(frame)
+        # (backward follows at once; the loss value is read after the step -- unless the LPIPS term is ADDED to it here)
+        with (defer_finalize() if p is None else nullcontext()):
+            out, loss, Ll1 = self.forward(frame, p)
         backward(loss, self.device)
         self.optimizers.step()
         self.optimizers.zero_grad()
         return loss, Ll1, out["image"], out
 
     def enable_graph(self, example: Frame, headroom: float = 1.5, warmup_steps: int = 2):
-        """Capture the whole step (the stage has a single phase and no density control: densify_until_iter = 0)."""
+        """Capture the whole step (the stage has no density control: densify_until_iter = 0; with ``lpips`` it has two
+        phases, before and after iterations // 2 -- the graph holds the one of the iterations right after the capture,
+        and one graph serves every patch size; warm-up steps that would straddle the boundary are preceded by eager
+        steps up to it).  step() drops a graph of the first half at iterations // 2 + 1 and launches eagerly from
+        there: call enable_graph again once ``_lpips_on(iteration + 1)`` to replay the second half (capturing costs
+        warm-up steps, which are train steps, so step() does not do it behind the caller's back)."""
         _drop_graph(self)
+        total = max(1, warmup_steps) + 2
+        on = self._lpips_on(self.iteration + total + 1)
+        # the warm-up steps run the captured body: they must all lie on the capture's side of iterations // 2
+        while self._lpips_on(self.iteration + 1) != on:
+            self.step(example)
+            on = self._lpips_on(self.iteration + total + 1)
 
         def pre():
             self.iteration += 1
+            if on:
+                from .lpips import draw_fuse_patch
+                self._stage_p(draw_fuse_patch(self.rng))
             self._set_learning_rates(self.iteration)
-        self._graph = graphs.GraphedStage(self._body, example, self.device,
+
+        def body(frame):
+            return self._body(frame, self._p_dev if on else None)
+        self._graph = graphs.GraphedStage(body, example, self.device,
                                           lambda counts: graphs.stage_capacities(counts, headroom), warmup_steps, pre)
+        self._graph_key = on
         return self._graph
 
     def step(self, frame: Frame):
         self.iteration += 1
         it = self.iteration
+        p = self._draw_patch(it)
+        if self._graph is not None and p is not None:
+            self._stage_p(p)                    # (travels with the learning rates)
         self._set_learning_rates(it)
-        if self._graph is not None and it >= self.opt.iterations:
+        if self._graph is not None and (it >= self.opt.iterations or self._graph_key != (p is not None)):
             _drop_graph(self)
         if self._graph is not None:
             loss, Ll1, image = self._graph.replay(frame)[:3]
@@ -350,11 +416,13 @@ class FuseTrainer:
                 _drop_graph(self)
         elif it < self.opt.iterations:
             graphs.begin_eager_step()
-            loss, Ll1, image = self._body(frame)[:3]
+            loss, Ll1, image = self._body(frame, p)[:3]
         else:
-            out, loss, Ll1 = self.forward(frame)         # last iteration: no optimizer step (:242)
+            out, loss, Ll1 = self.forward(frame, p)      # last iteration: no optimizer step (:242)
             backward(loss, self.device)
             self.optimizers.zero_grad()
             image = out["image"]
         self.last = dict(loss=loss.detach(), l1=Ll1.detach(), image=image.detach())
+        if self.lpips is not None:
+            self.last["patch"] = p
         return self.last
