@@ -637,6 +637,14 @@ int instag_adam_ema_step(const void* tensors, const void* host_grads, int32_t n_
  *    pointers to the other identities' heads [N,11] (columns 0..2 are read), n_others <=
  *    instag_pretrain_deform_max_others().  backward: g_reg (device scalar, may be NULL) = upstream gradient of the
  *    partial sums; no gradient for the other heads.
+ *  pretrain_mouth_deform: render_motion_mouth_con(personalized=True, align=False) of the mouth stage
+ *    (pretrain_mouth.py:34-358) from the mouth field's heads h [N,7], hs [N,1] and the PMF's head h_p [N,7]:
+ *    means3D = xyz + (((h[:, :3] * (sx, sy, sz)) * sigmoid(hs)) * 2 + h_p[:, :3] * 1e-2), scales = softplus(scaling),
+ *    rotations = normalize(rotation), opacity = sigmoid(opacity); reg_partials (may be NULL;
+ *    instag_pretrain_mouth_deform_num_partials(N) floats) = per-workgroup partial sums of 1e-5 * mean|.| of that
+ *    combined displacement, of h[:, 3:7], of h_p[:, :3] * 1e-2 and of h_p[:, 3:7], and of the contrast term
+ *    mean_n relu(sum_c (h_q[c]*1e-2) * (h_p[c]*1e-2)) against one partner's PMF head h_q [N,7] (NULL: no contrast).
+ *    backward: one launch; g_reg (device scalar, may be NULL) = upstream gradient of the partial sums; no gradient for h_q.
  *  window_mean: out[0:n_prev] = prev, out[n_prev] = w * x[ch, r0:r1, c0:c1].mean(), rect = device int32 (r0,r1,c0,c1);
  *    backward writes dx [C,H,W] = g[0] * w / count inside the window, 0 elsewhere.
  * ------------------------------------------------------------------------------------------ */
@@ -652,6 +660,18 @@ int instag_pretrain_deform_backward(const float* scaling, const float* rotation,
                                     const float* g_opac, const float* g_reg, float* d_xyz, float* d_scaling,
                                     float* d_rotation, float* d_opacity, float* d_hu, float* d_hp, int32_t N,
                                     instag_stream_t stream);
+int instag_pretrain_mouth_deform_num_partials(int32_t N);
+int instag_pretrain_mouth_deform_forward(const float* xyz, const float* scaling, const float* rotation,
+                                         const float* opacity, const float* h, const float* hs, const float* h_p,
+                                         const float* h_q, float sx, float sy, float sz, float* means3D, float* scales,
+                                         float* rotations, float* opac, float* reg_partials, int32_t N,
+                                         instag_stream_t stream);
+int instag_pretrain_mouth_deform_backward(const float* scaling, const float* rotation, const float* opacity,
+                                          const float* h, const float* hs, const float* h_p, const float* h_q, float sx,
+                                          float sy, float sz, const float* g_means, const float* g_scales,
+                                          const float* g_rots, const float* g_opac, const float* g_reg, float* d_xyz,
+                                          float* d_scaling, float* d_rotation, float* d_opacity, float* d_h, float* d_hs,
+                                          float* d_hp, int32_t N, instag_stream_t stream);
 int instag_window_mean_forward(const float* x, int32_t C, int32_t H, int32_t W, int32_t ch, const int32_t* rect,
                                float w, const float* prev, int32_t n_prev, float* out, instag_stream_t stream);
 int instag_window_mean_backward(int32_t C, int32_t H, int32_t W, int32_t ch, const int32_t* rect, float w,

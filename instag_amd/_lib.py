@@ -305,6 +305,9 @@ _PROTOS = {
     "instag_pretrain_deform_num_partials": (C.c_int, [i32]),
     "instag_pretrain_deform_forward": (C.c_int, [vp] * 7 + [i32] + [vp] * 5 + [i32, vp]),
     "instag_pretrain_deform_backward": (C.c_int, [vp] * 6 + [i32] + [vp] * 11 + [i32, vp]),
+    "instag_pretrain_mouth_deform_num_partials": (C.c_int, [i32]),
+    "instag_pretrain_mouth_deform_forward": (C.c_int, [vp] * 8 + [f32] * 3 + [vp] * 5 + [i32, vp]),
+    "instag_pretrain_mouth_deform_backward": (C.c_int, [vp] * 7 + [f32] * 3 + [vp] * 12 + [i32, vp]),
     "instag_window_mean_forward": (C.c_int, [vp, i32, i32, i32, i32, vp, f32, vp, i32, vp, vp]),
     "instag_window_mean_backward": (C.c_int, [i32, i32, i32, i32, vp, f32, vp, vp, vp]),
     "instag_lpips_workspace_bytes": (sz, [i32] * 5),

@@ -11,6 +11,15 @@
 //                     sum_j mean_n relu(sum_c d_xyz_j * d_xyz_p) against the other identities' PMF heads h_j.
 //                   One forward and one backward launch instead of ~20 elementwise launches each way plus the
 //                   regulariser and contrast chains.
+//  pretrain_mouth_deform  the mouth stage's counterpart (pretrain_mouth.py:34-358): render_motion_mouth_con(
+//                   personalized=True, align=False) (gaussian_renderer/__init__.py:379-406) with the per-Gaussian terms of
+//                   pretrain_mouth.py:231-276.  h [N,7], hs [N,1] = the mouth field's heads, h_p [N,7] = the PMF's head:
+//                     d_xyz = ((h[:, :3] * (sx, sy, sz)) * sigmoid(hs)) * 2 + h_p[:, :3]*1e-2   (the reference adds the
+//                     PMF's displacement IN PLACE, :387, so this combined value is what motion['d_xyz'] holds afterwards),
+//                     means3D = xyz + d_xyz, scales = softplus(scaling), rotations = normalize(rotation) (d_rot is never
+//                     applied), opacity = sigmoid(opacity_raw);
+//                     1e-5 * mean|.| of the combined d_xyz, of h[:, 3:7], of h_p[:, :3]*1e-2 and of h_p[:, 3:7], and the
+//                     contrast mean_n relu(sum_c (h_q[c]*1e-2) * (h_p[c]*1e-2)) against ONE partner's PMF head h_q.
 //  window_mean      w * x[ch, r0:r1, c0:c1].mean() (the personalised attention map's lips term) appended to a row of
 //                   partial sums, so the loss kernel reads all of the step's extra terms as one array.
 #include <cstring>
@@ -181,6 +190,139 @@ pretrain_deform_backward_kernel(int N, const float* __restrict__ scaling, const 
   }
 }
 
+// ---- mouth stage --------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(PB)
+pretrain_mouth_deform_forward_kernel(int N, const float* __restrict__ xyz, const float* __restrict__ scaling,
+                                     const float* __restrict__ rotation, const float* __restrict__ opacity,
+                                     const float* __restrict__ h /*[N,7]*/, const float* __restrict__ hs /*[N,1]*/,
+                                     const float* __restrict__ hp /*[N,7]*/, const float* __restrict__ hq /*[N,7] or NULL*/,
+                                     float sx, float sy, float sz, float* __restrict__ means3D,
+                                     float* __restrict__ scales, float* __restrict__ rots, float* __restrict__ opac,
+                                     float* __restrict__ reg_partials) {
+  __shared__ float s_red[PB / 64];
+  const int r = blockIdx.x * PB + threadIdx.x;
+  float reg = 0.f;
+  if (r < N) {
+    float u[7], p[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) { u[k] = h[(size_t)r * 7 + k]; p[k] = hp[(size_t)r * 7 + k]; }
+    const float sg = sigmoid_pf(hs[r]);
+    const float xs[3] = {sx, sy, sz};
+    float dx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      dx[k] = ((u[k] * xs[k]) * sg) * 2.0f + p[k] * 1e-2f;          // (no contraction: -ffp-contract=off)
+      means3D[3 * r + k] = xyz[3 * r + k] + dx[k];
+      scales[3 * r + k] = softplus_pf(scaling[3 * r + k]);
+    }
+    float q[4], n2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { q[k] = rotation[4 * r + k]; n2 += q[k] * q[k]; }
+    const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rots[4 * r + k] = q[k] * inv;
+    opac[r] = sigmoid_pf(opacity[r]);
+    if (reg_partials) {
+      const float w3 = 1e-5f / (3.f * N), w4 = 1e-5f / (4.f * N);
+      const float umf = w3 * (fabsf(dx[0]) + fabsf(dx[1]) + fabsf(dx[2]))
+          + w4 * (fabsf(u[3]) + fabsf(u[4]) + fabsf(u[5]) + fabsf(u[6]));
+      const float pmf = w3 * (fabsf(p[0] * 1e-2f) + fabsf(p[1] * 1e-2f) + fabsf(p[2] * 1e-2f))
+          + w4 * (fabsf(p[3]) + fabsf(p[4]) + fabsf(p[5]) + fabsf(p[6]));
+      const float con = hq ? fmaxf(contrast_dot(hq + (size_t)r * 7, p), 0.f) : 0.f;
+      reg = umf + pmf + con / (float)N;
+    }
+  }
+  if (reg_partials) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) reg += __shfl_xor(reg, o);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = reg;
+    __syncthreads();
+    if (threadIdx.x == 0) reg_partials[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+  }
+}
+
+__global__ void __launch_bounds__(PB)
+pretrain_mouth_deform_backward_kernel(int N, const float* __restrict__ scaling, const float* __restrict__ rotation,
+                                      const float* __restrict__ opacity, const float* __restrict__ h,
+                                      const float* __restrict__ hs, const float* __restrict__ hp,
+                                      const float* __restrict__ hq, float sx, float sy, float sz,
+                                      const float* __restrict__ g_means, const float* __restrict__ g_scales,
+                                      const float* __restrict__ g_rots, const float* __restrict__ g_opac,
+                                      const float* __restrict__ g_reg, float* __restrict__ d_xyz,
+                                      float* __restrict__ d_scaling, float* __restrict__ d_rotation,
+                                      float* __restrict__ d_opacity, float* __restrict__ d_h /*[N,7]*/,
+                                      float* __restrict__ d_hs /*[N,1]*/, float* __restrict__ d_hp /*[N,7]*/) {
+  const int r = blockIdx.x * PB + threadIdx.x;
+  if (r >= N) return;
+  float u[7], p[7], du[7], dp[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    u[k] = h[(size_t)r * 7 + k]; p[k] = hp[(size_t)r * 7 + k];
+    du[k] = 0.f; dp[k] = 0.f;
+  }
+  const float sg = sigmoid_pf(hs[r]);
+  const float xs[3] = {sx, sy, sz};
+  const bool with_reg = g_reg != nullptr;
+  const float go = with_reg ? g_reg[0] : 0.f;
+  const float w3 = go * 1e-5f / (3.f * N), w4 = go * 1e-5f / (4.f * N);
+  float dgate = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float gm = g_means ? g_means[3 * r + k] : 0.f;
+    d_xyz[3 * r + k] = gm;
+    // the gradient of the COMBINED displacement: the render's, and |.| of the first regulariser, into both fields
+    float G = gm;
+    if (with_reg) {
+      const float dxk = ((u[k] * xs[k]) * sg) * 2.0f + p[k] * 1e-2f;
+      G += w3 * sgn_f(dxk);
+    }
+    du[k] = G * 2.0f * sg * xs[k];
+    dgate += G * 2.0f * (u[k] * xs[k]);
+    dp[k] = G * 1e-2f;
+    if (with_reg) dp[k] += w3 * sgn_f(p[k] * 1e-2f) * 1e-2f;
+    const float gs = g_scales ? g_scales[3 * r + k] : 0.f;
+    d_scaling[3 * r + k] = gs * sigmoid_pf(scaling[3 * r + k]);           // d softplus = sigmoid
+  }
+  if (with_reg) {
+#pragma unroll
+    for (int k = 3; k < 7; ++k) {          // d_rot is regularised but never applied
+      du[k] = w4 * sgn_f(u[k]);
+      dp[k] = w4 * sgn_f(p[k]);
+    }
+    if (hq) {
+      // contrast: the reference zeroes the entries < 0 in place, so the gradient passes where c >= 0
+      const float* q7 = hq + (size_t)r * 7;
+      if (contrast_dot(q7, p) >= 0.f) {
+        const float wc = go / (float)N;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dp[k] += wc * (q7[k] * 1e-2f) * 1e-2f;
+      }
+    }
+  }
+  float q[4], n2 = 0.f, dot = 0.f, gr[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    q[k] = rotation[4 * r + k];
+    n2 += q[k] * q[k];
+    gr[k] = g_rots ? g_rots[4 * r + k] : 0.f;
+  }
+  const float nrm = sqrtf(n2);
+  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) dot += gr[k] * q[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    d_rotation[4 * r + k] = nrm > 1e-12f ? (gr[k] - q[k] * inv * dot * inv) * inv : gr[k] * inv;
+  const float so = sigmoid_pf(opacity[r]);
+  d_opacity[r] = (g_opac ? g_opac[r] : 0.f) * so * (1.f - so);
+  d_hs[r] = dgate * sg * (1.f - sg);
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    d_h[(size_t)r * 7 + k] = du[k];
+    d_hp[(size_t)r * 7 + k] = dp[k];
+  }
+}
+
 // One workgroup: copies the n_prev partial sums in front and appends w * mean of the window as the last entry.
 __global__ void __launch_bounds__(PB)
 window_mean_forward_kernel(const float* __restrict__ x, int H, int W, int ch, const int32_t* __restrict__ rect,
@@ -266,6 +408,40 @@ int instag_pretrain_deform_backward(const float* scaling, const float* rotation,
   pretrain_deform_backward_kernel<<<(N + PB - 1) / PB, PB, 0, (hipStream_t)stream>>>(
       N, scaling, rotation, opacity, h_u, h_p, oh, n_others, g_means, g_scales, g_rots, g_opac, g_reg, d_xyz,
       d_scaling, d_rotation, d_opacity, d_hu, d_hp);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+int instag_pretrain_mouth_deform_num_partials(int32_t N) { return N > 0 ? (N + PB - 1) / PB : 0; }
+
+int instag_pretrain_mouth_deform_forward(const float* xyz, const float* scaling, const float* rotation,
+                                         const float* opacity, const float* h, const float* hs, const float* h_p,
+                                         const float* h_q, float sx, float sy, float sz, float* means3D, float* scales,
+                                         float* rotations, float* opac, float* reg_partials, int32_t N,
+                                         instag_stream_t stream) {
+  INSTAG_REQUIRE(xyz && scaling && rotation && opacity && h && hs && h_p && means3D && scales && rotations && opac,
+                 "pretrain_mouth_deform_forward: NULL tensor");
+  INSTAG_REQUIRE(N >= 0, "pretrain_mouth_deform_forward: N >= 0");
+  if (N == 0) return INSTAG_OK;
+  pretrain_mouth_deform_forward_kernel<<<(N + PB - 1) / PB, PB, 0, (hipStream_t)stream>>>(
+      N, xyz, scaling, rotation, opacity, h, hs, h_p, h_q, sx, sy, sz, means3D, scales, rotations, opac, reg_partials);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+int instag_pretrain_mouth_deform_backward(const float* scaling, const float* rotation, const float* opacity,
+                                          const float* h, const float* hs, const float* h_p, const float* h_q, float sx,
+                                          float sy, float sz, const float* g_means, const float* g_scales,
+                                          const float* g_rots, const float* g_opac, const float* g_reg, float* d_xyz,
+                                          float* d_scaling, float* d_rotation, float* d_opacity, float* d_h, float* d_hs,
+                                          float* d_hp, int32_t N, instag_stream_t stream) {
+  INSTAG_REQUIRE(scaling && rotation && opacity && h && hs && h_p && d_xyz && d_scaling && d_rotation && d_opacity &&
+                 d_h && d_hs && d_hp, "pretrain_mouth_deform_backward: NULL tensor");
+  INSTAG_REQUIRE(N >= 0, "pretrain_mouth_deform_backward: N >= 0");
+  if (N == 0) return INSTAG_OK;
+  pretrain_mouth_deform_backward_kernel<<<(N + PB - 1) / PB, PB, 0, (hipStream_t)stream>>>(
+      N, scaling, rotation, opacity, h, hs, h_p, h_q, sx, sy, sz, g_means, g_scales, g_rots, g_opac, g_reg, d_xyz,
+      d_scaling, d_rotation, d_opacity, d_h, d_hs, d_hp);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }

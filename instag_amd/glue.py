@@ -4,6 +4,7 @@ composition and the loss block.  Each replaces a chain of eager elementwise ops 
   deform_activate  gaussian_renderer/__init__.py:200-235 (render_motion, personalized=False, align=True)
   motion_l1_reg    train_face.py:510-514
   pretrain_deform  render_motion(personalized=True, align=False) + the per-Gaussian loss terms of pretrain_face.py
+  pretrain_mouth_deform  render_motion_mouth_con(personalized=True, align=False) + those of pretrain_mouth.py
 """
 from __future__ import annotations
 
@@ -316,6 +317,74 @@ def pretrain_deform(xyz, scaling, rotation, opacity, h_u, h_p, others=(), with_r
         raise ValueError(f"pretrain_deform: at most {L.instag_pretrain_deform_max_others()} other identities")
     others = [t.detach() for t in others]
     return _PretrainDeform.apply(xyz, scaling, rotation, opacity, h_u, h_p, bool(with_reg), *others)
+
+
+class _PretrainMouthDeform(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, scaling, rotation, opacity, h, hs, h_p, h_q, with_reg, xyz_scale):
+        L = _lib.lib()
+        ctx.set_materialize_grads(False)
+        xyz, scaling, rotation, opacity, h, hs, h_p = (_c(t) for t in (xyz, scaling, rotation, opacity, h, hs, h_p))
+        h_q = None if h_q is None else _c(h_q)
+        N, dev = xyz.shape[0], xyz.device
+        means3D = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        rots = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        reg = torch.empty(L.instag_pretrain_mouth_deform_num_partials(N), dtype=torch.float32, device=dev) \
+            if with_reg else None
+        sx, sy, sz = xyz_scale
+        check(L.instag_pretrain_mouth_deform_forward(ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(hs),
+                                                     ptr(h_p), ptr(h_q), sx, sy, sz, ptr(means3D), ptr(scales), ptr(rots),
+                                                     ptr(opac), ptr(reg), N, _lib.current_stream()),
+              "pretrain_mouth_deform_forward")
+        ctx.save_for_backward(scaling, rotation, opacity, h, hs, h_p, *([h_q] if h_q is not None else []))
+        ctx.xyz_scale = (sx, sy, sz)
+        if reg is None:
+            return means3D, scales, rots, opac
+        return means3D, scales, rots, opac, reg
+
+    @staticmethod
+    def backward(ctx, g_means, g_scales, g_rots, g_opac, g_reg=None):
+        L = _lib.lib()
+        scaling, rotation, opacity, h, hs, h_p, *rest = ctx.saved_tensors
+        h_q = rest[0] if rest else None
+        N, dev = scaling.shape[0], scaling.device
+        gs = [None if g is None else _c(g) for g in (g_means, g_scales, g_rots, g_opac)]
+        # every partial sum feeds the same scalar: its upstream gradient is one number
+        g_reg1 = None if g_reg is None else g_reg.reshape(-1)[:1].contiguous().float()
+        d_xyz = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        d_scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        d_rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        d_op = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        d_h = torch.empty(N, 7, dtype=torch.float32, device=dev)
+        d_hs = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        d_hp = torch.empty(N, 7, dtype=torch.float32, device=dev)
+        sx, sy, sz = ctx.xyz_scale
+        check(L.instag_pretrain_mouth_deform_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(hs), ptr(h_p),
+                                                      ptr(h_q), sx, sy, sz, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]),
+                                                      ptr(g_reg1), ptr(d_xyz), ptr(d_scaling), ptr(d_rot), ptr(d_op),
+                                                      ptr(d_h), ptr(d_hs), ptr(d_hp), N, _lib.current_stream()),
+              "pretrain_mouth_deform_backward")
+        return d_xyz, d_scaling, d_rot, d_op, d_h, d_hs, d_hp, None, None, None
+
+
+def pretrain_mouth_deform(xyz, scaling, rotation, opacity, h, hs, h_p, h_q=None, with_reg=True,
+                          xyz_scale=(1e-2 / 5, 1e-2, 1e-2 / 5)):
+    """means3D, scales, rotations, opacity of render_motion_mouth_con(personalized=True, align=False) from the mouth
+    field's heads h [N,7], hs [N,1] and the PMF's head h_p [N,7] (csrc/pretrain.hip).  ``with_reg``: a fifth output holds
+    per-workgroup partial sums of the mouth pretraining step's per-Gaussian loss terms (pretrain_mouth.py:231-276) -- the
+    1e-5-weighted mean-|.| of the mouth field's d_xyz AFTER the reference's in-place addition of the PMF's displacement,
+    of its d_rot, of the PMF's d_xyz and d_rot, and the contrast against ``h_q``, the partner identity's PMF head [N,7]
+    evaluated without gradient (None: no contrast).  Feed it to ``losses.mouth_loss_fused(extra=...)``."""
+    N = xyz.shape[0]
+    if not (tuple(h.shape) == (N, 7) and hs.numel() == N and tuple(h_p.shape) == (N, 7)
+            and (h_q is None or tuple(h_q.shape) == (N, 7))
+            and tuple(scaling.shape) == (N, 3) and tuple(rotation.shape) == (N, 4) and opacity.numel() == N):
+        raise ValueError("pretrain_mouth_deform: heads [N,7], hs [N,1] and the Gaussians' tensors must share N")
+    h_q = None if h_q is None else h_q.detach()
+    return _PretrainMouthDeform.apply(xyz, scaling, rotation, opacity, h, hs, h_p, h_q, bool(with_reg),
+                                      tuple(float(v) for v in xyz_scale))
 
 
 class _WindowMeanAppend(torch.autograd.Function):

@@ -425,10 +425,21 @@ def _jaw_feature(h, column, scale, k):
 
 def render_motion_mouth_con(viewpoint_camera, pc, motion_net, pc_face, motion_net_face, pipe=None, bg_color=None,
                             scaling_modifier=1.0, frame_idx=None, return_attn=False, personalized=False, align=False,
-                            k=10, inference=False):
+                            k=10, inference=False, pretrain_other=None, pretrain_reg=None):
     """Mouth branch (gaussian_renderer/__init__.py:302-435): the mouth field is conditioned on a 3-element jaw
     movement feature derived (without gradient) from the k-th largest / smallest vertical displacement the FACE
-    field predicts for the face Gaussians with a neutral expression."""
+    field predicts for the face Gaussians with a neutral expression.
+    ``pretrain_reg`` (extension, personalized=True and align=False on the device only; None = off): the deformation
+    runs in the mouth pretraining operator (glue.pretrain_mouth_deform), which adds the personalised displacement to
+    the mouth field's as the reference does IN PLACE (:387); True also returns ``motion_reg`` = partial sums of the
+    per-Gaussian loss terms of pretrain_mouth.py:231-276, False returns ``motion_reg`` = None.  ``pretrain_other``: the
+    contrast partner's PMF head output [N,7] (None: no contrast term)."""
+    pretrain = pretrain_reg is not None or pretrain_other is not None
+    if pretrain and not (personalized and not align and not inference and pc.get_xyz.is_cuda):
+        raise RuntimeError("pretrain_other / pretrain_reg: the mouth pretraining deform operator needs "
+                           "personalized=True, align=False, inference=False and the GPU")
+    if pretrain_other is not None and not pretrain_reg:
+        raise RuntimeError("pretrain_other: the contrast term is part of the partial sums (pretrain_reg=True)")
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
                                               getattr(pipe, "debug", False)))
@@ -504,7 +515,22 @@ def render_motion_mouth_con(viewpoint_camera, pc, motion_net, pc_face, motion_ne
         xyz_route = carrier.pop("xyz", xyz_route)     # (align without the fused shift encodes xyz + p_xyz, not xyz)
     carrier.pop("shift", None)
     h_raw, hs_raw = dict.get(motion_preds, "_h"), dict.get(motion_preds, "_hs")
-    if (not personalized and torch.is_tensor(h_raw) and torch.is_tensor(hs_raw) and h_raw.is_cuda
+    motion_reg = None
+    if pretrain:
+        h_p = p_motion_preds.get("_h")
+        if not (torch.is_tensor(h_raw) and torch.is_tensor(hs_raw) and h_raw.shape[-1] == 7 and torch.is_tensor(h_p)
+                and h_p.shape[-1] == 7):
+            raise RuntimeError("pretrain_other / pretrain_reg: both fields' raw 7-column heads are needed")
+        from .glue import pretrain_mouth_deform
+        scale = getattr(motion_net, "XYZ_SCALE", (1e-2 / 5, 1e-2, 1e-2 / 5))
+        outs_d = pretrain_mouth_deform(xyz_route, pc._scaling, pc._rotation, pc._opacity, h_raw, hs_raw, h_p,
+                                       pretrain_other, with_reg=bool(pretrain_reg), xyz_scale=scale)
+        means3D, scales, rotations, opacity = outs_d[:4]
+        motion_reg = outs_d[4] if pretrain_reg else None
+        # (the reference's in-place addition to the returned dictionary's entry, :387, rebuilt on access)
+        motion_preds["d_xyz"] = lambda: ((h_raw[..., :3] * h_raw.new_tensor(scale)) * torch.sigmoid(hs_raw) * 2
+                                         + h_p[..., :3] * 1e-2)
+    elif (not personalized and torch.is_tensor(h_raw) and torch.is_tensor(hs_raw) and h_raw.is_cuda
             and h_raw.shape[-1] == 7):
         # gated displacement + softplus / normalize / sigmoid in one HIP kernel per pass (instag_amd/glue.py)
         from .glue import mouth_activate
@@ -527,7 +553,8 @@ def render_motion_mouth_con(viewpoint_camera, pc, motion_net, pc_face, motion_ne
     return LazyOutputs({"render": image, "viewspace_points": screenspace_points,
                         "visibility_filter": lambda: radii > 0,          # built on first access
                         "depth": depth, "alpha": alpha, "radii": radii, "motion": motion_preds,
-                        "p_motion": p_motion_preds if personalized or align else None})
+                        "p_motion": p_motion_preds if personalized or align else None,
+                        **({"motion_reg": motion_reg} if pretrain else {})})
 
 
 def render_fuse(viewpoint_camera, pc, motion_net, pc_mouth, motion_net_mouth, pipe=None, bg_color=None,
