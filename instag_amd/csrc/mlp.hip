@@ -720,10 +720,7 @@ __device__ __forceinline__ void weight_grad_body(const float* __restrict__ dZ, c
   for (int j = 0; j < MYT; ++j)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-#ifndef INSTAG_WG_UNROLL
-#define INSTAG_WG_UNROLL 6
-#endif
-  constexpr int UNROLL = INSTAG_WG_UNROLL;             // 2 * UNROLL rows of both operands in flight per wave
+  constexpr int UNROLL = 6;             // 2 * UNROLL rows of both operands in flight per wave
   for (long r0 = w0; r0 < w1; r0 += 2 * UNROLL) {
     float a[UNROLL][MYT], bb[UNROLL][MYT];
 #pragma unroll
@@ -798,10 +795,8 @@ struct WgBatch { WgJob j[WG_MAX_JOBS]; WgVirt virt; };
 // (same-box A/B of the C3 step, round 3: 3 waves per SIMD x 16 rows in flight 0.9000 ms, 4 x 12 0.8989, 5 x 8 0.9014 --
 // and 0.9005 for the round-2 kernel that held every tile in every wave at 2 waves per SIMD: the launch is not bound by
 // its own occupancy; kept for the smaller footprint)
-#ifndef INSTAG_WG_WAVES
-#define INSTAG_WG_WAVES 4
-#endif
-__global__ void __launch_bounds__(MLP_BLOCK) __attribute__((amdgpu_waves_per_eu(INSTAG_WG_WAVES)))
+constexpr int WG_WAVES = 4;
+__global__ void __launch_bounds__(MLP_BLOCK) __attribute__((amdgpu_waves_per_eu(WG_WAVES)))
 weight_grad_batched_kernel(WgBatch b) {
   __shared__ float s_acc[3 * 1024];          // only jobs of fewer than four tiles combine through LDS
   const WgJob job = b.j[blockIdx.y];

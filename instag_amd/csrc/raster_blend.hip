@@ -45,17 +45,6 @@ constexpr float T_MIN = 0.0001f;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float FAR_PIXEL = 1e18f;
 
-#ifdef BLEND_DBG2
-// (diagnostic build only: who claimed which segment slot, and what a wait for a post that gave up was looking at)
-__device__ uint32_t g_seg_owner[1 << 16];
-__device__ uint32_t g_stall_log[8 * 512 + 8];
-__device__ uint32_t* g_stall_host;            // (pinned host memory: readable while a kernel hangs)
-#endif
-#ifdef BLEND_DBG
-// (diagnostic build only: when each tile's workgroup started and ended, and where it ran -- scripts/probes/blend_tile_profile.py)
-__device__ uint32_t g_blend_dbg[4096 * 8];
-#endif
-
 //
 // GEO = false, the colour-only variant: depth, normal and extra are neither blended, checkpointed nor stored (a caller
 // that reads only the image, alpha and the attention map -- the training step outside its geometry-prior phase -- asks
@@ -97,9 +86,6 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
   const int start = ranges[2 * tile], end = ranges[2 * tile + 1];
   const int rounds = (end - start + BLOCK - 1) / BLOCK;
   int toDo = end - start;
-#ifdef BLEND_DBG
-  const uint64_t dbg_t0 = wall_clock64();
-#endif
   // every SEG_LEN entries of the list are a segment with a slot of its own (common.hpp BinningLayout): the per-pixel
   // state after each segment the tile walks is kept there, so that the backward pass can start anywhere
   static_assert(BLOCK % SEG_LEN == 0 && SEG_LEN % 4 == 0, "a batch is a whole number of segments");
@@ -248,17 +234,6 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
     if (tid == 0) {
       tile_rounds[tile] = (uint32_t)walked;
       s_base = nseg ? atomicAdd(seg_count, nseg) : 0u;
-#ifdef BLEND_DBG
-      if (tile < 4096) {
-        const uint64_t t1 = wall_clock64();
-        uint32_t hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        uint32_t* d = g_blend_dbg + 8 * tile;
-        d[0] = (uint32_t)dbg_t0; d[1] = (uint32_t)(dbg_t0 >> 32); d[2] = (uint32_t)t1; d[3] = (uint32_t)(t1 >> 32);
-        d[4] = hw; d[5] = xcc; d[6] = tile_last; d[7] = (uint32_t)(end - start);
-      }
-#endif
     }
     __syncthreads();
     for (uint32_t k = tid; k < nseg; k += BLOCK) {
@@ -295,7 +270,7 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
 // ---- forward, one SEGMENT at a time ------------------------------------------------------------------------------------
 // The kernel above walks a tile's list front to back in one workgroup: its duration is the longest tile's chain (C3: a
 // few dozen tiles of the 650 populated ones walk 700-960 entries -- rays through hair never saturate -- and run alone
-// for the last 60 of 110 us, scripts/probes/blend_tile_profile.py).  Here the unit of work is one SEG_LEN-entry segment:
+// for the last 60 of 110 us, profiles/r03_blend_tile_profile_*.txt).  Here the unit of work is one SEG_LEN-entry segment:
 // workgroups CLAIM the segments of a tile in order (one atomic), so several workgroups -- the tile's own plus helper
 // workgroups started for tiles that walked far in the previous launch (walk hints) -- walk one tile's list on several
 // CUs at a time.  What a segment needs from the segments in front of it is one number per pixel, the transmittance in
@@ -311,14 +286,8 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
 // transmittance-only pass (no colours, no stop rule: 0.6 of a walk), posts t_seg, waits for the predecessors' posts --
 // their owners are running and wait for nothing themselves -- and walks again with P known.  A tile nobody helps with
 // is therefore walked exactly once, as before; results are bit-identical whoever takes part.
-#ifndef FWD_HELPERS_N
-#define FWD_HELPERS_N 6
-#endif
-#ifndef FWD_LONG_SEGS_N
-#define FWD_LONG_SEGS_N 3
-#endif
-constexpr int FWD_HELPERS = FWD_HELPERS_N;            // helper workgroups per tile in a launch with walk hints
-constexpr uint32_t FWD_LONG_SEGS = FWD_LONG_SEGS_N;     // a tile that walked this many segments lately gets helpers
+constexpr int FWD_HELPERS = 6;            // helper workgroups per tile in a launch with walk hints
+constexpr uint32_t FWD_LONG_SEGS = 3;     // a tile that walked this many segments lately gets helpers
 constexpr uint32_t FWD_HINT_UNIT = 8;     // walk hints are kept in 1/8 segments (they decay by one unit per call)
 constexpr int SYNC_CLAIM = 0, SYNC_DONE = 1, SYNC_INV_DEAD = 2, SYNC_RESOLVED = 3;
 
@@ -380,13 +349,9 @@ __device__ __forceinline__ void fold_segment(FwdSums& r, int q, float T_after, c
 }
 
 template <bool AUX, bool GEO>
-#ifdef FWD_CAP128
-__global__ void __launch_bounds__(BLOCK, 4)
-#else
 // (three workgroups per CU at ~140 registers.  Held to 128 -- four per CU, every tile's own workgroup resident from the
 // start -- the inner loop waits for its LDS reads one by one: 112 us against 104)
 __global__ void __launch_bounds__(BLOCK)
-#endif
 blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                            const float* __restrict__ rec2d, uint32_t* __restrict__ n_contrib,
                            float* __restrict__ final_T, float* __restrict__ out_color,
@@ -413,14 +378,8 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
   // The tiles' own workgroups come first in block order, the helpers behind them: at 128 registers all 1,024 of C3's
   // tiles are resident at once, a third of them are empty and leave within a microsecond, and the helpers take those
   // slots (helpers in FRONT delay every tile's start by the dispatch of 3 x tiles blocks that mostly leave: +6 us)
-#ifdef FWD_HELPERS_FIRST
-  const int nhelp = (int)gridDim.x - ntiles;
-  const bool helper = (int)blockIdx.x < nhelp;
-  const int tile = helper ? (int)blockIdx.x / FWD_HELPERS : (int)blockIdx.x - nhelp;
-#else
   const bool helper = (int)blockIdx.x >= ntiles;
   const int tile = helper ? ((int)blockIdx.x - ntiles) / FWD_HELPERS : (int)blockIdx.x;
-#endif
   // (any content of the hint will do: the tile's own workgroup and its helpers read the same word -- nobody writes it
   // before the tile is complete -- and helpers only take work that is there)
   // share_all (tests): every tile long enough is shared, hints or not
@@ -452,9 +411,6 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
   const int slot0 = start / SEG_LEN + tile;
   constexpr size_t SLOT = (size_t)SEG_FLOATS * TILE_PIX;
   const f32x2 pix_in = inside ? f32x2{(float)pxi, (float)pyi} : f32x2{FAR_PIXEL, FAR_PIXEL};
-#ifdef BLEND_DBG
-  const uint64_t dbg_t0 = wall_clock64();
-#endif
 
   // the records of the segment this workgroup will probably take next are fetched while it walks the current one
   float4 nrec0, nrec1, nrec2, nrec3;
@@ -503,9 +459,6 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
       seg = (int)s_word[0];
     }
     const int slot = slot0 + seg;
-#ifdef BLEND_DBG2
-    if (!direct && tid == 0 && slot < (1 << 16)) g_seg_owner[slot] = (helper ? 0x80000000u : 0u) | ((uint32_t)blockIdx.x + 1u);
-#endif
     if (seg >= nsegs || (!direct && (uint32_t)seg >= s_word[1])) {
       // nothing left to take: the list ends here (or the tile is known to be finished in front of this segment).  A
       // claimed segment is always posted -- a workgroup that took a later one before the tile was known to be
@@ -573,19 +526,6 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
             __builtin_amdgcn_s_sleep(8);
             if (++spins > (1u << 15)) {                      // (~30 ms) gave up: the result is wrong, say so (sort_stalls())
               if (stalls) atomicAdd(stalls, 1u);
-#ifdef BLEND_DBG2
-              {
-                const uint32_t r = atomicAdd(&g_stall_log[0], 1u);
-                if (r < 512u && g_stall_host != nullptr) {
-                  uint32_t* d = g_stall_host + 8 + 8 * r;
-                  __hip_atomic_store(&g_stall_host[0], r + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                  d[0] = (uint32_t)tile; d[1] = (uint32_t)seg; d[2] = (uint32_t)q;
-                  d[3] = (slot0 + q) < (1 << 16) ? g_seg_owner[slot0 + q] : 0u;
-                  d[4] = (helper ? 0x80000000u : 0u) | ((uint32_t)blockIdx.x + 1u);
-                  d[5] = (uint32_t)nsegs; d[6] = ld_agent(&sync[SYNC_CLAIM]); d[7] = ~ld_agent(&sync[SYNC_INV_DEAD]);
-                }
-              }
-#endif
               break;
             }
           }
@@ -767,17 +707,6 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
       // tile that walked far in one of the last FWD_HINT_UNIT * (length - 2) calls is worth its helpers' first look
       if (walk_hints) st_agent(&walk_hints[tile], max((uint32_t)walked * FWD_HINT_UNIT, hint > 0u && hint < (1u << 20) ? hint - 1u : 0u));
       s_base = nseg ? atomicAdd(seg_count, nseg) : 0u;
-#ifdef BLEND_DBG
-      if (tile < 4096) {
-        const uint64_t t1 = wall_clock64();
-        uint32_t hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        uint32_t* d = g_blend_dbg + 8 * tile;
-        d[0] = (uint32_t)dbg_t0; d[1] = (uint32_t)(dbg_t0 >> 32); d[2] = (uint32_t)t1; d[3] = (uint32_t)(t1 >> 32);
-        d[4] = hw; d[5] = xcc; d[6] = tile_last; d[7] = (uint32_t)(end - start);
-      }
-#endif
     }
     __syncthreads();
     for (uint32_t k = tid; k < nseg; k += BLOCK) {
@@ -1187,9 +1116,6 @@ int launch_blend_forward(const Camera& c, const int32_t* ranges, const uint32_t*
     // INSTAG_BLEND_FWD_SHARE_ALL=1 (tests): helpers for every tile of three or more segments, with or without hints
     const char* e_all = getenv("INSTAG_BLEND_FWD_SHARE_ALL");
     const int share_all = (e_all && e_all[0] == '1') ? 1 : 0;
-#ifdef FWD_NO_HELP
-    walk_hints = nullptr;
-#endif
     const int grid = (walk_hints || share_all) ? tiles * (1 + FWD_HELPERS) : tiles;
     uint32_t* stalls = sort_stalls_device_ptr();
 #define INSTAG_BF(A, G)                                                                                                 \
@@ -1260,18 +1186,3 @@ int launch_blend_backward(const Camera& c, const int32_t* ranges, const uint32_t
 }
 
 }  // namespace instag
-
-#ifdef BLEND_DBG
-extern "C" int instag_debug_blend_timing(uint32_t* host, int n_words) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(instag::g_blend_dbg), sizeof(uint32_t) * (size_t)n_words);
-}
-#endif
-
-#ifdef BLEND_DBG2
-extern "C" int instag_debug_blend_stalls(uint32_t* host, int n_words) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(instag::g_stall_log), sizeof(uint32_t) * (size_t)n_words);
-}
-extern "C" int instag_debug_blend_stall_host(uint32_t* pinned_device_ptr) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(instag::g_stall_host), &pinned_device_ptr, sizeof(pinned_device_ptr));
-}
-#endif

@@ -264,7 +264,7 @@ def join_pending_aux(final: bool = False):
         while _PENDING_AUX:
             entry = _PENDING_AUX.pop()
             leaf, m2d_aux = entry["leaf"], entry["m2d_aux"]
-            if FOLD_AUX_M2D and (leaf.grad is not None or FOLD_AUX_M2D == "always"):
+            if FOLD_AUX_M2D and leaf.grad is not None:
                 _FOLDED.append((leaf, m2d_aux))          # the caller adds it (take_folded_aux)
             else:
                 leaf.grad = m2d_aux if leaf.grad is None else leaf.grad.add_(m2d_aux)
@@ -273,7 +273,6 @@ def join_pending_aux(final: bool = False):
 # A trainer whose next launch after backward reads means2D.grad anyway (the densification statistics) may take the aux
 # image's share from here and add it in that launch (glue.densify_stats(grad_add=...)) instead of paying an elementwise
 # launch on the tail of the step: set FOLD_AUX_M2D around backward, call take_folded_aux(leaf) right after it.
-# ("always": also when the leaf has no .grad at that point -- its gradient was asked for with torch.autograd.grad.)
 FOLD_AUX_M2D = False
 _FOLDED = []
 

@@ -40,7 +40,6 @@ class MultiTensorAdam:
         self._dev = None
         self._step = None
         self._layout_key = None
-        self._partition = None
         self._extra_n, self._extra_vals, self._extra_off = 0, [], 0
 
     # ---- a few 64-bit words that ride on the learning-rate upload ------------------------------------------------------
@@ -129,12 +128,6 @@ class MultiTensorAdam:
                                "capturing step() into a graph")
         # static part: chunk table, group table, pinned staging buffers
         chunks = [(ti, c) for ti, t in enumerate(tensors) for c in range((t[0].numel() + chunk - 1) // chunk)]
-        self._n_late_chunks = len(chunks)
-        if self._partition is not None:
-            # step(part): "late" tensors' chunks first, "early" ones behind them -- each part is one range of the table
-            early = [bool(self._partition(t[0])) for t in tensors]
-            chunks = [c for c in chunks if not early[c[0]]] + [c for c in chunks if early[c[0]]]
-            self._n_late_chunks = sum(1 for c in chunks if not early[c[0]])
         self._chunks = torch.tensor(chunks, dtype=torch.int32, device=dev).contiguous()
         garr = np.zeros(len(self.param_groups), dtype=_GROUP_DT)
         for i, g in enumerate(self.param_groups):
@@ -177,9 +170,7 @@ class MultiTensorAdam:
             self._layout(tensors)
 
     @torch.no_grad()
-    def step(self, part=None):
-        """``part`` (with a ``partition`` set): "early" / "late" steps only the tensors the partition function sends
-        there -- a step as two launches at different points of the backward pass; both parts together are one step()."""
+    def step(self):
         L = _lib.lib()
         tensors = self._gather()
         if not tensors:
@@ -190,19 +181,12 @@ class MultiTensorAdam:
             gh = self._grads_host
             for i, t in enumerate(tensors):
                 gh[i] = 0 if t[1] is None else t[1].data_ptr()
-            first, count = 0, self._chunks.shape[0]
-            if part is not None:
-                assert self._partition is not None and part in ("early", "late")
-                first, count = (0, self._n_late_chunks) if part == "late" else \
-                    (self._n_late_chunks, count - self._n_late_chunks)
             # (one launch: the kernel counts the steps itself, per tensor)
             check(L.instag_adam_step_grads_ticketed(ptr(self._tensors_dev), gh.ctypes.data, len(tensors),
                                                     ptr(self._groups_dev), ptr(self._lr_dev),
-                                                    self._chunks.data_ptr() + 8 * first, count, ptr(self._step),
+                                                    ptr(self._chunks), self._chunks.shape[0], ptr(self._step),
                                                     ptr(self._tickets), _lib.current_stream()), "adam_step")
             return
-        if part is not None:
-            raise RuntimeError("MultiTensorAdam.step(part): more tensors than one launch's gradient table holds")
         tarr = self._tensors_host.numpy().view(_TENSOR_DT)
         for i, (p, grad, m, v, gi) in enumerate(tensors):
             tarr[i] = (p.data_ptr(), 0 if grad is None else grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi, 0)
@@ -255,13 +239,11 @@ class CombinedAdam(MultiTensorAdam):
     ``motion_optimizer`` back to back, train_face.py:781-788).  The member optimizers keep their own ``param_groups``
     and ``state`` (densify / prune / lr schedules keep working on them); this object only steps them together."""
 
-    def __init__(self, optimizers, partition=None):
-        """``partition(param) -> bool``: True = the parameter belongs to step("early"), False to step("late")."""
+    def __init__(self, optimizers):
         self.optimizers = list(optimizers)
         self._dev = None
         self._step = None
         self._layout_key = None
-        self._partition = partition
         self._extra_n, self._extra_vals, self._extra_off = 0, [], 0
 
     @property
@@ -325,8 +307,7 @@ class MultiTensorAdamEMA(MultiTensorAdam):
             self._ema_table(tensors)
 
     @torch.no_grad()
-    def step(self, part=None):
-        assert part is None, "MultiTensorAdamEMA steps all of its tensors in one launch"
+    def step(self):
         L = _lib.lib()
         tensors = self._gather()
         if not tensors:
@@ -366,13 +347,12 @@ def lambda_lr(optimizer, base_lrs, factor: float):
 
 class StepOptimizers:
     """The optimizers one train step advances, in the order the reference steps them.  With ``combine`` and every member
-    fused, one CombinedAdam launches them together (and uploads their learning rates in one copy); ``partition`` is its
-    early / late split (CombinedAdam)."""
+    fused, one CombinedAdam launches them together (and uploads their learning rates in one copy)."""
 
-    def __init__(self, *members, combine: bool = True, partition=None):
+    def __init__(self, *members, combine: bool = True):
         self.members = list(members)
         fused = all(isinstance(o, MultiTensorAdam) for o in self.members)
-        self.combined = CombinedAdam(self.members, partition=partition) if combine and fused else None
+        self.combined = CombinedAdam(self.members) if combine and fused else None
         self._launches = [self.combined] if self.combined is not None else self.members
 
     def push_lrs(self):
@@ -381,9 +361,9 @@ class StepOptimizers:
             if hasattr(o, "set_lrs"):
                 o.set_lrs()
 
-    def step(self, part=None):
+    def step(self):
         if self.combined is not None:
-            self.combined.step(part)
+            self.combined.step()
             return
         for o in self.members:
             o.step()

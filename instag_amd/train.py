@@ -374,12 +374,8 @@ class FaceTrainer:
         self.motion_optimizer = make_motion_optimizer(motion_net, self.on_gpu)
         self._motion_base_lr = [float(g["lr"]) for g in self.motion_optimizer.param_groups]
         self.g.training_setup(self.opt, fused=self.on_gpu)
-        # on the GPU one launch steps both (train_face.py:781-788 steps them back to back); step("early") / step("late")
-        # = the same step as two launches (GraphedStep's single-graph form): the per-Gaussian parameters whose gradients
-        # are final when the backward pass reaches the motion fields (_forward_backward_cut) are stepped beside the rest
-        # of the pass, positions and networks behind it
-        early = lambda q: any(q is v for k, v in self.g._p.items() if k != "xyz")
-        self.optimizers = StepOptimizers(self.motion_optimizer, self.g.optimizer, partition=early)
+        # on the GPU one launch steps both (train_face.py:781-788 steps them back to back)
+        self.optimizers = StepOptimizers(self.motion_optimizer, self.g.optimizer)
         self.last = {}
         self._graph = None            # the captured step replayed last
         self._graph_cache = {}        # phase -> captured step
@@ -515,7 +511,7 @@ class FaceTrainer:
             pkg["_m2d_aux"] = diff_gauss.take_folded_aux(pkg["viewspace_points"])
         return pkg, loss, Ll1
 
-    def _forward_backward_cut(self, frame: Frame, phase: FacePhase = C3_PHASE, fold_aux: bool = False):
+    def _forward_backward_cut(self, frame: Frame, phase: FacePhase = C3_PHASE):
         """The step's forward and the FIRST part of its backward: from the loss through the loss block, the rasterizer
         and the deform operator -- up to the tensors render_motion names as the cut (the motion fields' head outputs,
         the routed position, the attention colours).  Afterwards the gradients of every per-Gaussian parameter except
@@ -548,7 +544,6 @@ class FaceTrainer:
         cut = [c for c in cut if c is not None and c.requires_grad]
         vs = pkg["viewspace_points"]
         early = [q for k, q in self.g._p.items() if k != "xyz" and q.requires_grad]
-        diff_gauss.FOLD_AUX_M2D = "always" if fold_aux else False    # (see _forward_backward)
         try:
             with deferred_grads(self.device):
                 got = torch.autograd.grad(loss, cut + early + [vs], grad_outputs=root_gradient(loss), allow_unused=True,
@@ -556,10 +551,6 @@ class FaceTrainer:
         except BaseException:
             diff_gauss.reset_aux_state()
             raise
-        finally:
-            diff_gauss.FOLD_AUX_M2D = False
-        if fold_aux:
-            pkg["_m2d_aux"] = diff_gauss.take_folded_aux(vs)
         g_cut, g_early, g_vs = got[:len(cut)], got[len(cut):len(cut) + len(early)], got[-1]
         have = []
         for q, gq in zip(early, g_early):
@@ -804,16 +795,13 @@ class GraphedStep(graphs.CapturedStep):
         # "early": THREE graphs -- A' (forward, backward down to the motion fields' outputs), A'' (the motion fields'
         # backward), B (scale, hand back, statistics, optimizers): the bucket of the per-Gaussian gradients that are
         # final after A' (8 of the 10 MB at 100k Gaussians) is exchanged WHILE A'' runs, the small second bucket
-        # (positions + networks) behind it.  INSTAG_DP_EARLY_ALLREDUCE=1 makes it the form several ranks use.
+        # (positions + networks) behind it.  It is the form several ranks use.
         if split_for_allreduce is None:
-            split_for_allreduce = ("early" if os.environ.get("INSTAG_DP_EARLY_ALLREDUCE", "1") == "1" else True) \
-                if self.distributed else False
+            split_for_allreduce = "early" if self.distributed else False
         # (the cut runs through the fused deform operator, which needs the alignment on: a phase without it -- the same
         # on every rank -- takes the two-graph form)
         self.early = split_for_allreduce == "early" and bool(phase.align)
         self.split = bool(split_for_allreduce)
-        self.early_optimizer = (not self.split and bool(phase.align) and t.optimizers.combined is not None
-                                and os.environ.get("INSTAG_EARLY_OPTIMIZER", "0") == "1")
         self.static = example.clone_static()
         cold = warmup_steps > 0
 
@@ -857,43 +845,7 @@ class GraphedStep(graphs.CapturedStep):
         if dot:
             self.graph_a.enable_debug_mode()
         self.graph_a2 = None
-        # single graph, optimizers in two launches (INSTAG_EARLY_OPTIMIZER=1, off by default): statistics and the
-        # per-Gaussian parameters except the positions (20 of 24 floats per Gaussian) on a side stream beside the motion
-        # fields' backward, positions + networks behind it.  The last launch of the step shrinks from 24 to 15 us, but
-        # whatever the side launches run beside pays for it (sigma_net's backward 64 -> 73 us): no gain measured from
-        # any fork point
-        if self.early_optimizer:
-            side = _lib.side_stream(dev, "early_optimizer")
-            with graphs.capture(self.graph_a, self.plan, cold, **options):
-                main = torch.cuda.current_stream(dev)
-                pkg, loss, l1, early, finish = t._forward_backward_cut(self.static, phase, fold_aux=True)
-
-                def early_launches():
-                    side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(side), torch.no_grad():
-                        update_densification_stats(t.g, pkg["viewspace_points"].grad, pkg["radii"],
-                                                   dict.get(pkg, "_m2d_aux"))
-                        t.optimizers.step("early")
-
-                # where the side launches start: beside the largest MLP's backward they cost it 9 us and take 65 us
-                # themselves (24 alone); behind it they run beside the heads' and the encoder's backward
-                at = os.environ.get("INSTAG_EARLY_OPTIMIZER_AT", "sigma_backward")
-                from . import deferred
-                if at == "cut":
-                    early_launches()
-                else:
-                    deferred.on_milestone(at, early_launches)
-                try:
-                    finish()
-                    deferred.milestone(at)          # (an operator path without that milestone: launch now)
-                finally:
-                    deferred.clear_milestones()
-                main.wait_stream(side)
-                with torch.no_grad():
-                    t.optimizers.step("late")
-                t._zero_grad()
-            del pkg, finish
-        elif not self.split:
+        if not self.split:
             with graphs.capture(self.graph_a, self.plan, cold, **options):
                 pkg, loss, l1 = t._forward_backward(self.static, phase, fold_aux=True)
                 t._stats_and_optimizers(pkg, False)

@@ -1,4 +1,4 @@
-"""Micro-benchmark of the tri-plane encoder kernels at the C3 shape (debug variants via INSTAG_TP_VARIANT)."""
+"""Micro-benchmark of the tri-plane encoder kernels at the C3 shape."""
 import sys, os, torch, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from instag_amd import _lib
@@ -24,4 +24,4 @@ torch.cuda.synchronize()
 for name, kid in (("fwd", 7), ("bwd", 8)):
     ms, cnt = C.c_double(0), C.c_int64(0)
     L.instag_prof_read(kid, C.byref(ms), C.byref(cnt))
-    print(f"variant {os.environ.get('INSTAG_TP_VARIANT', '0')}: triplane {name} {1e3 * ms.value / max(1, cnt.value):7.1f} us", flush=True)
+    print(f"triplane {name} {1e3 * ms.value / max(1, cnt.value):7.1f} us", flush=True)

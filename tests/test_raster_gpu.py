@@ -306,7 +306,7 @@ def test_capacity_mode_matches_sync_mode():
             assert all(torch.isfinite(v.grad).all() for v in inp.values() if v is not None and v.grad is not None)
 
 
-def test_graphed_train_step_matches_eager(monkeypatch):
+def test_graphed_train_step_matches_eager():
     """The hipGraph-replayed train step performs the same arithmetic as the eager step."""
     from instag_amd import diff_gauss
     from instag_amd.scene_synth import synthetic_frame, toy_cameras
@@ -316,11 +316,8 @@ def test_graphed_train_step_matches_eager(monkeypatch):
     frames = [make_frame(cams[i].to(dev), synthetic_frame(128, i, dev)) for i in range(3)]
     losses = {}
     params = {}
-    for mode in ("eager", "graph", "graph-two-optimizer-launches", "graph-split", "graph-early"):
+    for mode in ("eager", "graph", "graph-split", "graph-early"):
         tr = build_trainer(3000, dev, seed=1)
-        # "graph-two-optimizer-launches": one graph, statistics + the optimizer step of SH / opacity / scale / rotation
-        # on a side stream beside the motion fields' backward, positions + networks at the end (off by default)
-        monkeypatch.setenv("INSTAG_EARLY_OPTIMIZER", "1" if mode == "graph-two-optimizer-launches" else "0")
         try:
             if mode != "eager":
                 # 2 eager + 2 capacity-mode steps on frame 0; "graph-split" = the two-graph form used with several
@@ -329,7 +326,6 @@ def test_graphed_train_step_matches_eager(monkeypatch):
                 # fields' backward runs) is exchanged beside that backward
                 tr.enable_graph(frames[0], warmup_steps=2,
                                 split_for_allreduce={"graph-split": True, "graph-early": "early"}.get(mode, False))
-                assert tr._graph.early_optimizer == (mode == "graph-two-optimizer-launches")
                 if mode == "graph-early":
                     g = tr._graph
                     assert g.graph_a2 is not None and g.graph_b is not None
@@ -350,7 +346,7 @@ def test_graphed_train_step_matches_eager(monkeypatch):
         losses[mode] = ls
         params[mode] = tr.g.get_xyz.detach().clone()
     assert tr.iteration == 10
-    for mode in ("graph", "graph-two-optimizer-launches", "graph-split", "graph-early"):
+    for mode in ("graph", "graph-split", "graph-early"):
         for a_, b_ in zip(losses["eager"], losses[mode]):
             assert abs(a_ - b_) <= 1e-5 * max(1.0, abs(a_)), (mode, losses["eager"], losses[mode])
         assert float((params["eager"] - params[mode]).abs().max()) <= 1e-5
