@@ -720,6 +720,33 @@ int instag_lpips_backward(const instag_lpips_weights* w, const int32_t* p_dev, i
                           instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation (csrc/metrics.hip): frame metrics and the inference epilogue.  Forward only.
+ *
+ * frame_metrics: pred, gt [B,3,H,W] fp32.  flags bit 0: pred is clamped to [0,1] first; bit 1: pred and
+ *   gt are quantised as a video frame is, float(int(clamp(x,0,1) * 255)) / 255 with truncation (the
+ *   operands metrics.py:205-206 feeds its meters).  partials: workspace of
+ *   instag_frame_metrics_num_partials(B,H,W) doubles.  per_frame [B,5] = l1, mse, psnr = -10 log10(mse)
+ *   (+inf for mse == 0, metrics.py:127), psnr_rgb = the mean over the channels of 20 log10(1 / sqrt(mse_c))
+ *   (utils/image_utils.py psnr), ssim (utils/loss_utils.py:42-72).  meter (may be NULL): double[6] on the
+ *   device; the five figures of the first n_valid <= B frames and their count are added to it.
+ *   Two launches on `stream`, no host synchronisation, fixed summation order (fp64, no atomics).
+ * meter_add: slot[0] += values[0] + ... + values[n-1] (in order), slot[1] += n; a further figure (LPIPS)
+ *   kept in the same device state.
+ * infer_compose (synthesize_fuse.py:65-76): face, mouth [3,H,W] rendered over bg [3], a_face, a_mouth
+ *   [1,H,W], scene [3,H,W] or NULL (= black), dilate odd in 1 .. 31 (1 = off).  With a_d the dilate x dilate
+ *   running maximum of a_mouth (stride 1, positions outside the image do not take part):
+ *   mouth_image = mouth - bg (1 - a_mouth) + scene (1 - a_d), image = clamp(face - bg (1 - a_face) +
+ *   mouth_image (1 - a_face), 0, 1) [3,H,W]; frame_u8 (may be NULL) [H,W,3] = uint8(int(image * 255)).
+ * ------------------------------------------------------------------------------------------ */
+int64_t instag_frame_metrics_num_partials(int32_t B, int32_t H, int32_t W);
+int instag_frame_metrics(const float* pred, const float* gt, int32_t B, int32_t H, int32_t W, int32_t flags,
+                         double* partials, float* per_frame, double* meter, int32_t n_valid, instag_stream_t stream);
+int instag_meter_add(const float* values, int32_t n, double* slot, instag_stream_t stream);
+int instag_infer_compose(const float* face, const float* a_face, const float* mouth, const float* a_mouth,
+                         const float* bg, const float* scene, int32_t dilate, float* image, uint8_t* frame_u8,
+                         int32_t H, int32_t W, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named
  * kernel with hipEvents on the launch stream; instag_prof_read synchronises those events and
  * returns accumulated milliseconds and launch count since the last reset.

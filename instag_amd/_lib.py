@@ -316,6 +316,10 @@ _PROTOS = {
                                        vp, vp, vp]),
     "instag_lpips_backward": (C.c_int, [C.POINTER(LpipsWeights), vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz,
                                         vp, vp]),
+    "instag_frame_metrics_num_partials": (C.c_int64, [i32, i32, i32]),
+    "instag_frame_metrics": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "instag_meter_add": (C.c_int, [vp, i32, vp, vp]),
+    "instag_infer_compose": (C.c_int, [vp] * 6 + [i32, vp, vp, i32, i32, vp]),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

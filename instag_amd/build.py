@@ -47,6 +47,7 @@ SOURCES = {
     "prior.hip": [],
     "pretrain.hip": ["-ffp-contract=off"],
     "lpips.hip": [],
+    "metrics.hip": [],
 }
 
 

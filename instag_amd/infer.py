@@ -20,34 +20,57 @@ from .train import Frame
 
 
 class FuseRenderer:
-    def __init__(self, gaussians, motion_net, gaussians_mouth, motion_net_mouth, background, personalized=False):
+    def __init__(self, gaussians, motion_net, gaussians_mouth, motion_net_mouth, background, personalized=False,
+                 dilate: int = 1, as_uint8: bool = False):
+        """``dilate`` (odd, 1 = off; synthesize_fuse.py --dilate is 13): the scene background shows through the mouth
+        pass where the dilate x dilate maximum of its alpha is below one.  ``as_uint8``: ``render`` / ``render_batch``
+        also return the frames as the reference writes them, uint8 [H,W,3] (synthesize_fuse.py:76).  With either set
+        the frame is composed by metrics.infer_compose (one launch: dilation, composition, clamp, bytes)."""
         self.g, self.net, self.gm, self.netm = gaussians, motion_net, gaussians_mouth, motion_net_mouth
         self.bg = background
         self.personalized = personalized
+        self.dilate, self.as_uint8 = int(dilate), bool(as_uint8)
+        if self.dilate < 1 or self.dilate > 31 or self.dilate % 2 == 0:
+            raise ValueError(f"FuseRenderer: dilate must be odd and in 1 .. 31, got {dilate}")
+        self.frames_per_replay = 1
         self._graph = None
 
     @torch.no_grad()
     def _render(self, frame: Frame, scene_background=None):
+        """-> image, or (image, frame_u8) with ``as_uint8``."""
+        if self.dilate != 1 or self.as_uint8:
+            from .metrics import infer_compose
+            out = render_fuse(frame, self.g, self.net, self.gm, self.netm, None, self.bg, personalized=self.personalized,
+                              inference=True, compose=False)
+            face, mouth = out["face"], out["mouth"]
+            image, u8 = infer_compose(face["render"], face["alpha"], mouth["render"], mouth["alpha"], self.bg,
+                                      scene_background, self.dilate, self.as_uint8)
+            return (image, u8) if self.as_uint8 else image
         out = render_fuse(frame, self.g, self.net, self.gm, self.netm, None, self.bg,
                           scene_background=scene_background, personalized=self.personalized, inference=True)
         return out["image"].clamp(0, 1)
 
     def render(self, frame: Frame, scene_background=None):
-        """-> image [3,H,W] in [0,1].  With a captured graph the returned tensor is the graph's static output buffer
-        (valid until the next call)."""
+        """-> image [3,H,W] in [0,1] (with ``as_uint8``: (image, frame uint8 [H,W,3])).  With a captured graph the
+        returned tensors are the graph's static output buffers (valid until the next call)."""
         if self._graph is None:
             return self._render(frame, scene_background)
-        return self.render_batch([frame], None if scene_background is None else [scene_background])[0]
+        out = self.render_batch([frame], None if scene_background is None else [scene_background])
+        return (out[0][0], out[1][0]) if self.as_uint8 else out[0]
 
     def render_batch(self, frames, scene_backgrounds=None):
         """-> images [len(frames),3,H,W].  With a captured graph of K frames per replay the frames go through in
         groups of K (one launch per group; a short last group is padded with its last frame); the returned tensor
-        is a copy only when more than one group was needed."""
+        is a copy only when more than one group was needed.  With ``as_uint8``: (images, frames uint8
+        [len(frames),H,W,3])."""
         if self._graph is None:
-            return torch.stack([self._render(f, None if scene_backgrounds is None else scene_backgrounds[i])
-                                for i, f in enumerate(frames)])
+            outs = [self._render(f, None if scene_backgrounds is None else scene_backgrounds[i])
+                    for i, f in enumerate(frames)]
+            if self.as_uint8:
+                return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
+            return torch.stack(outs)
         K = len(self._static)
-        outs = []
+        outs, outs_u8 = [], []
         for g0 in range(0, len(frames), K):
             group = frames[g0:g0 + K]
             for k in range(K):
@@ -58,9 +81,11 @@ class FuseRenderer:
             self._plan.begin_step()
             self._graph.replay()
             if len(frames) <= K:
-                return self._out[:len(group)]
+                return (self._out[:len(group)], self._out_u8[:len(group)]) if self.as_uint8 else self._out[:len(group)]
             outs.append(self._out[:len(group)].clone())
-        return torch.cat(outs)
+            if self.as_uint8:
+                outs_u8.append(self._out_u8[:len(group)].clone())
+        return (torch.cat(outs), torch.cat(outs_u8)) if self.as_uint8 else torch.cat(outs)
 
     def enable_graph(self, example: Frame, headroom: float = 1.5, frames_per_replay: int = 1):
         dev = self.bg.device
@@ -92,8 +117,13 @@ class FuseRenderer:
         self._graph = torch.cuda.CUDAGraph()
         with graphs.capture(self._graph, self._plan):
             outs = all_frames()
-            self._out = torch.stack(outs)
+            if self.as_uint8:
+                self._out = torch.stack([o[0] for o in outs])
+                self._out_u8 = torch.stack([o[1] for o in outs])
+            else:
+                self._out = torch.stack(outs)
         self._lanes = lanes
+        self.frames_per_replay = K
         return self
 
     def check_overflow(self):
@@ -101,4 +131,5 @@ class FuseRenderer:
 
     def close(self):
         self._graph = None
+        self.frames_per_replay = 1
         diff_gauss.set_capacity_plan(None)

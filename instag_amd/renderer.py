@@ -558,11 +558,12 @@ def render_motion_mouth_con(viewpoint_camera, pc, motion_net, pc_face, motion_ne
 
 
 def render_fuse(viewpoint_camera, pc, motion_net, pc_mouth, motion_net_mouth, pipe=None, bg_color=None,
-                scene_background=None, personalized=False, inference=False, k=10):
+                scene_background=None, personalized=False, inference=False, k=10, compose=True):
     """Face + mouth composition of the fuse stage: train_fuse_con.py:102-121 (training: both passes carry gradients
     and were rendered over ``bg_color``, which is taken out again) / synthesize_fuse.py:46-66 (inference: the mouth
     field reads the face field's cached motion).  ``scene_background`` [3,H,W] in [0,1] is what shows through both.
-    -> dict(image, face=<render_motion pkg>, mouth=<render_motion_mouth_con pkg>)."""
+    -> dict(image, face=<render_motion pkg>, mouth=<render_motion_mouth_con pkg>).  ``compose=False`` (extension): the two
+    passes only, ``image`` and ``mouth_image`` are None (the inference epilogue of metrics.infer_compose composes)."""
     from . import _lib
     dev = pc.get_xyz.device
     if CONCURRENT_FUSE_PASSES and dev.type == "cuda" and not inference and _lib.may_fork(dev):
@@ -584,6 +585,8 @@ def render_fuse(viewpoint_camera, pc, motion_net, pc_mouth, motion_net_mouth, pi
         face = render_motion(viewpoint_camera, pc, motion_net, pipe, bg_color, personalized=personalized, align=True)
         mouth = render_motion_mouth_con(viewpoint_camera, pc_mouth, motion_net_mouth, pc, motion_net, pipe, bg_color,
                                         personalized=personalized, align=True, k=k, inference=inference)
+    if not compose:
+        return {"image": None, "mouth_image": None, "face": face, "mouth": mouth}
     alpha, alpha_mouth = face["alpha"], mouth["alpha"]
     fr, mr = face["render"], mouth["render"]
     if (fr.is_cuda and fr.dim() == 3 and fr.shape[0] == 3 and fr.dtype == torch.float32 and mr.shape == fr.shape
