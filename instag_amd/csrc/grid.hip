@@ -267,9 +267,14 @@ grid_backward_kernel(const float* __restrict__ grad, const float* __restrict__ i
   const uint32_t b1 = min(B, b0 + per_block);
 
   // fixed-point scale of this workgroup: |sum into one entry| <= (#points) * max|grad| < 2^62
+  // (fmaxf drops a NaN operand and the integer conversion below would swallow it: a NaN gradient counts as an infinite
+  // one, so that the workgroup takes the float-atomic path and the NaN reaches the table gradient as in the reference)
   float gmax = 0.f;
   for (uint32_t l = 0; l < L; ++l)
-    for (uint32_t i = b0 * C + threadIdx.x; i < b1 * C; i += GRID_BLOCK) gmax = fmaxf(gmax, fabsf(grad[(size_t)l * B * C + i]));
+    for (uint32_t i = b0 * C + threadIdx.x; i < b1 * C; i += GRID_BLOCK) {
+      const float gv = grad[(size_t)l * B * C + i];
+      gmax = fmaxf(gmax, gv != gv ? INFINITY : fabsf(gv));
+    }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
   if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = gmax;
@@ -509,6 +514,9 @@ int run_tv(const float* inputs, const float* emb, float* grad, const int32_t* of
   return INSTAG_OK;
 }
 
+// the instantiations DISPATCH_DC knows; checked before any device work
+inline bool dc_supported(uint32_t D, uint32_t C) { return D >= 2 && D <= 5 && (C == 1 || C == 2 || C == 4 || C == 8); }
+
 #define DISPATCH_DC(D, C, FN, ...)                                                            \
   switch (D) {                                                                                \
     case 2: switch (C) { case 1: return FN<2, 1>(__VA_ARGS__); case 2: return FN<2, 2>(__VA_ARGS__); \
@@ -531,9 +539,10 @@ extern "C" {
 int instag_grid_encode_forward(const float* inputs, const float* embeddings, const int32_t* offsets, float* outputs,
                                uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, float* dy_dx,
                                uint32_t gridtype, int align_corners, uint32_t interp, instag_stream_t stream) {
-  INSTAG_REQUIRE(inputs && embeddings && offsets && outputs, "grid_encode_forward: NULL tensor");
   INSTAG_REQUIRE(L >= 1 && L <= 64, "GridEncoding: L must be in [1,64]");
-  if (B == 0) return INSTAG_OK;
+  INSTAG_REQUIRE(dc_supported(D, C), "GridEncoding: D must be 2..5 and C must be 1, 2, 4, or 8.");
+  if (B == 0) return INSTAG_OK;         // (an empty tensor has no storage: its pointers are NULL)
+  INSTAG_REQUIRE(inputs && embeddings && offsets && outputs, "grid_encode_forward: NULL tensor");
   hipStream_t s = (hipStream_t)stream;
   DISPATCH_DC(D, C, run_forward, inputs, embeddings, offsets, outputs, B, L, S, H, dy_dx, gridtype,
               align_corners != 0, interp, s);
@@ -546,9 +555,10 @@ int instag_grid_encode_backward(const float* grad, const float* inputs, const fl
                                 uint32_t L, float S, uint32_t H, const float* dy_dx, float* grad_inputs,
                                 uint32_t gridtype, int align_corners, uint32_t interp, instag_stream_t stream) {
   (void)embeddings;                     // (part of the reference's signature; the table gradient does not need the table)
-  INSTAG_REQUIRE(grad && inputs && offsets && grad_embeddings, "grid_encode_backward: NULL tensor");
   INSTAG_REQUIRE(L >= 1 && L <= 64, "GridEncoding: L must be in [1,64]");
+  INSTAG_REQUIRE(dc_supported(D, C), "GridEncoding: D must be 2..5 and C must be 1, 2, 4, or 8.");
   if (B == 0) return INSTAG_OK;
+  INSTAG_REQUIRE(grad && inputs && offsets && grad_embeddings, "grid_encode_backward: NULL tensor");
   hipStream_t s = (hipStream_t)stream;
   DISPATCH_DC(D, C, run_backward, grad, inputs, offsets, grad_embeddings, B, L, S, H, dy_dx, grad_inputs,
               gridtype, align_corners != 0, interp, s);
@@ -564,11 +574,12 @@ int instag_grid_total_variation(const float* inputs, const float* embeddings, fl
                                 float weight, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                                 uint32_t gridtype, int align_corners, uint32_t total_params, void* workspace,
                                 size_t workspace_bytes, instag_stream_t stream) {
-  INSTAG_REQUIRE(inputs && embeddings && grad && offsets, "grad_total_variation: NULL tensor");
   INSTAG_REQUIRE(L >= 1 && L <= 64, "GridEncoding: L must be in [1,64]");
+  INSTAG_REQUIRE(dc_supported(D, C), "GridEncoding: D must be 2..5 and C must be 1, 2, 4, or 8.");   // before the workspace is cleared
+  if (B == 0) return INSTAG_OK;
+  INSTAG_REQUIRE(inputs && embeddings && grad && offsets, "grad_total_variation: NULL tensor");
   const size_t need = instag_grid_total_variation_workspace_bytes(total_params, C);
   if (workspace == nullptr || workspace_bytes < need) { set_error("grad_total_variation: workspace too small"); return INSTAG_E_SPACE; }
-  if (B == 0) return INSTAG_OK;
   hipStream_t s = (hipStream_t)stream;
   INSTAG_CHECK_HIP(hipMemsetAsync(workspace, 0, need, s));
   uint32_t* counts = (uint32_t*)workspace;

@@ -44,6 +44,32 @@ def test_argument_errors_do_not_need_a_gpu():
     assert rc != 0 and b"D must be" in lib.instag_last_error()
 
 
+def test_grid_dispatch_errors_do_not_need_a_gpu():
+    """The three grid entry points refuse a (D, C) outside the sixteen built instantiations and a level count outside
+    [1, 64] with INSTAG_E_ARG, before any device work (the total variation: before its workspace is cleared)."""
+    from instag_amd import _lib
+    lib = _lib.lib()
+    E_ARG = 1                                   # INSTAG_E_ARG, include/instag_hip.h
+    one = ctypes.c_void_p(16)
+
+    def forward(D, C, L):
+        return lib.instag_grid_encode_forward(one, one, one, one, 4, D, C, L, 0.5, 16, None, 0, 0, 0, None)
+
+    def backward(D, C, L):
+        return lib.instag_grid_encode_backward(one, one, one, one, one, 4, D, C, L, 0.5, 16, None, None, 0, 0, 0, None)
+
+    def total_variation(D, C, L):
+        return lib.instag_grid_total_variation(one, one, one, one, 1e-3, 4, D, C, L, 0.5, 16, 0, 0, 8, one, 1 << 20, None)
+
+    for call in (forward, backward, total_variation):
+        for D, C in ((6, 2), (3, 3), (1, 1), (5, 16)):
+            assert call(D, C, 2) == E_ARG, (call.__name__, D, C)
+            assert b"D must be 2..5 and C must be 1, 2, 4, or 8" in lib.instag_last_error()
+        for L in (0, 65):
+            assert call(3, 2, L) == E_ARG, (call.__name__, L)
+            assert b"L must be in [1,64]" in lib.instag_last_error()
+
+
 def test_drop_in_package_names_import():
     import diff_gauss
     import gridencoder
