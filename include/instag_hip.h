@@ -501,6 +501,34 @@ int instag_frame_code_backward(const float* a, const float* e, const float* cons
                                instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same codes for a network built with audio_extractor == 'ave' (csrc/audio.hip):
+ *   enc_a [dim_aud] = AudioAttNet(AudioNet_ave(a))          scene/motion_net.py:29-64, :132-149
+ *   enc_e [6]       = cat(exp_encode_net(e[:5]), e[5:6])    as above
+ * a [8, 1, 512] (8 audio windows of 512 features), e [6] or NULL (then enc_e NULL).  `params` / `grads` are HOST
+ * arrays of 20 DEVICE pointers in state_dict order:
+ *   0-5   audio_net.encoder_fc1.{0,2,4}.{weight,bias}      linear 512->256->128->dim_aud (LeakyReLU 0.02 after 0 and 2)
+ *   6-15  audio_att_net.attentionConvNet.{0,2,4,6,8}.{weight,bias}   conv1d k3 s1 p1: dim_aud->16->8->4->2->1
+ *   16-17 audio_att_net.attentionNet.0.{weight,bias}       linear 8->8 (+ softmax)
+ *   18-19 exp_encode_net.net.{0,1}.weight                  [16,5], [5,16] (may be NULL when e is NULL)
+ * Semantics of instag_frame_code_*: forward keeps the activations backward reads in `saved`
+ * (instag_frame_code_ave_saved_floats floats, -1: dim_aud not supported); backward OVERWRITES every grads[i]; no
+ * gradient flows to a or e; no atomics on floats, two runs give the same bits.
+ * arrivals (device uint32, ZERO before the first call, one word per set of calls that may overlap): the 256 neurons
+ * of the first layer are split over 16 workgroups, each reads its rows of the 512 KB weight once for all eight windows,
+ * the last one to arrive runs the rest and leaves the word zero again.  NULL selects the single-workgroup form.
+ * backward runs on 16 workgroups that write disjoint rows of the two large weight gradients: it needs no workspace
+ * (the size query returns 0; workspace may be NULL).
+ * ------------------------------------------------------------------------------------------ */
+int64_t instag_frame_code_ave_saved_floats(int32_t dim_aud);
+int instag_frame_code_ave_forward(const float* a, const float* e, const float* const* params, float* enc_a,
+                                  float* enc_e, float* saved, int32_t dim_aud, uint32_t* arrivals,
+                                  instag_stream_t stream);
+size_t instag_frame_code_ave_backward_workspace_bytes(int32_t dim_aud);
+int instag_frame_code_ave_backward(const float* a, const float* e, const float* const* params, const float* saved,
+                                   const float* d_enc_a, const float* d_enc_e, float* const* grads, int32_t dim_aud,
+                                   void* workspace, size_t workspace_bytes, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused L1 + SSIM image loss.  Replaces utils/loss_utils.py l1_loss :26-27 and ssim :42-72 (11x11
  * Gaussian window sigma 1.5, zero padding, C1=0.01^2, C2=0.03^2, mean over C*H*W) as used at
  * train_face.py:450-456.  img1/img2 [C,H,W].  forward writes per-workgroup partial sums

@@ -283,6 +283,10 @@ _PROTOS = {
     "instag_frame_code_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "instag_frame_code_backward_workspace_bytes": (sz, [i32, i32, i32]),
     "instag_frame_code_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "instag_frame_code_ave_saved_floats": (C.c_int64, [i32]),
+    "instag_frame_code_ave_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+    "instag_frame_code_ave_backward_workspace_bytes": (sz, [i32]),
+    "instag_frame_code_ave_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "instag_l1_ssim_num_partials": (C.c_int, [i32, i32, i32]),
     "instag_l1_ssim_forward": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "instag_l1_ssim_backward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),

@@ -1,9 +1,11 @@
-"""Per-frame conditioning codes of a motion network as one HIP workgroup per pass (csrc/audio.hip).
+"""Per-frame conditioning codes of a motion network as one HIP launch per pass (csrc/audio.hip).
 
 Replaces, on the device, the reference's chain
     enc_a = audio_att_net(audio_net(a).unsqueeze(0))          scene/motion_net.py:283-289 / :672-677
     enc_e = cat(exp_encode_net(e[:-1]), e[-1:])               scene/motion_net.py:297-299 / :684-686
 (~11 conv1d / GEMM launches plus activations, three times that in backward) by one launch each way.
+A network built with audio_extractor == 'ave' has AudioNet_ave (scene/motion_net.py:132-149: three linear layers on
+[8, 1, 512] windows) in AudioNet's place: the instag_frame_code_ave_* pair, 20 parameters instead of 26.
 """
 from __future__ import annotations
 
@@ -15,11 +17,12 @@ from . import _lib
 from ._lib import check, ptr
 
 NPARAM = 26
+NPARAM_AVE = 20
 _ARRIVAL_SLOTS = 64
 
 
 def _ptr_array(tensors):
-    arr = (C.c_void_p * NPARAM)()
+    arr = (C.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):
         arr[i] = None if t is None else t.data_ptr()
     return arr
@@ -79,6 +82,108 @@ class _FrameCodes(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+class _FrameCodesAve(torch.autograd.Function):
+    """_FrameCodes for AudioNet_ave: a [8, 512], 20 parameters, `arrivals` None = the single-workgroup forward."""
+
+    @staticmethod
+    def forward(ctx, a, e, dim_aud, arrivals, *params):
+        L = _lib.lib()
+        a = a.contiguous().float()
+        params = tuple(None if p is None else p.contiguous() for p in params)
+        dev = a.device
+        n_saved = L.instag_frame_code_ave_saved_floats(dim_aud)
+        if n_saved < 0:
+            raise RuntimeError("frame_codes: unsupported dimensions")
+        enc_a = torch.empty(1, dim_aud, dtype=torch.float32, device=dev)
+        enc_e = None
+        if e is not None:
+            e = e.contiguous().float()
+            enc_e = torch.empty(6, dtype=torch.float32, device=dev)
+        saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
+        check(L.instag_frame_code_ave_forward(ptr(a), ptr(e), _ptr_array(params), ptr(enc_a), ptr(enc_e), ptr(saved),
+                                              dim_aud, ptr(arrivals), _lib.current_stream()),
+              "frame_code_ave_forward")
+        ctx.dim_aud = dim_aud
+        ctx.has_e = e is not None
+        ctx.save_for_backward(a, saved, *( [e] if e is not None else [] ), *[p for p in params if p is not None])
+        ctx.param_mask = [p is not None for p in params]
+        if enc_e is None:
+            return enc_a, torch.empty(0, device=dev)
+        return enc_a, enc_e
+
+    @staticmethod
+    def backward(ctx, d_enc_a, d_enc_e):
+        L = _lib.lib()
+        tensors = list(ctx.saved_tensors)
+        a, saved = tensors[0], tensors[1]
+        e = tensors[2] if ctx.has_e else None
+        rest = iter(tensors[3 if ctx.has_e else 2:])
+        params = [next(rest) if m else None for m in ctx.param_mask]
+        if d_enc_a is None:
+            d_enc_a = torch.zeros(1, ctx.dim_aud, dtype=torch.float32, device=a.device)
+        d_enc_a = d_enc_a.contiguous().float()
+        d_enc_e = d_enc_e.contiguous().float() if (ctx.has_e and d_enc_e is not None) else None
+        grads = [None if p is None else torch.empty_like(p) for p in params]
+        # sixteen workgroups write disjoint rows of the two large weight gradients: no workspace
+        check(L.instag_frame_code_ave_backward(ptr(a), ptr(e), _ptr_array(params), ptr(saved), ptr(d_enc_a),
+                                               ptr(d_enc_e), _ptr_array(grads), ctx.dim_aud, None, 0,
+                                               _lib.current_stream()),
+              "frame_code_ave_backward")
+        return (None, None, None, None, *grads)
+
+
+def _attention_params(field):
+    """The twelve audio_att_net tensors and the two expression weights (None, None without the expression branch) in
+    the C ABI's order, or None when the modules are not the stock architecture."""
+    att = field.audio_att_net
+    try:
+        aconvs = [att.attentionConvNet[i] for i in (0, 2, 4, 6, 8)]
+        lin = att.attentionNet[0]
+    except (IndexError, AttributeError, TypeError):
+        return None
+    if [(c.in_channels, c.out_channels) for c in aconvs] != [(att.dim_aud, 16), (16, 8), (8, 4), (4, 2), (2, 1)]:
+        return None
+    if att.seq_len != 8 or any(m.bias is None for m in aconvs + [lin]):
+        return None
+    out = []
+    for m in aconvs + [lin]:
+        out += [m.weight, m.bias]
+    if getattr(field, "exp_eye", False):
+        net = field.exp_encode_net.net
+        if len(net) != 2 or tuple(net[0].weight.shape) != (16, 5) or tuple(net[1].weight.shape) != (5, 16):
+            return None
+        out += [net[0].weight, net[1].weight]
+    else:
+        out += [None, None]
+    return out
+
+
+def _is_ave(field) -> bool:
+    return not hasattr(field.audio_net, "encoder_conv")
+
+
+def _module_params_ave(field):
+    """The 20 parameters of a network with AudioNet_ave in the C ABI's order, or None when the modules are not the
+    stock architecture (three Linear with bias, 512 -> 256 -> 128 -> dim_aud)."""
+    an = field.audio_net
+    try:
+        fcs = [an.encoder_fc1[i] for i in (0, 2, 4)]
+        if len(an.encoder_fc1) != 5:
+            return None
+        slopes = [an.encoder_fc1[i].negative_slope for i in (1, 3)]
+        shapes = [(m.in_features, m.out_features) for m in fcs]
+    except (IndexError, AttributeError, TypeError):
+        return None
+    tail = _attention_params(field)
+    if tail is None or slopes != [0.02, 0.02] or any(m.bias is None for m in fcs) \
+            or shapes != [(512, 256), (256, 128), (128, field.audio_att_net.dim_aud)]:
+        return None
+    out = []
+    for m in fcs:
+        out += [m.weight, m.bias]
+    return out + tail
+
+
 def _module_params(field):
     """The 26 parameters in the C ABI's order, or None when the modules are not the stock architecture."""
     an, att = field.audio_net, field.audio_att_net
@@ -112,11 +217,17 @@ def _module_params(field):
 
 
 def supported(field, a, e) -> bool:
-    if not (a.is_cuda and a.dim() == 3 and a.shape[0] == 8 and a.shape[2] == 16):
+    if not (a.is_cuda and a.dim() == 3 and a.shape[0] == 8):
         return False
     if e is not None and (e.numel() != 6 or not getattr(field, "exp_eye", False)):
         return False
     if e is None and getattr(field, "exp_eye", False):
+        return False
+    if _is_ave(field):
+        if tuple(a.shape[1:]) != (1, 512) or _module_params_ave(field) is None:
+            return False
+        return _lib.lib().instag_frame_code_ave_saved_floats(field.audio_att_net.dim_aud) > 0
+    if a.shape[2] != 16:
         return False
     params = _module_params(field)
     if params is None or a.shape[1] != field.audio_net.encoder_conv[0].in_channels:
@@ -128,8 +239,8 @@ def supported(field, a, e) -> bool:
 
 def frame_codes(field, a, e):
     """-> (enc_a [1, dim_aud], enc_e [6] or None) for a motion network `field` (UMF or PMF)."""
-    params = _module_params(field)
-    dims = (int(a.shape[1]), int(field.audio_net.encoder_conv[0].out_channels), int(field.audio_att_net.dim_aud))
+    ave = _is_ave(field)
+    params = _module_params_ave(field) if ave else _module_params(field)
     # arrival counter of the forward's eight workgroups: one word per network (the universal and the personalised
     # field's branches run on different streams at the same time), zero between launches
     # (and per stream: frames streamed through several lanes at once must not share it either)
@@ -145,7 +256,15 @@ def frame_codes(field, a, e):
     if entry is not None and (handle in entry[1] or len(entry[1]) < _ARRIVAL_SLOTS):
         slot = entry[1].setdefault(handle, len(entry[1]))
         arrivals = entry[0][slot:slot + 1]
+    elif ave:
+        arrivals = None                         # no word this call can own: the single-workgroup forward needs none
     else:
         arrivals = torch.zeros(1, dtype=torch.int32, device=a.device)      # owned by this call (and its capture) only
-    enc_a, enc_e = _FrameCodes.apply(a, None if e is None else e.reshape(-1), dims, arrivals, *params)
+    e_flat = None if e is None else e.reshape(-1)
+    if ave:
+        enc_a, enc_e = _FrameCodesAve.apply(a.reshape(8, 512), e_flat, int(field.audio_att_net.dim_aud), arrivals,
+                                            *params)
+    else:
+        dims = (int(a.shape[1]), int(field.audio_net.encoder_conv[0].out_channels), int(field.audio_att_net.dim_aud))
+        enc_a, enc_e = _FrameCodes.apply(a, e_flat, dims, arrivals, *params)
     return enc_a, (enc_e if e is not None else None)

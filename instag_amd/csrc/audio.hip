@@ -129,14 +129,14 @@ __device__ __forceinline__ void conv_forward(const float* x, const float* w, con
   }
 }
 
-// g_out holds d(pre-activation) of the layer's output.  Writes dW, dbias to global and, when g_in != nullptr,
+// g_out holds d(pre-activation) of the layer's output.  Writes dW, dbias to global (each unless nullptr) and, when g_in != nullptr,
 // d(pre-activation) of the layer's input (x is a leaky output when in_act) or the plain input gradient.
 template <int K, int STRIDE>
 __device__ __forceinline__ void conv_backward(const float* x, const float* g_out, const float* w, float* __restrict__ dW,
                                               float* __restrict__ dbias, float* g_in, int B, int cin, int cout, int lin,
                                               int lout, bool in_act) {
   constexpr int PAD = K == 3 ? 1 : 0;
-  const int nW = cout * cin * K;
+  const int nW = dW ? cout * cin * K : 0;
   const int nB = dbias ? cout : 0;
   const int nI = g_in ? B * cin * lin : 0;
   for (int idx = threadIdx.x; idx < nW + nB + nI; idx += FT) {
@@ -594,6 +594,375 @@ inline bool dims_ok(int D, int M, int A) {
   return (size_t)(2 * L.end - L.a1 + 4 + weight_stage_floats(D, M, A)) * sizeof(float) <= 160u * 1024u;
 }
 
+// ---- the 'ave' extractor ---------------------------------------------------------------------------------------
+// AudioNet_ave (scene/motion_net.py:132-149) is three linear layers 512 -> 256 -> 128 -> A (LeakyReLU after the first
+// two) on the eight windows a [8][512]; AudioAttNet and the expression MLP follow unchanged.  The first weight alone is
+// 512 KB: nothing is staged through LDS here.  A WAVE owns an output neuron: its 64 lanes load the neuron's row
+// straight into registers (16 bytes per lane and load), use every weight for all eight windows (the windows sit in LDS)
+// and add the 64 partial sums of each window up in a fixed butterfly, so each weight is read once per launch.
+//   forward : fc1's 256 neurons are split over the workgroups of the launch; the last one to arrive (the arrival
+//             protocol of frame_code_forward_split_kernel) runs fc2, fc3, the attention stage and the expression MLP.
+//             A launch of ONE workgroup does everything and needs no arrival word.
+//   backward: every workgroup repeats the small tail (attention, fc3, down to d z2), then takes ITS 16 fc1 neurons back
+//             through fc2 and writes its rows of dW1 = dZ1^T a, db1 and its rows of dW2, db2: disjoint slices, eight-term
+//             sums in window order, no workspace, no reduce launch.  Workgroup 0 writes the other gradients.
+constexpr int AVE_IN = 512, AVE_H1 = 256, AVE_H2 = 128;
+constexpr int AVE_WG = 16;        // workgroups of the split passes
+constexpr int AVE_NPARAM = 20;
+constexpr int AVE_WAVES = FT / 64;
+
+struct AveDims { int A, has_exp; };
+struct AveParamPtrs { const float* p[AVE_NPARAM]; };
+struct AveGradPtrs { float* p[AVE_NPARAM]; };
+
+// float offsets inside the saved block (and its LDS copy): z1 [8][256], z2 [8][128] (both after their LeakyReLU),
+// f2 [8][A], then FrameLayout's xt .. eh
+struct AveLayout { int z1, z2, f2, att, end; };
+__host__ __device__ inline AveLayout ave_layout(int A) {
+  const FrameLayout L = frame_layout(1, 1, A);
+  AveLayout Y;
+  Y.z1 = 0;
+  Y.z2 = Y.z1 + NB * AVE_H1;
+  Y.f2 = Y.z2 + NB * AVE_H2;
+  Y.att = Y.f2 + NB * A;
+  Y.end = Y.att + (L.end - L.xt);
+  return Y;
+}
+
+inline size_t ave_forward_floats(int A) { return (size_t)NB * AVE_IN + ave_layout(A).end + att_floats(A) + 4; }
+inline size_t ave_backward_floats(int A) {
+  return (size_t)NB * AVE_IN + 2 * (size_t)ave_layout(A).end + (size_t)A * AVE_H2 + att_floats(A) + 2 * NB * 16;
+}
+inline bool ave_dims_ok(int A) {
+  return A >= 1 && ave_backward_floats(A) * sizeof(float) <= 160u * 1024u &&
+         ave_forward_floats(A) * sizeof(float) <= 160u * 1024u;
+}
+
+// sum_k row[k] * x[w][k] (k < K) for the window w = lane >> 3, in every lane.  x [8][K] lives in LDS (16-byte aligned);
+// `vec`: row is 16-byte aligned.  A lane multiplies its K / 64 weights with all eight windows, then the eight partial
+// sums per lane are folded: three exchange steps that halve the windows a lane holds, three plain steps.
+template <int K>
+__device__ __forceinline__ float wave_dot8(const float* __restrict__ row, bool vec, const float* x, int lane) {
+  constexpr int V = K >= 256 ? 4 : 2;         // consecutive floats per lane and chunk
+  constexpr int NC = K / (64 * V);
+  float w[NC][V];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const float* src = row + c * 64 * V + lane * V;
+    if (vec) {
+      if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(src);
+        w[c][0] = t.x; w[c][1] = t.y; w[c][2] = t.z; w[c][3] = t.w;
+      } else {
+        const float2 t = *reinterpret_cast<const float2*>(src);
+        w[c][0] = t.x; w[c][1] = t.y;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) w[c][j] = src[j];
+    }
+  }
+  float acc[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    float s0 = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const float* xs = x + b * K + c * 64 * V + lane * V;
+      if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(xs);
+        s0 += w[c][0] * t.x; s0 += w[c][1] * t.y; s0 += w[c][2] * t.z; s0 += w[c][3] * t.w;
+      } else {
+        const float2 t = *reinterpret_cast<const float2*>(xs);
+        s0 += w[c][0] * t.x; s0 += w[c][1] * t.y;
+      }
+    }
+    acc[b] = s0;
+  }
+  const bool h5 = (lane & 32) != 0, h4 = (lane & 16) != 0, h3 = (lane & 8) != 0;
+  float u[4], t2[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) u[i] = (h5 ? acc[4 + i] : acc[i]) + __shfl_xor(h5 ? acc[i] : acc[4 + i], 32);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) t2[i] = (h4 ? u[2 + i] : u[i]) + __shfl_xor(h4 ? u[i] : u[2 + i], 16);
+  float r = (h3 ? t2[1] : t2[0]) + __shfl_xor(h3 ? t2[0] : t2[1], 8);
+  r += __shfl_xor(r, 4);
+  r += __shfl_xor(r, 2);
+  r += __shfl_xor(r, 1);
+  return r;
+}
+
+// vec: bit 0 / 1 / 2 = the weight of fc1 / fc2 / fc3 is 16-byte aligned
+__global__ void __launch_bounds__(FT)
+frame_code_ave_forward_kernel(AveDims d, AveParamPtrs P, const float* __restrict__ a, const float* __restrict__ e,
+                              float* __restrict__ enc_a, float* __restrict__ enc_e, float* saved, uint32_t* arrivals,
+                              int vec) {
+  extern __shared__ __align__(16) float s[];
+  const int A = d.A, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwg = gridDim.x;
+  const FrameLayout L = frame_layout(1, 1, A);
+  const AveLayout Y = ave_layout(A);
+  float* xa = s;                                // a [8][512]
+  float* act = xa + NB * AVE_IN;                // the saved block
+  float* sw = act + Y.end;                      // attention + expression weights
+  volatile uint32_t* s_ticket = reinterpret_cast<volatile uint32_t*>(sw + att_floats(A));
+  for (int i = tid; i < NB * AVE_IN; i += FT) xa[i] = a[i];
+  const AttW aw = att_layout(A);
+  {
+    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
+    for (int i = 0; i < 6; ++i) {
+      stage(sw + aw.w[i], P.p[6 + 2 * i], cout[i] * cin[i] * K[i]);
+      stage(sw + aw.b[i], P.p[7 + 2 * i], cout[i]);
+    }
+    if (d.has_exp) { stage(sw + aw.e1, P.p[18], 80); stage(sw + aw.e2, P.p[19], 80); }
+  }
+  __syncthreads();
+  // fc1: this workgroup's neurons, all eight windows
+  const int per = AVE_H1 / nwg, n0 = (int)blockIdx.x * per;
+  for (int j = wave; j < per; j += AVE_WAVES) {
+    const int n = n0 + j;
+    const float v = wave_dot8<AVE_IN>(P.p[0] + (size_t)n * AVE_IN, (vec & 1) != 0, xa, lane);
+    if ((lane & 7) == 0) {
+      const int w = lane >> 3;
+      const float z = leaky(v + P.p[1][n]);
+      saved[Y.z1 + w * AVE_H1 + n] = z;
+      if (nwg == 1) act[Y.z1 + w * AVE_H1 + n] = z;
+    }
+  }
+  if (nwg > 1) {
+    // hand-off to the last workgroup, as in frame_code_forward_split_kernel: stores drained by every wave, workgroup
+    // barrier, agent-scope release, then the arrival counter; the last ticket acquires and reads all of z1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      *s_ticket = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (*s_ticket != (uint32_t)nwg - 1u) return;
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      *arrivals = 0u;                          // ready for the next launch (stream-ordered behind this one)
+    }
+    __syncthreads();
+    for (int i = tid; i < NB * AVE_H1; i += FT) act[Y.z1 + i] = saved[Y.z1 + i];
+  }
+  __syncthreads();
+  for (int j = wave; j < AVE_H2; j += AVE_WAVES) {
+    const float v = wave_dot8<AVE_H1>(P.p[2] + (size_t)j * AVE_H1, (vec & 2) != 0, act + Y.z1, lane);
+    if ((lane & 7) == 0) act[Y.z2 + (lane >> 3) * AVE_H2 + j] = leaky(v + P.p[3][j]);
+  }
+  __syncthreads();
+  for (int j = wave; j < A; j += AVE_WAVES) {
+    const float v = wave_dot8<AVE_H2>(P.p[4] + (size_t)j * AVE_H2, (vec & 4) != 0, act + Y.z2, lane);
+    if ((lane & 7) == 0) act[Y.f2 + (lane >> 3) * A + j] = v + P.p[5][j];
+  }
+  __syncthreads();
+  // ---- AudioAttNet over the eight windows + the expression MLP (activations in FrameLayout order from xt on) ----
+  float* F2 = act + Y.f2;                       // [8][A]
+  float* aa = act + Y.att - L.xt;               // aa[L.<act>] for act in xt .. eh
+  for (int i = tid; i < A * NB; i += FT) {      // xt[j][t] = feat[t][j]
+    const int t = i % NB, j = i / NB;
+    aa[L.xt + i] = F2[t * A + j];
+  }
+  if (d.has_exp && tid >= FT - 16) {            // expression hidden layer on an idle part of the block
+    const int h = tid - (FT - 16);
+    float acc = 0.f;
+    for (int i = 0; i < 5; ++i) acc += sw[aw.e1 + h * 5 + i] * e[i];
+    aa[L.eh + h] = fmaxf(acc, 0.f);
+  }
+  __syncthreads();
+  conv_forward<3, 1>(aa + L.xt, sw + aw.w[0], sw + aw.b[0], aa + L.c1, 1, A, 16, NB, NB, true);  __syncthreads();
+  conv_forward<3, 1>(aa + L.c1, sw + aw.w[1], sw + aw.b[1], aa + L.c2, 1, 16, 8, NB, NB, true);  __syncthreads();
+  conv_forward<3, 1>(aa + L.c2, sw + aw.w[2], sw + aw.b[2], aa + L.c3, 1, 8, 4, NB, NB, true);   __syncthreads();
+  conv_forward<3, 1>(aa + L.c3, sw + aw.w[3], sw + aw.b[3], aa + L.c4, 1, 4, 2, NB, NB, true);   __syncthreads();
+  conv_forward<3, 1>(aa + L.c4, sw + aw.w[4], sw + aw.b[4], aa + L.c5, 1, 2, 1, NB, NB, true);   __syncthreads();
+  conv_forward<1, 1>(aa + L.c5, sw + aw.w[5], sw + aw.b[5], aa + L.z, 1, NB, NB, 1, 1, false);   __syncthreads();
+  if (tid < NB) {
+    float m = aa[L.z];
+    for (int t = 1; t < NB; ++t) m = fmaxf(m, aa[L.z + t]);
+    float sum = 0.f;
+    for (int t = 0; t < NB; ++t) sum += expf(aa[L.z + t] - m);
+    aa[L.y + tid] = expf(aa[L.z + tid] - m) / sum;
+  }
+  __syncthreads();
+  for (int j = tid; j < A; j += FT) {
+    float acc = 0.f;
+    for (int t = 0; t < NB; ++t) acc += aa[L.y + t] * F2[t * A + j];
+    enc_a[j] = acc;
+  }
+  if (d.has_exp && tid >= FT - 6) {
+    const int q = tid - (FT - 6);
+    float acc;
+    if (q < 5) {
+      acc = 0.f;
+      for (int h = 0; h < 16; ++h) acc += sw[aw.e2 + q * 16 + h] * aa[L.eh + h];
+    } else {
+      acc = e[5];
+    }
+    enc_e[q] = acc;
+  }
+  for (int i = tid; i < Y.end - Y.z2; i += FT) saved[Y.z2 + i] = act[Y.z2 + i];
+}
+
+// vec: bit 0 = the gradient of fc1's weight is 16-byte aligned
+__global__ void __launch_bounds__(FT)
+frame_code_ave_backward_kernel(AveDims d, AveParamPtrs P, AveGradPtrs G, const float* __restrict__ a,
+                               const float* __restrict__ e, const float* __restrict__ saved,
+                               const float* __restrict__ d_enc_a, const float* __restrict__ d_enc_e, int vec) {
+  static_assert(FT == 1024 && AVE_H1 / AVE_WG == 16 && AVE_H2 % AVE_WG == 0, "the thread maps below assume these");
+  extern __shared__ __align__(16) float s[];
+  const int A = d.A, tid = threadIdx.x;
+  const bool first = blockIdx.x == 0;           // writes the gradients that are the same in every workgroup
+  const FrameLayout L = frame_layout(1, 1, A);
+  const AveLayout Y = ave_layout(A);
+  float* xa = s;                                // a [8][512]
+  float* act = xa + NB * AVE_IN;                // saved activations
+  float* g = act + Y.end;                       // their gradients, same offsets
+  float* w3 = g + Y.end;                        // fc3 weight [A][128]
+  float* sw = w3 + A * AVE_H2;                  // attention + expression weights
+  float* part = sw + att_floats(A);             // [8][2][16] partial sums of d z1
+  const AttW aw = att_layout(A);
+  for (int i = tid; i < NB * AVE_IN; i += FT) xa[i] = a[i];
+  for (int i = tid; i < Y.end; i += FT) act[i] = saved[i];
+  {
+    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
+    for (int i = 0; i < 6; ++i) stage(sw + aw.w[i], P.p[6 + 2 * i], cout[i] * cin[i] * K[i]);
+    if (d.has_exp) stage(sw + aw.e2, P.p[19], 80);
+  }
+  stage(w3, P.p[4], A * AVE_H2);
+  __syncthreads();
+  const float* F2 = act + Y.f2;
+  float* gF2 = g + Y.f2;
+  const float* sa = act + Y.att - L.xt;         // sa[L.<act>], ga[L.<act>] for act in xt .. eh
+  float* ga = g + Y.att - L.xt;
+  auto G0 = [&](int i) -> float* { return first ? G.p[i] : nullptr; };
+
+  // enc_a = sum_t y[t] feat[t]: d_y, d_feat; then softmax
+  if (tid < NB) {
+    float acc = 0.f;
+    for (int j = 0; j < A; ++j) acc += d_enc_a[j] * F2[tid * A + j];
+    ga[L.y + tid] = acc;
+  }
+  for (int i = tid; i < NB * A; i += FT) gF2[i] = sa[L.y + i / A] * d_enc_a[i % A];
+  if (d.has_exp && first) {
+    // enc_e[q<5] = sum_h W2[q][h] eh[h], eh = relu(W1 e[:5]); 80 + 80 threads own one weight each
+    const int t = tid - 64;
+    if (t >= 0 && t < 80) {
+      const int q = t / 16, h = t % 16;
+      G.p[19][t] = (d_enc_e ? d_enc_e[q] : 0.f) * sa[L.eh + h];
+    } else if (t >= 80 && t < 160) {
+      const int i = (t - 80) % 5, h = (t - 80) / 5;
+      float dh = 0.f;
+      if (d_enc_e && sa[L.eh + h] > 0.f)
+        for (int q = 0; q < 5; ++q) dh += sw[aw.e2 + q * 16 + h] * d_enc_e[q];
+      G.p[18][h * 5 + i] = dh * e[i];
+    }
+  }
+  __syncthreads();
+  if (tid < NB) {
+    float dot = 0.f;
+    for (int t = 0; t < NB; ++t) dot += sa[L.y + t] * ga[L.y + t];
+    ga[L.z + tid] = sa[L.y + tid] * (ga[L.y + tid] - dot);
+  }
+  __syncthreads();
+  conv_backward<1, 1>(sa + L.c5, ga + L.z, sw + aw.w[5], G0(16), G0(17), ga + L.c5, 1, NB, NB, 1, 1, true);   __syncthreads();
+  conv_backward<3, 1>(sa + L.c4, ga + L.c5, sw + aw.w[4], G0(14), G0(15), ga + L.c4, 1, 2, 1, NB, NB, true);  __syncthreads();
+  conv_backward<3, 1>(sa + L.c3, ga + L.c4, sw + aw.w[3], G0(12), G0(13), ga + L.c3, 1, 4, 2, NB, NB, true);  __syncthreads();
+  conv_backward<3, 1>(sa + L.c2, ga + L.c3, sw + aw.w[2], G0(10), G0(11), ga + L.c2, 1, 8, 4, NB, NB, true);  __syncthreads();
+  conv_backward<3, 1>(sa + L.c1, ga + L.c2, sw + aw.w[1], G0(8), G0(9), ga + L.c1, 1, 16, 8, NB, NB, true);   __syncthreads();
+  conv_backward<3, 1>(sa + L.xt, ga + L.c1, sw + aw.w[0], G0(6), G0(7), ga + L.xt, 1, A, 16, NB, NB, false);
+  __syncthreads();
+  for (int i = tid; i < NB * A; i += FT) {      // feat[t][j] also feeds xt[j][t]
+    const int j = i % A, t = i / A;
+    gF2[i] += ga[L.xt + j * NB + t];
+  }
+  __syncthreads();
+  // fc3 (no activation behind it): dW3, db3 once, d z2 (before its LeakyReLU) in every workgroup
+  conv_backward<1, 1>(act + Y.z2, gF2, w3, G0(4), G0(5), g + Y.z2, NB, AVE_H2, A, 1, 1, true);
+  __syncthreads();
+  const float* z1 = act + Y.z1;
+  const float* gz2 = g + Y.z2;
+  // fc2: this workgroup's rows of dW2 [128][256] and db2
+  {
+    constexpr int ROWS = AVE_H2 / AVE_WG;
+    const int r0 = (int)blockIdx.x * ROWS;
+    for (int idx = tid; idx < ROWS * AVE_H1 + ROWS; idx += FT) {
+      float acc = 0.f;
+      if (idx < ROWS * AVE_H1) {
+        const int j = r0 + idx / AVE_H1, k = idx % AVE_H1;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc += gz2[b * AVE_H2 + j] * z1[b * AVE_H1 + k];
+        G.p[2][j * AVE_H1 + k] = acc;
+      } else {
+        const int j = r0 + idx - ROWS * AVE_H1;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc += gz2[b * AVE_H2 + j];
+        G.p[3][j] = acc;
+      }
+    }
+  }
+  // d z1 of this workgroup's 16 neurons: wave = (window, half of the 128 fc2 rows), lane = (quarter of the half, neuron)
+  const int n0 = (int)blockIdx.x * 16;
+  {
+    const int wave = tid >> 6, lane = tid & 63, b = wave >> 1, half = wave & 1, jq = lane >> 4, kk = lane & 15;
+    const float* w2 = P.p[2] + n0 + kk;
+    float acc = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+      const int j = half * 64 + jq * 16 + jj;
+      acc += w2[(size_t)j * AVE_H1] * gz2[b * AVE_H2 + j];
+    }
+    acc += __shfl_xor(acc, 16);
+    acc += __shfl_xor(acc, 32);
+    if (jq == 0) part[(b * 2 + half) * 16 + kk] = acc;
+  }
+  __syncthreads();
+  float* gz1 = g + Y.z1;                        // [8][16]: only this workgroup's neurons
+  if (tid < NB * 16) {
+    const int b = tid >> 4, kk = tid & 15;
+    gz1[tid] = (part[(b * 2) * 16 + kk] + part[(b * 2 + 1) * 16 + kk]) * dleaky(z1[b * AVE_H1 + n0 + kk]);
+  }
+  __syncthreads();
+  // dW1 rows n0 .. n0 + 15 (512 contiguous floats each) and db1
+  {
+    const int c = tid & 127, r = tid >> 7;
+    float4 x4[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) x4[b] = *reinterpret_cast<const float4*>(xa + b * AVE_IN + 4 * c);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int kk = r + 8 * h;
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float gv = gz1[b * 16 + kk];
+        acc.x += gv * x4[b].x; acc.y += gv * x4[b].y; acc.z += gv * x4[b].z; acc.w += gv * x4[b].w;
+      }
+      float* dst = G.p[0] + (size_t)(n0 + kk) * AVE_IN + 4 * c;
+      if (vec & 1) {
+        *reinterpret_cast<float4*>(dst) = acc;
+      } else {
+        dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z; dst[3] = acc.w;
+      }
+    }
+    if (tid < 16) {
+      float acc = 0.f;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc += gz1[b * 16 + tid];
+      G.p[1][n0 + tid] = acc;
+    }
+  }
+}
+
+inline int set_ave_lds_limit() {
+  if (int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(frame_code_ave_forward_kernel), 160 * 1024)) return rc;
+  return set_max_dynamic_lds(reinterpret_cast<const void*>(frame_code_ave_backward_kernel), 160 * 1024);
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 }  // namespace instag
 
@@ -671,6 +1040,56 @@ int instag_frame_code_backward(const float* a, const float* e, const float* cons
     return INSTAG_OK;
   }
   frame_code_backward_kernel<false><<<1, FT, lds, (hipStream_t)stream>>>(d, P, G, a, e, saved, d_enc_a, d_enc_e, nullptr);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+int64_t instag_frame_code_ave_saved_floats(int32_t dim_aud) {
+  if (!ave_dims_ok(dim_aud)) return -1;
+  return ave_layout(dim_aud).end;
+}
+
+int instag_frame_code_ave_forward(const float* a, const float* e, const float* const* params, float* enc_a,
+                                  float* enc_e, float* saved, int32_t dim_aud, uint32_t* arrivals,
+                                  instag_stream_t stream) {
+  INSTAG_REQUIRE(a && params && enc_a && saved, "frame_code_ave_forward: NULL tensor");
+  INSTAG_REQUIRE(ave_dims_ok(dim_aud), "frame_code_ave: activations do not fit the 160 KB LDS");
+  INSTAG_REQUIRE((e == nullptr) == (enc_e == nullptr), "frame_code_ave_forward: e and enc_e go together");
+  const int has_exp = e != nullptr;
+  AveParamPtrs P;
+  for (int i = 0; i < AVE_NPARAM; ++i) {
+    P.p[i] = params[i];
+    INSTAG_REQUIRE(P.p[i] || (i >= 18 && !has_exp), "frame_code_ave_forward: NULL parameter");
+  }
+  if (int rc = set_ave_lds_limit()) return rc;
+  const AveDims d{dim_aud, has_exp};
+  const int vec = (aligned16(P.p[0]) ? 1 : 0) | (aligned16(P.p[2]) ? 2 : 0) | (aligned16(P.p[4]) ? 4 : 0);
+  // with an arrival word fc1 is split over AVE_WG workgroups and the last one to arrive runs the rest
+  frame_code_ave_forward_kernel<<<arrivals ? AVE_WG : 1, FT, ave_forward_floats(dim_aud) * sizeof(float),
+                                  (hipStream_t)stream>>>(d, P, a, e, enc_a, enc_e, saved, arrivals, vec);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+size_t instag_frame_code_ave_backward_workspace_bytes(int32_t) { return 0; }
+
+int instag_frame_code_ave_backward(const float* a, const float* e, const float* const* params, const float* saved,
+                                   const float* d_enc_a, const float* d_enc_e, float* const* grads, int32_t dim_aud,
+                                   void*, size_t, instag_stream_t stream) {
+  INSTAG_REQUIRE(a && params && saved && d_enc_a && grads, "frame_code_ave_backward: NULL tensor");
+  INSTAG_REQUIRE(ave_dims_ok(dim_aud), "frame_code_ave: activations do not fit the 160 KB LDS");
+  const int has_exp = e != nullptr;
+  AveParamPtrs P;
+  AveGradPtrs G;
+  for (int i = 0; i < AVE_NPARAM; ++i) {
+    P.p[i] = params[i];
+    G.p[i] = grads[i];
+    INSTAG_REQUIRE((P.p[i] && G.p[i]) || (i >= 18 && !has_exp), "frame_code_ave_backward: NULL parameter / gradient");
+  }
+  if (int rc = set_ave_lds_limit()) return rc;
+  const AveDims d{dim_aud, has_exp};
+  frame_code_ave_backward_kernel<<<AVE_WG, FT, ave_backward_floats(dim_aud) * sizeof(float), (hipStream_t)stream>>>(
+      d, P, G, a, e, saved, d_enc_a, d_enc_e, aligned16(G.p[0]) ? 1 : 0);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }

@@ -2,7 +2,7 @@
 
 Counterpart of /root/reference/scene/motion_net.py (same module / parameter names so reference
 ``state_dict``s load unchanged):
-  AudioAttNet :29-64, AudioNet :67-99, MLP :152-173,
+  AudioAttNet :29-64, AudioNet :67-99, AudioNet_ave :132-149, MLP :152-173,
   MotionNetwork (UMF) :176-345, MouthMotionNetwork :346-478, PersonalizedMotionNetwork (PMF) :562-748.
 The tri-plane grid encoders are ``instag_amd.gridencoder.GridEncoder`` (HIP); ``encoder_cls`` lets
 the CPU tests inject the oracle encoder.  The per-Gaussian MLP chains (B = N rows) run as fused
@@ -93,6 +93,23 @@ class AudioNet(nn.Module):
         return self.encoder_fc1(self.encoder_conv(x).squeeze(-1))
 
 
+class AudioNet_ave(nn.Module):
+    """Per-frame encoder of the 512-feature 'ave' windows: three linear layers (motion_net.py:132-149)."""
+
+    def __init__(self, dim_in=29, dim_aud=64, win_size=16):
+        super().__init__()
+        self.win_size, self.dim_aud = win_size, dim_aud
+        self.encoder_fc1 = nn.Sequential(nn.Linear(512, 256), nn.LeakyReLU(0.02, True), nn.Linear(256, 128),
+                                         nn.LeakyReLU(0.02, True), nn.Linear(128, dim_aud))
+
+    def forward(self, x):                       # x: [8, 1, 512]
+        return self.encoder_fc1(x).permute(1, 0, 2).squeeze(0)
+
+
+def _audio_net(audio_extractor, dim_in, dim_aud):
+    return (AudioNet_ave if audio_extractor == "ave" else AudioNet)(dim_in, dim_aud)
+
+
 class MLP(nn.Module):
     """Bias-free ReLU MLP (motion_net.py:152-173)."""
 
@@ -135,9 +152,7 @@ class _TriPlaneField(nn.Module):
         if ind_dim > 0:
             self.individual_codes = nn.Parameter(torch.randn(10000, ind_dim) * 0.1)
         self.audio_dim = audio_dim
-        if audio_extractor == "ave":
-            raise NotImplementedError("the 'ave' audio extractor is outside the accelerated path")
-        self.audio_net = AudioNet(self.audio_in_dim, audio_dim)
+        self.audio_net = _audio_net(audio_extractor, self.audio_in_dim, audio_dim)
         self.audio_att_net = AudioAttNet(audio_dim)
         self.num_levels, self.level_dim = 12, 1
         enc = dict(input_dim=2, num_levels=self.num_levels, level_dim=self.level_dim, base_resolution=16,
@@ -393,9 +408,7 @@ class MouthMotionNetwork(nn.Module):
         if ind_dim > 0:
             self.individual_codes = nn.Parameter(torch.randn(10000, ind_dim) * 0.1)
         self.audio_dim = audio_dim
-        if args.audio_extractor == "ave":
-            raise NotImplementedError("the 'ave' audio extractor is outside the accelerated path")
-        self.audio_net = AudioNet(self.audio_in_dim, audio_dim)
+        self.audio_net = _audio_net(args.audio_extractor, self.audio_in_dim, audio_dim)
         self.audio_att_net = AudioAttNet(audio_dim)
         self.num_levels, self.level_dim = 12, 1
         enc = dict(input_dim=2, num_levels=self.num_levels, level_dim=self.level_dim, base_resolution=64,

@@ -592,13 +592,13 @@ class _PretrainGraph(graphs.CapturedStep):
 
 
 def build_pretrainer(K: int, n_gaussians: int, device, sh_degree: int = 1, seed: int = 0, opt=OptimizationParams,
-                     densify: bool = False) -> PretrainFaceTrainer:
+                     densify: bool = False, audio_extractor: str = "deepspeech") -> PretrainFaceTrainer:
     """Synthetic K-identity pretrainer: K clouds of n_gaussians (different seeds) with their PMFs, one UMF."""
     from types import SimpleNamespace
     from .motion_net import MotionNetwork, PersonalizedMotionNetwork
     from .scene_synth import synthetic_gaussians
     torch.manual_seed(seed)
-    args = SimpleNamespace(audio_extractor="deepspeech", type="face")
+    args = SimpleNamespace(audio_extractor=audio_extractor, type="face")
     ids = []
     for k in range(K):
         pmf = PersonalizedMotionNetwork(args=args).to(device)
@@ -611,15 +611,16 @@ def build_pretrainer(K: int, n_gaussians: int, device, sh_degree: int = 1, seed:
 
 
 def build_mouth_pretrainer(K: int, n_mouth: int, n_face: int, device, sh_degree: int = 1, seed: int = 0,
-                           opt=OptimizationParams, densify: bool = False, fused_deform: bool = True) -> PretrainMouthTrainer:
+                           opt=OptimizationParams, densify: bool = False, fused_deform: bool = True,
+                           audio_extractor: str = "deepspeech") -> PretrainMouthTrainer:
     """Synthetic K-identity mouth pretrainer: K mouth clouds of n_mouth Gaussians (different seeds, centred on the lips)
     with their mouth-type PMFs, K frozen face clouds of n_face with a frozen face UMF, one MouthMotionNetwork."""
     from types import SimpleNamespace
     from .motion_net import MotionNetwork, MouthMotionNetwork, PersonalizedMotionNetwork
     from .scene_synth import synthetic_gaussians
     torch.manual_seed(seed)
-    face_args = SimpleNamespace(audio_extractor="deepspeech", type="face")
-    mouth_args = SimpleNamespace(audio_extractor="deepspeech", type="mouth")
+    face_args = SimpleNamespace(audio_extractor=audio_extractor, type="face")
+    mouth_args = SimpleNamespace(audio_extractor=audio_extractor, type="mouth")
     ids, faces = [], []
     for k in range(K):
         g = GaussianModel(sh_degree, neural_motion_grid=PersonalizedMotionNetwork(args=mouth_args).to(device))

@@ -918,12 +918,13 @@ class GraphedStep(graphs.CapturedStep):
             self.graph_b.replay()
 
 
-def build_trainer(n_gaussians, device, sh_degree=1, seed=0, densify=False, encoder_cls=None, raw=None, schedule=None):
+def build_trainer(n_gaussians, device, sh_degree=1, seed=0, densify=False, encoder_cls=None, raw=None, schedule=None,
+                  audio_extractor="deepspeech"):
     """Synthetic config-C3 trainer: N Gaussians + PMF + UMF with random-init weights."""
     from .motion_net import MotionNetwork, PersonalizedMotionNetwork
     from .scene_synth import synthetic_gaussians
     torch.manual_seed(seed)
-    args = SimpleNamespace(audio_extractor="deepspeech", type="face")
+    args = SimpleNamespace(audio_extractor=audio_extractor, type="face")
     pmf = PersonalizedMotionNetwork(args=args, encoder_cls=encoder_cls).to(device)
     umf = MotionNetwork(args=args, encoder_cls=encoder_cls).to(device)
     g = GaussianModel(sh_degree, neural_motion_grid=pmf)
