@@ -748,6 +748,33 @@ int instag_lpips_backward(const instag_lpips_weights* w, const int32_t* p_dev, i
                           instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AudioEncoder of the 'ave' audio extractor (csrc/ave_encoder.hip): scene/motion_net.py:8-25, 102-129 in
+ * eval mode, as scene/dataset_readers.py:111-142 runs it over the mel windows of a wav.  fp32, forward only.
+ *
+ *  Thirteen blocks relu(scale * conv_nobias(x) + shift [+ x]); scale / shift are BatchNorm (eval) and
+ *  the convolution bias folded per channel by the caller.
+ *  weights: w[0] = layer 0's weight as stored [32][9]; w[l >= 1] = [K = cin * kh * kw][cout] with
+ *    k = (cin, ky, kx); scale[l], shift[l] = [cout].
+ *  mel [T,80] with starts_dev [n] (device int32): window i is mel[starts[i] : starts[i] + 16, :]
+ *    transposed to [80,16], read in place (utils/audio_utils.py:130-155).  starts_dev == NULL: `mel`
+ *    is a stack of n windows [n,1,80,16] and T is not read.
+ *  out [n,512].  n <= instag_ave_encoder_max_batch(); the workspace (instag_ave_encoder_workspace_bytes(batch),
+ *    batch >= n; 0 = bad argument) holds the two activation buffers; the caller loops over chunks.
+ *  No atomics, a fixed K order: a window's row does not depend on the batch it sat in, and repeated
+ *  runs give the same bits.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_ave_encoder_weights {
+  const float* w[13];
+  const float* scale[13];
+  const float* shift[13];
+} instag_ave_encoder_weights;
+int instag_ave_encoder_max_batch(void);
+size_t instag_ave_encoder_workspace_bytes(int32_t batch);
+int instag_ave_encoder_forward(const instag_ave_encoder_weights* w, const float* mel, int32_t T,
+                               const int32_t* starts_dev, int32_t n, float* out, void* workspace,
+                               size_t workspace_bytes, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluation (csrc/metrics.hip): frame metrics and the inference epilogue.  Forward only.
  *
  * frame_metrics: pred, gt [B,3,H,W] fp32.  flags bit 0: pred is clamped to [0,1] first; bit 1: pred and

@@ -34,6 +34,11 @@ class LpipsWeights(C.Structure):
     _fields_ = [("wf", vp * 5), ("bias", vp * 5), ("wb", vp * 5), ("lin", vp * 5)]
 
 
+class AveEncoderWeights(C.Structure):
+    """struct instag_ave_encoder_weights (include/instag_hip.h)."""
+    _fields_ = [("w", vp * 13), ("scale", vp * 13), ("shift", vp * 13)]
+
+
 class WgradJob(C.Structure):
     """struct instag_wgrad_job (include/instag_hip.h)."""
     _fields_ = [("dz", vp), ("inp", vp), ("dw", vp), ("N", i32), ("O", i32), ("K", i32)]
@@ -320,6 +325,9 @@ _PROTOS = {
                                        vp, vp, vp]),
     "instag_lpips_backward": (C.c_int, [C.POINTER(LpipsWeights), vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz,
                                         vp, vp]),
+    "instag_ave_encoder_max_batch": (C.c_int, []),
+    "instag_ave_encoder_workspace_bytes": (sz, [i32]),
+    "instag_ave_encoder_forward": (C.c_int, [C.POINTER(AveEncoderWeights), vp, i32, vp, i32, vp, vp, sz, vp]),
     "instag_frame_metrics_num_partials": (C.c_int64, [i32, i32, i32]),
     "instag_frame_metrics": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "instag_meter_add": (C.c_int, [vp, i32, vp, vp]),

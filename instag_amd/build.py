@@ -48,6 +48,7 @@ SOURCES = {
     "pretrain.hip": ["-ffp-contract=off"],
     "lpips.hip": [],
     "metrics.hip": [],
+    "ave_encoder.hip": [],
 }
 
 
