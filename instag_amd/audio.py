@@ -30,27 +30,44 @@ def _ptr_array(tensors):
 
 SPLIT_BACKWARD = True        # False: the single-workgroup backward kernel (tests compare the two)
 
+
+class _Variant:
+    """What tells the two kernel families apart on this side: the C symbols instag_<name>_{saved_floats, forward,
+    backward_workspace_bytes, backward}, which take the same arguments but for the integer dimensions (`dims`, dim_aud
+    last), and whether the backward pass can use a workspace."""
+
+    def __init__(self, name, workspace):
+        self.name, self.workspace = name, workspace
+
+    def symbol(self, what):
+        return getattr(_lib.lib(), f"instag_{self.name}_{what}")
+
+
+_STOCK = _Variant("frame_code", True)          # AudioNet: a [8, dim_in, 16], dims (dim_in, mid, dim_aud), 26 parameters
+_AVE = _Variant("frame_code_ave", False)       # AudioNet_ave: a [8, 512], dims (dim_aud,), 20 parameters
+
+
 class _FrameCodes(torch.autograd.Function):
+    """`arrivals` None = the single-workgroup forward."""
+
     @staticmethod
-    def forward(ctx, a, e, dims, arrivals, *params):
-        L = _lib.lib()
-        dim_in, mid, dim_aud = dims
+    def forward(ctx, a, e, variant, dims, arrivals, *params):
         a = a.contiguous().float()
         params = tuple(None if p is None else p.contiguous() for p in params)
         dev = a.device
-        n_saved = L.instag_frame_code_saved_floats(dim_in, mid, dim_aud)
+        n_saved = variant.symbol("saved_floats")(*dims)
         if n_saved < 0:
             raise RuntimeError("frame_codes: unsupported dimensions")
-        enc_a = torch.empty(1, dim_aud, dtype=torch.float32, device=dev)
+        enc_a = torch.empty(1, dims[-1], dtype=torch.float32, device=dev)
         enc_e = None
         if e is not None:
             e = e.contiguous().float()
             enc_e = torch.empty(6, dtype=torch.float32, device=dev)
         saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
-        check(L.instag_frame_code_forward(ptr(a), ptr(e), _ptr_array(params), ptr(enc_a), ptr(enc_e), ptr(saved),
-                                          dim_in, mid, dim_aud, ptr(arrivals), _lib.current_stream()),
-              "frame_code_forward")
-        ctx.dims = dims
+        check(variant.symbol("forward")(ptr(a), ptr(e), _ptr_array(params), ptr(enc_a), ptr(enc_e), ptr(saved), *dims,
+                                        ptr(arrivals), _lib.current_stream()),
+              variant.name + "_forward")
+        ctx.variant, ctx.dims = variant, dims
         ctx.has_e = e is not None
         ctx.save_for_backward(a, saved, *( [e] if e is not None else [] ), *[p for p in params if p is not None])
         ctx.param_mask = [p is not None for p in params]
@@ -60,76 +77,26 @@ class _FrameCodes(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_enc_a, d_enc_e):
-        L = _lib.lib()
-        dim_in, mid, dim_aud = ctx.dims
+        variant, dims = ctx.variant, ctx.dims
         tensors = list(ctx.saved_tensors)
         a, saved = tensors[0], tensors[1]
         e = tensors[2] if ctx.has_e else None
         rest = iter(tensors[3 if ctx.has_e else 2:])
         params = [next(rest) if m else None for m in ctx.param_mask]
         if d_enc_a is None:
-            d_enc_a = torch.zeros(1, dim_aud, dtype=torch.float32, device=a.device)
+            d_enc_a = torch.zeros(1, dims[-1], dtype=torch.float32, device=a.device)
         d_enc_a = d_enc_a.contiguous().float()
         d_enc_e = d_enc_e.contiguous().float() if (ctx.has_e and d_enc_e is not None) else None
         grads = [None if p is None else torch.empty_like(p) for p in params]
-        # eight workgroups (one per audio window), each with its own row of parameter gradients in `ws`
-        ws = torch.empty(L.instag_frame_code_backward_workspace_bytes(dim_in, mid, dim_aud), dtype=torch.uint8,
-                         device=a.device) if SPLIT_BACKWARD else None
-        check(L.instag_frame_code_backward(ptr(a), ptr(e), _ptr_array(params), ptr(saved), ptr(d_enc_a), ptr(d_enc_e),
-                                           _ptr_array(grads), dim_in, mid, dim_aud, ptr(ws),
-                                           0 if ws is None else ws.numel(), _lib.current_stream()),
-              "frame_code_backward")
-        return (None, None, None, None, *grads)
-
-
-class _FrameCodesAve(torch.autograd.Function):
-    """_FrameCodes for AudioNet_ave: a [8, 512], 20 parameters, `arrivals` None = the single-workgroup forward."""
-
-    @staticmethod
-    def forward(ctx, a, e, dim_aud, arrivals, *params):
-        L = _lib.lib()
-        a = a.contiguous().float()
-        params = tuple(None if p is None else p.contiguous() for p in params)
-        dev = a.device
-        n_saved = L.instag_frame_code_ave_saved_floats(dim_aud)
-        if n_saved < 0:
-            raise RuntimeError("frame_codes: unsupported dimensions")
-        enc_a = torch.empty(1, dim_aud, dtype=torch.float32, device=dev)
-        enc_e = None
-        if e is not None:
-            e = e.contiguous().float()
-            enc_e = torch.empty(6, dtype=torch.float32, device=dev)
-        saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
-        check(L.instag_frame_code_ave_forward(ptr(a), ptr(e), _ptr_array(params), ptr(enc_a), ptr(enc_e), ptr(saved),
-                                              dim_aud, ptr(arrivals), _lib.current_stream()),
-              "frame_code_ave_forward")
-        ctx.dim_aud = dim_aud
-        ctx.has_e = e is not None
-        ctx.save_for_backward(a, saved, *( [e] if e is not None else [] ), *[p for p in params if p is not None])
-        ctx.param_mask = [p is not None for p in params]
-        if enc_e is None:
-            return enc_a, torch.empty(0, device=dev)
-        return enc_a, enc_e
-
-    @staticmethod
-    def backward(ctx, d_enc_a, d_enc_e):
-        L = _lib.lib()
-        tensors = list(ctx.saved_tensors)
-        a, saved = tensors[0], tensors[1]
-        e = tensors[2] if ctx.has_e else None
-        rest = iter(tensors[3 if ctx.has_e else 2:])
-        params = [next(rest) if m else None for m in ctx.param_mask]
-        if d_enc_a is None:
-            d_enc_a = torch.zeros(1, ctx.dim_aud, dtype=torch.float32, device=a.device)
-        d_enc_a = d_enc_a.contiguous().float()
-        d_enc_e = d_enc_e.contiguous().float() if (ctx.has_e and d_enc_e is not None) else None
-        grads = [None if p is None else torch.empty_like(p) for p in params]
-        # sixteen workgroups write disjoint rows of the two large weight gradients: no workspace
-        check(L.instag_frame_code_ave_backward(ptr(a), ptr(e), _ptr_array(params), ptr(saved), ptr(d_enc_a),
-                                               ptr(d_enc_e), _ptr_array(grads), ctx.dim_aud, None, 0,
-                                               _lib.current_stream()),
-              "frame_code_ave_backward")
-        return (None, None, None, None, *grads)
+        # stock: eight workgroups (one per audio window), each with its own row of parameter gradients in `ws`;
+        # 'ave': sixteen workgroups write disjoint rows of the two large weight gradients, no workspace
+        ws = torch.empty(variant.symbol("backward_workspace_bytes")(*dims), dtype=torch.uint8,
+                         device=a.device) if (variant.workspace and SPLIT_BACKWARD) else None
+        check(variant.symbol("backward")(ptr(a), ptr(e), _ptr_array(params), ptr(saved), ptr(d_enc_a), ptr(d_enc_e),
+                                         _ptr_array(grads), *dims, ptr(ws), 0 if ws is None else ws.numel(),
+                                         _lib.current_stream()),
+              variant.name + "_backward")
+        return (None, None, None, None, None, *grads)
 
 
 def _attention_params(field):
@@ -186,34 +153,26 @@ def _module_params_ave(field):
 
 def _module_params(field):
     """The 26 parameters in the C ABI's order, or None when the modules are not the stock architecture."""
-    an, att = field.audio_net, field.audio_att_net
+    an = field.audio_net
     try:
         convs = [an.encoder_conv[i] for i in (0, 2, 4, 6)]
         fcs = [an.encoder_fc1[i] for i in (0, 2)]
-        aconvs = [att.attentionConvNet[i] for i in (0, 2, 4, 6, 8)]
-        lin = att.attentionNet[0]
     except (IndexError, AttributeError, TypeError):
+        return None
+    tail = _attention_params(field)
+    if tail is None:
         return None
     mid = convs[0].out_channels
     chans = [(c.in_channels, c.out_channels) for c in convs]
     if chans != [(an.encoder_conv[0].in_channels, mid), (mid, mid), (mid, 64), (64, 64)]:
         return None
-    if [(c.in_channels, c.out_channels) for c in aconvs] != [(att.dim_aud, 16), (16, 8), (8, 4), (4, 2), (2, 1)]:
-        return None
-    if att.seq_len != 8 or an.win_size != 16 or fcs[0].in_features != 64 or fcs[0].out_features != 64 \
-            or fcs[1].out_features != att.dim_aud or any(m.bias is None for m in convs + fcs + aconvs + [lin]):
+    if an.win_size != 16 or fcs[0].in_features != 64 or fcs[0].out_features != 64 \
+            or fcs[1].out_features != field.audio_att_net.dim_aud or any(m.bias is None for m in convs + fcs):
         return None
     out = []
-    for m in convs + fcs + aconvs + [lin]:
+    for m in convs + fcs:
         out += [m.weight, m.bias]
-    if getattr(field, "exp_eye", False):
-        net = field.exp_encode_net.net
-        if len(net) != 2 or tuple(net[0].weight.shape) != (16, 5) or tuple(net[1].weight.shape) != (5, 16):
-            return None
-        out += [net[0].weight, net[1].weight]
-    else:
-        out += [None, None]
-    return out
+    return out + tail
 
 
 def supported(field, a, e) -> bool:
@@ -262,9 +221,9 @@ def frame_codes(field, a, e):
         arrivals = torch.zeros(1, dtype=torch.int32, device=a.device)      # owned by this call (and its capture) only
     e_flat = None if e is None else e.reshape(-1)
     if ave:
-        enc_a, enc_e = _FrameCodesAve.apply(a.reshape(8, 512), e_flat, int(field.audio_att_net.dim_aud), arrivals,
-                                            *params)
+        enc_a, enc_e = _FrameCodes.apply(a.reshape(8, 512), e_flat, _AVE, (int(field.audio_att_net.dim_aud),), arrivals,
+                                         *params)
     else:
         dims = (int(a.shape[1]), int(field.audio_net.encoder_conv[0].out_channels), int(field.audio_att_net.dim_aud))
-        enc_a, enc_e = _FrameCodes.apply(a, e_flat, dims, arrivals, *params)
+        enc_a, enc_e = _FrameCodes.apply(a, e_flat, _STOCK, dims, arrivals, *params)
     return enc_a, (enc_e if e is not None else None)

@@ -10,6 +10,13 @@
 //   attention (B=1, channels = A features, length = 8 windows): conv k3 s1 p1 A->16->8->4->2->1 (leaky each),
 //   linear 8->8, softmax, enc_a = sum_t y[t] * feat[t]
 //   expression: relu(W1[16x5] e[:5]), W2[5x16], enc_e = (.., e[5])
+//
+// Two kernel families share that tail: the stock AudioNet (frame_code_*) and AudioNet_ave (frame_code_ave_*, below).
+// Their front parts are different algorithms and stay apart; everything behind the feature block [8][A] exists once:
+//   att_layer / att_layout / stage_attention  the attention layer table, its LDS segments and their staging
+//   attention_forward<T, SPLIT_CONV>          AudioAttNet + expression MLP forward (all three forward kernels)
+//   attention_backward                        their backward (both backward kernels)
+//   last_to_arrive                            the hand-off of a split forward to its last workgroup
 #include "common.hpp"
 
 namespace instag {
@@ -60,7 +67,31 @@ __device__ __forceinline__ float dleaky(float post) { return post > 0.f ? 1.f : 
 // Weights are staged into LDS one layer group at a time (coalesced 16-byte loads, all issued before the first
 // wait): a MAC loop that reads its weight from global memory pays one L2 round trip per iteration.
 // Groups: 0 conv1, 1 conv2, 2 conv3, 3 conv4, 4 fc1+fc2, 5 attention convs + linear + expression MLP.
-__host__ __device__ inline int att_floats(int A) { return 48 * A + 784; }   // segments padded to 4 floats
+// The attention stage's layers: five k3 s1 p1 convolutions A -> 16 -> 8 -> 4 -> 2 -> 1 over the eight windows and the
+// 8 x 8 linear layer (K = 1).  The only copy of this table: the segment offsets, the staging and both passes read it.
+constexpr int NATT = 6;
+struct AttLayer { int cin, cout, K; };
+__host__ __device__ inline AttLayer att_layer(int i, int A) {
+  const AttLayer t[NATT] = {{A, 16, 3}, {16, 8, 3}, {8, 4, 3}, {4, 2, 3}, {2, 1, 3}, {NB, NB, 1}};
+  return t[i];
+}
+
+// offsets of the group-5 segments inside the staging buffer (segments padded to 4 floats)
+struct AttW { int w[NATT], b[NATT], e1, e2, end; };
+__host__ __device__ inline AttW att_layout(int A) {
+  AttW o;
+  int p = 0;
+  for (int i = 0; i < NATT; ++i) {
+    const AttLayer l = att_layer(i, A);
+    o.w[i] = p; p += (l.cout * l.cin * l.K + 3) & ~3;
+    o.b[i] = p; p += (l.cout + 3) & ~3;
+  }
+  o.e1 = p; p += 80;
+  o.e2 = p; p += 80;
+  o.end = p;
+  return o;
+}
+__host__ __device__ inline int att_floats(int A) { return att_layout(A).end + 4; }   // 48 A + 784: four spare floats
 __host__ __device__ inline int weight_stage_floats(int D, int M, int A) {
   int m = M * D * 3 + M;
   m = max(m, M * M * 3 + M);
@@ -71,32 +102,36 @@ __host__ __device__ inline int weight_stage_floats(int D, int M, int A) {
   return (m + 3) & ~3;
 }
 
+// T = threads of the workgroup
+template <int T>
 __device__ __forceinline__ void stage(float* dst, const float* __restrict__ src, int n) {
   if (src == nullptr) return;
   if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
     const float4* s4 = reinterpret_cast<const float4*>(src);
     float4* d4 = reinterpret_cast<float4*>(dst);
 #pragma unroll 4
-    for (int i = threadIdx.x; i < n / 4; i += FT) d4[i] = s4[i];
+    for (int i = threadIdx.x; i < n / 4; i += T) d4[i] = s4[i];
   } else {
 #pragma unroll 4
-    for (int i = threadIdx.x; i < n; i += FT) dst[i] = src[i];
+    for (int i = threadIdx.x; i < n; i += T) dst[i] = src[i];
   }
 }
 
-// offsets of the group-5 segments inside the staging buffer
-struct AttW { int w[6], b[6], e1, e2; };
-__device__ __forceinline__ AttW att_layout(int A) {
-  AttW o;
-  const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
-  int p = 0;
-  for (int i = 0; i < 6; ++i) {
-    o.w[i] = p; p += (cout[i] * cin[i] * K[i] + 3) & ~3;
-    o.b[i] = p; p += (cout[i] + 3) & ~3;
+// Group 5 into dst: p = the stage's 14 parameters (six weight, bias pairs, then the two expression weights).
+// weights_only: the backward kernels need the six weights and e2 and load nothing else.
+template <int T>
+__device__ __forceinline__ void stage_attention(float* dst, const AttW& aw, const float* const* p, int A, bool has_exp,
+                                                bool weights_only) {
+#pragma unroll
+  for (int i = 0; i < NATT; ++i) {
+    const AttLayer l = att_layer(i, A);
+    stage<T>(dst + aw.w[i], p[2 * i], l.cout * l.cin * l.K);
+    if (!weights_only) stage<T>(dst + aw.b[i], p[2 * i + 1], l.cout);
   }
-  o.e1 = p; p += 80;
-  o.e2 = p;
-  return o;
+  if (has_exp) {
+    if (!weights_only) stage<T>(dst + aw.e1, p[12], 80);
+    stage<T>(dst + aw.e2, p[13], 80);
+  }
 }
 
 // y[b][co][l] = act(bias[co] + sum_{ci,k} w[co][ci][k] * x[b][ci][STRIDE*l + k - pad]); K = 1 is a linear layer.
@@ -187,101 +222,10 @@ __device__ __forceinline__ void conv_backward(const float* x, const float* g_out
   }
 }
 
-__global__ void __launch_bounds__(FT)
-frame_code_forward_kernel(FrameDims d, ParamPtrs P, const float* __restrict__ a, const float* __restrict__ e,
-                          float* __restrict__ enc_a, float* __restrict__ enc_e, float* __restrict__ saved) {
-  extern __shared__ __align__(16) float s[];
-  const FrameLayout L = frame_layout(d.D, d.M, d.A);
-  float* sw = s + ((L.end + 3) & ~3);            // weight staging buffer
-  const int D = d.D, M = d.M, A = d.A;
-  for (int i = threadIdx.x; i < NB * D * WIN; i += FT) s[L.x0 + i] = a[i];
-  stage(sw, P.p[0], M * D * 3); stage(sw + M * D * 3, P.p[1], M);
-  __syncthreads();
-  conv_forward<3, 2>(s + L.x0, sw, sw + M * D * 3, s + L.a1, NB, D, M, 16, 8, true);
-  __syncthreads();
-  stage(sw, P.p[2], M * M * 3); stage(sw + M * M * 3, P.p[3], M);
-  __syncthreads();
-  conv_forward<3, 2>(s + L.a1, sw, sw + M * M * 3, s + L.a2, NB, M, M, 8, 4, true);
-  __syncthreads();
-  stage(sw, P.p[4], 64 * M * 3); stage(sw + 64 * M * 3, P.p[5], 64);
-  __syncthreads();
-  conv_forward<3, 2>(s + L.a2, sw, sw + 64 * M * 3, s + L.a3, NB, M, 64, 4, 2, true);
-  __syncthreads();
-  stage(sw, P.p[6], 64 * 64 * 3); stage(sw + 64 * 64 * 3, P.p[7], 64);
-  __syncthreads();
-  conv_forward<3, 2>(s + L.a3, sw, sw + 64 * 64 * 3, s + L.a4, NB, 64, 64, 2, 1, true);
-  __syncthreads();
-  stage(sw, P.p[8], 4096); stage(sw + 4096, P.p[9], 64); stage(sw + 4160, P.p[10], A * 64);
-  stage(sw + 4160 + A * 64, P.p[11], A);
-  __syncthreads();
-  conv_forward<1, 1>(s + L.a4, sw, sw + 4096, s + L.f1, NB, 64, 64, 1, 1, true);
-  __syncthreads();
-  conv_forward<1, 1>(s + L.f1, sw + 4160, sw + 4160 + A * 64, s + L.f2, NB, 64, A, 1, 1, false);
-  __syncthreads();
-  const AttW aw = att_layout(A);
-  {
-    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
-    for (int i = 0; i < 6; ++i) {
-      stage(sw + aw.w[i], P.p[12 + 2 * i], cout[i] * cin[i] * K[i]);
-      stage(sw + aw.b[i], P.p[13 + 2 * i], cout[i]);
-    }
-    if (d.has_exp) { stage(sw + aw.e1, P.p[24], 80); stage(sw + aw.e2, P.p[25], 80); }
-  }
-  for (int i = threadIdx.x; i < A * NB; i += FT) {            // xt[j][t] = feat[t][j]
-    const int t = i % NB, j = i / NB;
-    s[L.xt + i] = s[L.f2 + t * A + j];
-  }
-  __syncthreads();
-  if (d.has_exp && threadIdx.x >= FT - 16) {                     // expression hidden layer on an idle part of the block
-    const int h = threadIdx.x - (FT - 16);
-    float acc = 0.f;
-    for (int i = 0; i < 5; ++i) acc += sw[aw.e1 + h * 5 + i] * e[i];
-    s[L.eh + h] = fmaxf(acc, 0.f);
-  }
-  conv_forward<3, 1>(s + L.xt, sw + aw.w[0], sw + aw.b[0], s + L.c1, 1, A, 16, NB, NB, true);  __syncthreads();
-  conv_forward<3, 1>(s + L.c1, sw + aw.w[1], sw + aw.b[1], s + L.c2, 1, 16, 8, NB, NB, true);  __syncthreads();
-  conv_forward<3, 1>(s + L.c2, sw + aw.w[2], sw + aw.b[2], s + L.c3, 1, 8, 4, NB, NB, true);   __syncthreads();
-  conv_forward<3, 1>(s + L.c3, sw + aw.w[3], sw + aw.b[3], s + L.c4, 1, 4, 2, NB, NB, true);   __syncthreads();
-  conv_forward<3, 1>(s + L.c4, sw + aw.w[4], sw + aw.b[4], s + L.c5, 1, 2, 1, NB, NB, true);   __syncthreads();
-  conv_forward<1, 1>(s + L.c5, sw + aw.w[5], sw + aw.b[5], s + L.z, 1, NB, NB, 1, 1, false);   __syncthreads();
-  if (threadIdx.x < NB) {
-    float m = s[L.z];
-    for (int t = 1; t < NB; ++t) m = fmaxf(m, s[L.z + t]);
-    float sum = 0.f;
-    for (int t = 0; t < NB; ++t) sum += expf(s[L.z + t] - m);
-    s[L.y + threadIdx.x] = expf(s[L.z + threadIdx.x] - m) / sum;
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < A; j += FT) {
-    float acc = 0.f;
-    for (int t = 0; t < NB; ++t) acc += s[L.y + t] * s[L.f2 + t * A + j];
-    enc_a[j] = acc;
-  }
-  if (d.has_exp && threadIdx.x >= FT - 6) {
-    const int q = threadIdx.x - (FT - 6);
-    float acc;
-    if (q < 5) {
-      acc = 0.f;
-      for (int h = 0; h < 16; ++h) acc += sw[aw.e2 + q * 16 + h] * s[L.eh + h];
-    } else {
-      acc = e[5];
-    }
-    enc_e[q] = acc;
-  }
-  for (int i = threadIdx.x; i < L.end - L.a1; i += FT) saved[i] = s[L.a1 + i];
-}
-
+constexpr int FW = 256;           // threads per workgroup of the split forward pass
 __device__ __forceinline__ int co_of(int o, int lout) { return o / lout; }
 
-// ---- forward over NB workgroups --------------------------------------------------------------------------------
-// AudioNet's eight windows are independent (scene/motion_net.py:67-99): workgroup b runs window b through the four
-// convolutions and two linear layers with EVERY weight already in LDS (all staging loads are issued at kernel start:
-// one memory round trip instead of one per layer), the last workgroup to finish runs AudioAttNet over the eight feature
-// vectors (+ the expression MLP).  The single-workgroup form took 97 us, ~5 us per layer, almost all of it waiting
-// for the layer's weights and for barriers.
-constexpr int FW = 256;           // threads per workgroup of the forward pass
-
-// one output per group of `tpo` lanes (a power of two <= 64), each lane sums a slice of the input channels
+// conv_forward for ONE window and FW threads: one output per group of `tpo` lanes (a power of two <= 64), each lane sums a slice of the input channels
 template <int K, int STRIDE>
 __device__ __forceinline__ void conv_forward_split(const float* x, const float* w, const float* bias, float* y, int cin,
                                                    int cout, int lin, int lout, bool act) {
@@ -314,6 +258,192 @@ __device__ __forceinline__ void conv_forward_split(const float* x, const float* 
   }
 }
 
+// ---- the stages that every kernel family shares ------------------------------------------------------------------
+// Hand-off of a forward pass that is split over n workgroups: stores drained by every wave, workgroup barrier,
+// agent-scope release, then the arrival counter.  True in the workgroup that draws the last ticket: it has acquired,
+// may read what the others stored, and has zeroed the word for the next launch (stream-ordered behind this one).
+__device__ __forceinline__ bool last_to_arrive(uint32_t* arrivals, volatile uint32_t* s_ticket, uint32_t n) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    *s_ticket = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (*s_ticket != n - 1u) return false;
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    *arrivals = 0u;
+  }
+  __syncthreads();
+  return true;
+}
+
+// one attention layer forward with the caller's convolution routine: the two sum in different orders
+template <bool SPLIT_CONV, int K>
+__device__ __forceinline__ void att_conv(const float* x, const float* w, const float* bias, float* y, int cin, int cout,
+                                         int len, bool act) {
+  if constexpr (SPLIT_CONV) conv_forward_split<K, 1>(x, w, bias, y, cin, cout, len, len, act);
+  else conv_forward<K, 1>(x, w, bias, y, 1, cin, cout, len, len, act);
+}
+
+// AudioAttNet over the eight windows + the expression MLP, forward.  F2 = the feature block [8][A]; aa[L.<act>] = the
+// activations xt .. eh (FrameLayout order); wa = group 5 in LDS, laid out by aw: staged before the call, or its loads
+// issued and left to the first barrier here.  T = threads of the workgroup: FW with conv_forward_split, FT without.
+template <int T, bool SPLIT_CONV>
+__device__ __forceinline__ void attention_forward(const float* F2, float* aa, const FrameLayout& L, const float* wa,
+                                                  const AttW& aw, int A, const float* __restrict__ e,
+                                                  float* __restrict__ enc_a, float* __restrict__ enc_e, bool has_exp) {
+  static_assert(T == (SPLIT_CONV ? FW : FT), "the convolution routines are written for these workgroup sizes");
+  const int tid = threadIdx.x;
+  for (int i = tid; i < A * NB; i += T) {              // xt[j][t] = feat[t][j]
+    const int t = i % NB, j = i / NB;
+    aa[L.xt + i] = F2[t * A + j];
+  }
+  __syncthreads();
+  if (has_exp && tid >= T - 16) {                      // expression hidden layer on an idle part of the block
+    const int h = tid - (T - 16);
+    float acc = 0.f;
+    for (int i = 0; i < 5; ++i) acc += wa[aw.e1 + h * 5 + i] * e[i];
+    aa[L.eh + h] = fmaxf(acc, 0.f);
+  }
+  const int act[NATT + 1] = {L.xt, L.c1, L.c2, L.c3, L.c4, L.c5, L.z};    // layer i reads act[i], writes act[i + 1]
+#pragma unroll
+  for (int i = 0; i < NATT - 1; ++i) {
+    const AttLayer l = att_layer(i, A);
+    att_conv<SPLIT_CONV, 3>(aa + act[i], wa + aw.w[i], wa + aw.b[i], aa + act[i + 1], l.cin, l.cout, NB, true);
+    __syncthreads();
+  }
+  att_conv<SPLIT_CONV, 1>(aa + L.c5, wa + aw.w[5], wa + aw.b[5], aa + L.z, NB, NB, 1, false);   // the linear layer
+  __syncthreads();
+  if (tid < NB) {
+    float m = aa[L.z];
+    for (int t = 1; t < NB; ++t) m = fmaxf(m, aa[L.z + t]);
+    float sum = 0.f;
+    for (int t = 0; t < NB; ++t) sum += expf(aa[L.z + t] - m);
+    aa[L.y + tid] = expf(aa[L.z + tid] - m) / sum;
+  }
+  __syncthreads();
+  for (int j = tid; j < A; j += T) {
+    float acc = 0.f;
+    for (int t = 0; t < NB; ++t) acc += aa[L.y + t] * F2[t * A + j];
+    enc_a[j] = acc;
+  }
+  if (has_exp && tid >= T - 6) {
+    const int q = tid - (T - 6);
+    float acc;
+    if (q < 5) {
+      acc = 0.f;
+      for (int h = 0; h < 16; ++h) acc += wa[aw.e2 + q * 16 + h] * aa[L.eh + h];
+    } else {
+      acc = e[5];
+    }
+    enc_e[q] = acc;
+  }
+}
+
+// ... and backward (FT threads).  F2, sa as in attention_forward; gF2 / ga[L.<act>] = the gradients at the same offsets;
+// sw = group 5 staged weights-only; G = the stage's 14 gradient slots in parameter order.  `write`: this workgroup
+// stores them (every workgroup computes d feat; where several repeat the stage, one writes).  On return gF2 holds
+// d feat; no barrier behind the last loop.
+__device__ __forceinline__ void attention_backward(const float* F2, float* gF2, const float* sa, float* ga,
+                                                   const FrameLayout& L, const float* sw, const AttW& aw, int A,
+                                                   const float* __restrict__ e, const float* __restrict__ d_enc_a,
+                                                   const float* __restrict__ d_enc_e, float* const* G, bool write,
+                                                   bool has_exp) {
+  const int tid = threadIdx.x;
+  auto G0 = [&](int i) -> float* { return write ? G[i] : nullptr; };
+  // enc_a = sum_t y[t] feat[t]: d_y, d_feat; then softmax
+  if (tid < NB) {
+    float acc = 0.f;
+    for (int j = 0; j < A; ++j) acc += d_enc_a[j] * F2[tid * A + j];
+    ga[L.y + tid] = acc;
+  }
+  for (int i = tid; i < NB * A; i += FT) gF2[i] = sa[L.y + i / A] * d_enc_a[i % A];
+  if (has_exp && write) {
+    // enc_e[q<5] = sum_h W2[q][h] eh[h], eh = relu(W1 e[:5]); 80 + 80 threads own one weight each
+    // (two ifs, not if / else: merged into one store, the two arms would index G by a variable)
+    const int t = tid - 64;
+    if (t >= 0 && t < 80) {
+      const int q = t / 16, h = t % 16;
+      G[13][t] = (d_enc_e ? d_enc_e[q] : 0.f) * sa[L.eh + h];
+    }
+    if (t >= 80 && t < 160) {
+      const int i = (t - 80) % 5, h = (t - 80) / 5;
+      float dh = 0.f;
+      if (d_enc_e && sa[L.eh + h] > 0.f)
+        for (int q = 0; q < 5; ++q) dh += sw[aw.e2 + q * 16 + h] * d_enc_e[q];
+      G[12][h * 5 + i] = dh * e[i];
+    }
+  }
+  __syncthreads();
+  if (tid < NB) {
+    float dot = 0.f;
+    for (int t = 0; t < NB; ++t) dot += sa[L.y + t] * ga[L.y + t];
+    ga[L.z + tid] = sa[L.y + tid] * (ga[L.y + tid] - dot);
+  }
+  __syncthreads();
+  conv_backward<1, 1>(sa + L.c5, ga + L.z, sw + aw.w[5], G0(10), G0(11), ga + L.c5, 1, NB, NB, 1, 1, true);
+  __syncthreads();
+  const int act[NATT + 1] = {L.xt, L.c1, L.c2, L.c3, L.c4, L.c5, L.z};
+#pragma unroll
+  for (int i = NATT - 2; i >= 0; --i) {
+    const AttLayer l = att_layer(i, A);
+    conv_backward<3, 1>(sa + act[i], ga + act[i + 1], sw + aw.w[i], G0(2 * i), G0(2 * i + 1), ga + act[i], 1, l.cin,
+                        l.cout, NB, NB, i > 0);         // xt is no LeakyReLU output
+    __syncthreads();
+  }
+  for (int i = tid; i < NB * A; i += FT) {              // feat[t][j] also feeds xt[j][t]
+    const int j = i % A, t = i / A;
+    gF2[i] += ga[L.xt + j * NB + t];
+  }
+}
+
+__global__ void __launch_bounds__(FT)
+frame_code_forward_kernel(FrameDims d, ParamPtrs P, const float* __restrict__ a, const float* __restrict__ e,
+                          float* __restrict__ enc_a, float* __restrict__ enc_e, float* __restrict__ saved) {
+  extern __shared__ __align__(16) float s[];
+  const FrameLayout L = frame_layout(d.D, d.M, d.A);
+  float* sw = s + ((L.end + 3) & ~3);            // weight staging buffer
+  const int D = d.D, M = d.M, A = d.A;
+  for (int i = threadIdx.x; i < NB * D * WIN; i += FT) s[L.x0 + i] = a[i];
+  stage<FT>(sw, P.p[0], M * D * 3); stage<FT>(sw + M * D * 3, P.p[1], M);
+  __syncthreads();
+  conv_forward<3, 2>(s + L.x0, sw, sw + M * D * 3, s + L.a1, NB, D, M, 16, 8, true);
+  __syncthreads();
+  stage<FT>(sw, P.p[2], M * M * 3); stage<FT>(sw + M * M * 3, P.p[3], M);
+  __syncthreads();
+  conv_forward<3, 2>(s + L.a1, sw, sw + M * M * 3, s + L.a2, NB, M, M, 8, 4, true);
+  __syncthreads();
+  stage<FT>(sw, P.p[4], 64 * M * 3); stage<FT>(sw + 64 * M * 3, P.p[5], 64);
+  __syncthreads();
+  conv_forward<3, 2>(s + L.a2, sw, sw + 64 * M * 3, s + L.a3, NB, M, 64, 4, 2, true);
+  __syncthreads();
+  stage<FT>(sw, P.p[6], 64 * 64 * 3); stage<FT>(sw + 64 * 64 * 3, P.p[7], 64);
+  __syncthreads();
+  conv_forward<3, 2>(s + L.a3, sw, sw + 64 * 64 * 3, s + L.a4, NB, 64, 64, 2, 1, true);
+  __syncthreads();
+  stage<FT>(sw, P.p[8], 4096); stage<FT>(sw + 4096, P.p[9], 64); stage<FT>(sw + 4160, P.p[10], A * 64);
+  stage<FT>(sw + 4160 + A * 64, P.p[11], A);
+  __syncthreads();
+  conv_forward<1, 1>(s + L.a4, sw, sw + 4096, s + L.f1, NB, 64, 64, 1, 1, true);
+  __syncthreads();
+  conv_forward<1, 1>(s + L.f1, sw + 4160, sw + 4160 + A * 64, s + L.f2, NB, 64, A, 1, 1, false);
+  __syncthreads();
+  const AttW aw = att_layout(A);
+  stage_attention<FT>(sw, aw, P.p + 12, A, d.has_exp, false);         // complete at the stage's first barrier
+  attention_forward<FT, false>(s + L.f2, s, L, sw, aw, A, e, enc_a, enc_e, d.has_exp);
+  for (int i = threadIdx.x; i < L.end - L.a1; i += FT) saved[i] = s[L.a1 + i];
+}
+
+// ---- forward over NB workgroups --------------------------------------------------------------------------------
+// AudioNet's eight windows are independent (scene/motion_net.py:67-99): workgroup b runs window b through the four
+// convolutions and two linear layers with EVERY weight already in LDS (all staging loads are issued at kernel start:
+// one memory round trip instead of one per layer), the last workgroup to finish runs AudioAttNet over the eight feature
+// vectors (+ the expression MLP).  The single-workgroup form took 97 us, ~5 us per layer, almost all of it waiting
+// for the layer's weights and for barriers.
 __global__ void __launch_bounds__(FW)
 frame_code_forward_split_kernel(FrameDims d, ParamPtrs P, const float* __restrict__ a, const float* __restrict__ e,
                                 float* __restrict__ enc_a, float* __restrict__ enc_e, float* __restrict__ saved,
@@ -336,33 +466,14 @@ frame_code_forward_split_kernel(FrameDims d, ParamPtrs P, const float* __restric
   volatile uint32_t* s_ticket = reinterpret_cast<volatile uint32_t*>(att + NB * A + (L.end - L.xt));
   // every load of the kernel's weights is issued here
   for (int i = tid; i < D * WIN; i += FW) x0[i] = a[b * D * WIN + i];
-  auto stage = [&](int off, const float* src, int n) {
-    if (src == nullptr) return;
-    if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)(off * 4)) & 15) == 0) {
-      const float4* s4 = reinterpret_cast<const float4*>(src);
-      float4* d4 = reinterpret_cast<float4*>(s + off);
-#pragma unroll 4
-      for (int i = tid; i < n / 4; i += FW) d4[i] = s4[i];
-    } else {
-#pragma unroll 4
-      for (int i = tid; i < n; i += FW) s[off + i] = src[i];
-    }
-  };
-  stage(w1, P.p[0], M * D * 3); stage(b1, P.p[1], M);
-  stage(w2, P.p[2], M * M * 3); stage(b2, P.p[3], M);
-  stage(w3, P.p[4], 64 * M * 3); stage(b3, P.p[5], 64);
-  stage(w4, P.p[6], 64 * 64 * 3); stage(b4, P.p[7], 64);
-  stage(w5, P.p[8], 4096); stage(b5, P.p[9], 64);
-  stage(w6, P.p[10], A * 64); stage(b6, P.p[11], A);
+  stage<FW>(s + w1, P.p[0], M * D * 3); stage<FW>(s + b1, P.p[1], M);
+  stage<FW>(s + w2, P.p[2], M * M * 3); stage<FW>(s + b2, P.p[3], M);
+  stage<FW>(s + w3, P.p[4], 64 * M * 3); stage<FW>(s + b3, P.p[5], 64);
+  stage<FW>(s + w4, P.p[6], 64 * 64 * 3); stage<FW>(s + b4, P.p[7], 64);
+  stage<FW>(s + w5, P.p[8], 4096); stage<FW>(s + b5, P.p[9], 64);
+  stage<FW>(s + w6, P.p[10], A * 64); stage<FW>(s + b6, P.p[11], A);
   const AttW aw = att_layout(A);
-  {
-    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
-    for (int i = 0; i < 6; ++i) {
-      stage(watt + aw.w[i], P.p[12 + 2 * i], cout[i] * cin[i] * K[i]);
-      stage(watt + aw.b[i], P.p[13 + 2 * i], cout[i]);
-    }
-    if (d.has_exp) { stage(watt + aw.e1, P.p[24], 80); stage(watt + aw.e2, P.p[25], 80); }
-  }
+  stage_attention<FW>(s + watt, aw, P.p + 12, A, d.has_exp, false);
   __syncthreads();
   conv_forward_split<3, 2>(x0, s + w1, s + b1, a1, D, M, 16, 8, true);    __syncthreads();
   conv_forward_split<3, 2>(a1, s + w2, s + b2, a2, M, M, 8, 4, true);     __syncthreads();
@@ -379,71 +490,14 @@ frame_code_forward_split_kernel(FrameDims d, ParamPtrs P, const float* __restric
     for (int i = tid; i < 64; i += FW) { sv[L.a4 + b * 64 + i] = a4[i]; sv[L.f1 + b * 64 + i] = f1[i]; }
     for (int i = tid; i < A; i += FW) sv[L.f2 + b * A + i] = f2[i];
   }
-  // hand-off to the last workgroup: stores drained by every wave, workgroup barrier, agent-scope release, then the
-  // arrival counter; the workgroup that draws the last ticket acquires and reads all eight feature vectors
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    *s_ticket = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (*s_ticket != NB - 1) return;
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    *arrivals = 0u;                          // ready for the next launch (stream-ordered behind this one)
-  }
-  __syncthreads();
-  // ---- AudioAttNet over the eight windows + the expression MLP (activations in FrameLayout order from xt on) ----
+  if (!last_to_arrive(arrivals, s_ticket, NB)) return;
+  // the last workgroup reads all eight feature vectors; activations in FrameLayout order from xt on
   float* F2 = att;                           // [8][A]
   float* aa = F2 + NB * A - L.xt;            // aa[L.<act>] for act in xt .. eh
   const float* svr = saved - L.a1;
   for (int i = tid; i < NB * A; i += FW) F2[i] = svr[L.f2 + i];
   __syncthreads();
-  for (int i = tid; i < A * NB; i += FW) {            // xt[j][t] = feat[t][j]
-    const int t = i % NB, j = i / NB;
-    aa[L.xt + i] = F2[t * A + j];
-  }
-  if (d.has_exp && tid >= FW - 16) {                   // expression hidden layer on an idle part of the block
-    const int h = tid - (FW - 16);
-    float acc = 0.f;
-    for (int i = 0; i < 5; ++i) acc += s[watt + aw.e1 + h * 5 + i] * e[i];
-    aa[L.eh + h] = fmaxf(acc, 0.f);
-  }
-  __syncthreads();
-  const float* wa = s + watt;
-  conv_forward_split<3, 1>(aa + L.xt, wa + aw.w[0], wa + aw.b[0], aa + L.c1, A, 16, NB, NB, true);  __syncthreads();
-  conv_forward_split<3, 1>(aa + L.c1, wa + aw.w[1], wa + aw.b[1], aa + L.c2, 16, 8, NB, NB, true);  __syncthreads();
-  conv_forward_split<3, 1>(aa + L.c2, wa + aw.w[2], wa + aw.b[2], aa + L.c3, 8, 4, NB, NB, true);   __syncthreads();
-  conv_forward_split<3, 1>(aa + L.c3, wa + aw.w[3], wa + aw.b[3], aa + L.c4, 4, 2, NB, NB, true);   __syncthreads();
-  conv_forward_split<3, 1>(aa + L.c4, wa + aw.w[4], wa + aw.b[4], aa + L.c5, 2, 1, NB, NB, true);   __syncthreads();
-  conv_forward_split<1, 1>(aa + L.c5, wa + aw.w[5], wa + aw.b[5], aa + L.z, NB, NB, 1, 1, false);   __syncthreads();
-  if (tid < NB) {
-    float m = aa[L.z];
-    for (int t = 1; t < NB; ++t) m = fmaxf(m, aa[L.z + t]);
-    float sum = 0.f;
-    for (int t = 0; t < NB; ++t) sum += expf(aa[L.z + t] - m);
-    aa[L.y + tid] = expf(aa[L.z + tid] - m) / sum;
-  }
-  __syncthreads();
-  for (int j = tid; j < A; j += FW) {
-    float acc = 0.f;
-    for (int t = 0; t < NB; ++t) acc += aa[L.y + t] * F2[t * A + j];
-    enc_a[j] = acc;
-  }
-  if (d.has_exp && tid >= FW - 6) {
-    const int q = tid - (FW - 6);
-    float acc;
-    if (q < 5) {
-      acc = 0.f;
-      for (int h = 0; h < 16; ++h) acc += s[watt + aw.e2 + q * 16 + h] * aa[L.eh + h];
-    } else {
-      acc = e[5];
-    }
-    enc_e[q] = acc;
-  }
+  attention_forward<FW, true>(F2, aa, L, s + watt, aw, A, e, enc_a, enc_e, d.has_exp);
   {
     float* sv = saved - L.a1;
     for (int i = tid; i < L.end - L.xt; i += FW) sv[L.xt + i] = aa[L.xt + i];
@@ -488,65 +542,23 @@ frame_code_backward_kernel(FrameDims d, ParamPtrs P, GradPtrs G, const float* __
   const AttW aw = att_layout(A);
   for (int i = threadIdx.x; i < NB * D * WIN; i += FT) s[L.x0 + i] = a[i];
   for (int i = threadIdx.x; i < L.end - L.a1; i += FT) s[L.a1 + i] = saved[i];
-  {
-    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
-    for (int i = 0; i < 6; ++i) stage(sw + aw.w[i], P.p[12 + 2 * i], cout[i] * cin[i] * K[i]);
-    if (d.has_exp) stage(sw + aw.e2, P.p[25], 80);
-  }
+  stage_attention<FT>(sw, aw, P.p + 12, A, d.has_exp, true);
   __syncthreads();
-
-  // enc_a = sum_t y[t] feat[t]: d_y, d_feat; then softmax
-  if (threadIdx.x < NB) {
-    float acc = 0.f;
-    for (int j = 0; j < A; ++j) acc += d_enc_a[j] * s[L.f2 + threadIdx.x * A + j];
-    g[L.y + threadIdx.x] = acc;
-  }
-  for (int i = threadIdx.x; i < NB * A; i += FT) g[L.f2 + i] = s[L.y + i / A] * d_enc_a[i % A];
-  if (d.has_exp) {
-    // enc_e[q<5] = sum_h W2[q][h] eh[h], eh = relu(W1 e[:5]); 80 + 80 threads own one weight each
-    const int t = (int)threadIdx.x - 64;
-    if (t >= 0 && t < 80) {
-      const int q = t / 16, h = t % 16;
-      G.p[25][t] = (d_enc_e ? d_enc_e[q] : 0.f) * s[L.eh + h];
-    } else if (t >= 80 && t < 160) {
-      const int i = (t - 80) % 5, h = (t - 80) / 5;
-      float dh = 0.f;
-      if (d_enc_e && s[L.eh + h] > 0.f)
-        for (int q = 0; q < 5; ++q) dh += sw[aw.e2 + q * 16 + h] * d_enc_e[q];
-      G.p[24][h * 5 + i] = dh * e[i];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < NB) {
-    float dot = 0.f;
-    for (int t = 0; t < NB; ++t) dot += s[L.y + t] * g[L.y + t];
-    g[L.z + threadIdx.x] = s[L.y + threadIdx.x] * (g[L.y + threadIdx.x] - dot);
-  }
-  __syncthreads();
-  conv_backward<1, 1>(s + L.c5, g + L.z, sw + aw.w[5], G.p[22], G.p[23], g + L.c5, 1, NB, NB, 1, 1, true);   __syncthreads();
-  conv_backward<3, 1>(s + L.c4, g + L.c5, sw + aw.w[4], G.p[20], G.p[21], g + L.c4, 1, 2, 1, NB, NB, true);  __syncthreads();
-  conv_backward<3, 1>(s + L.c3, g + L.c4, sw + aw.w[3], G.p[18], G.p[19], g + L.c3, 1, 4, 2, NB, NB, true);  __syncthreads();
-  conv_backward<3, 1>(s + L.c2, g + L.c3, sw + aw.w[2], G.p[16], G.p[17], g + L.c2, 1, 8, 4, NB, NB, true);  __syncthreads();
-  conv_backward<3, 1>(s + L.c1, g + L.c2, sw + aw.w[1], G.p[14], G.p[15], g + L.c1, 1, 16, 8, NB, NB, true); __syncthreads();
-  conv_backward<3, 1>(s + L.xt, g + L.c1, sw + aw.w[0], G.p[12], G.p[13], g + L.xt, 1, A, 16, NB, NB, false);
-  __syncthreads();
-  for (int i = threadIdx.x; i < NB * A; i += FT) {            // feat[t][j] also feeds xt[j][t]
-    const int j = i % A, t = i / A;
-    g[L.f2 + i] += g[L.xt + j * NB + t];
-  }
-  stage(sw, P.p[8], 4096); stage(sw + 4096, P.p[10], A * 64);
+  // every workgroup writes the stage's gradients: into G, or (SPLIT) into its row of `partial`
+  attention_backward(s + L.f2, g + L.f2, s, g, L, sw, aw, A, e, d_enc_a, d_enc_e, G.p + 12, true, d.has_exp);
+  stage<FT>(sw, P.p[8], 4096); stage<FT>(sw + 4096, P.p[10], A * 64);
   __syncthreads();
   // AudioNet, windows wb .. wb + WB - 1 (activations are [window][channel][position])
 #define WIN_AT(base, c, l) ((base) + wb * (c) * (l))
   conv_backward<1, 1>(WIN_AT(s + L.f1, 64, 1), WIN_AT(g + L.f2, A, 1), sw + 4096, G.p[10], G.p[11], WIN_AT(g + L.f1, 64, 1), WB, 64, A, 1, 1, true); __syncthreads();
   conv_backward<1, 1>(WIN_AT(s + L.a4, 64, 1), WIN_AT(g + L.f1, 64, 1), sw, G.p[8], G.p[9], WIN_AT(g + L.a4, 64, 1), WB, 64, 64, 1, 1, true);         __syncthreads();
-  stage(sw, P.p[6], 64 * 64 * 3);
+  stage<FT>(sw, P.p[6], 64 * 64 * 3);
   __syncthreads();
   conv_backward<3, 2>(WIN_AT(s + L.a3, 64, 2), WIN_AT(g + L.a4, 64, 1), sw, G.p[6], G.p[7], WIN_AT(g + L.a3, 64, 2), WB, 64, 64, 2, 1, true);         __syncthreads();
-  stage(sw, P.p[4], 64 * M * 3);
+  stage<FT>(sw, P.p[4], 64 * M * 3);
   __syncthreads();
   conv_backward<3, 2>(WIN_AT(s + L.a2, M, 4), WIN_AT(g + L.a3, 64, 2), sw, G.p[4], G.p[5], WIN_AT(g + L.a2, M, 4), WB, M, 64, 4, 2, true);          __syncthreads();
-  stage(sw, P.p[2], M * M * 3);
+  stage<FT>(sw, P.p[2], M * M * 3);
   __syncthreads();
   conv_backward<3, 2>(WIN_AT(s + L.a1, M, 8), WIN_AT(g + L.a2, M, 4), sw, G.p[2], G.p[3], WIN_AT(g + L.a1, M, 8), WB, M, M, 8, 4, true);           __syncthreads();
   conv_backward<3, 2>(WIN_AT(s + L.x0, D, 16), WIN_AT(g + L.a1, M, 8), nullptr, G.p[0], G.p[1], nullptr, WB, D, M, 16, 8, false);
@@ -707,14 +719,7 @@ frame_code_ave_forward_kernel(AveDims d, AveParamPtrs P, const float* __restrict
   volatile uint32_t* s_ticket = reinterpret_cast<volatile uint32_t*>(sw + att_floats(A));
   for (int i = tid; i < NB * AVE_IN; i += FT) xa[i] = a[i];
   const AttW aw = att_layout(A);
-  {
-    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
-    for (int i = 0; i < 6; ++i) {
-      stage(sw + aw.w[i], P.p[6 + 2 * i], cout[i] * cin[i] * K[i]);
-      stage(sw + aw.b[i], P.p[7 + 2 * i], cout[i]);
-    }
-    if (d.has_exp) { stage(sw + aw.e1, P.p[18], 80); stage(sw + aw.e2, P.p[19], 80); }
-  }
+  stage_attention<FT>(sw, aw, P.p + 6, A, d.has_exp, false);
   __syncthreads();
   // fc1: this workgroup's neurons, all eight windows
   const int per = AVE_H1 / nwg, n0 = (int)blockIdx.x * per;
@@ -729,23 +734,8 @@ frame_code_ave_forward_kernel(AveDims d, AveParamPtrs P, const float* __restrict
     }
   }
   if (nwg > 1) {
-    // hand-off to the last workgroup, as in frame_code_forward_split_kernel: stores drained by every wave, workgroup
-    // barrier, agent-scope release, then the arrival counter; the last ticket acquires and reads all of z1
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      *s_ticket = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (*s_ticket != (uint32_t)nwg - 1u) return;
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      *arrivals = 0u;                          // ready for the next launch (stream-ordered behind this one)
-    }
-    __syncthreads();
+    if (!last_to_arrive(arrivals, s_ticket, nwg)) return;
+    // the last workgroup reads all of z1
     for (int i = tid; i < NB * AVE_H1; i += FT) act[Y.z1 + i] = saved[Y.z1 + i];
   }
   __syncthreads();
@@ -759,50 +749,8 @@ frame_code_ave_forward_kernel(AveDims d, AveParamPtrs P, const float* __restrict
     if ((lane & 7) == 0) act[Y.f2 + (lane >> 3) * A + j] = v + P.p[5][j];
   }
   __syncthreads();
-  // ---- AudioAttNet over the eight windows + the expression MLP (activations in FrameLayout order from xt on) ----
-  float* F2 = act + Y.f2;                       // [8][A]
-  float* aa = act + Y.att - L.xt;               // aa[L.<act>] for act in xt .. eh
-  for (int i = tid; i < A * NB; i += FT) {      // xt[j][t] = feat[t][j]
-    const int t = i % NB, j = i / NB;
-    aa[L.xt + i] = F2[t * A + j];
-  }
-  if (d.has_exp && tid >= FT - 16) {            // expression hidden layer on an idle part of the block
-    const int h = tid - (FT - 16);
-    float acc = 0.f;
-    for (int i = 0; i < 5; ++i) acc += sw[aw.e1 + h * 5 + i] * e[i];
-    aa[L.eh + h] = fmaxf(acc, 0.f);
-  }
-  __syncthreads();
-  conv_forward<3, 1>(aa + L.xt, sw + aw.w[0], sw + aw.b[0], aa + L.c1, 1, A, 16, NB, NB, true);  __syncthreads();
-  conv_forward<3, 1>(aa + L.c1, sw + aw.w[1], sw + aw.b[1], aa + L.c2, 1, 16, 8, NB, NB, true);  __syncthreads();
-  conv_forward<3, 1>(aa + L.c2, sw + aw.w[2], sw + aw.b[2], aa + L.c3, 1, 8, 4, NB, NB, true);   __syncthreads();
-  conv_forward<3, 1>(aa + L.c3, sw + aw.w[3], sw + aw.b[3], aa + L.c4, 1, 4, 2, NB, NB, true);   __syncthreads();
-  conv_forward<3, 1>(aa + L.c4, sw + aw.w[4], sw + aw.b[4], aa + L.c5, 1, 2, 1, NB, NB, true);   __syncthreads();
-  conv_forward<1, 1>(aa + L.c5, sw + aw.w[5], sw + aw.b[5], aa + L.z, 1, NB, NB, 1, 1, false);   __syncthreads();
-  if (tid < NB) {
-    float m = aa[L.z];
-    for (int t = 1; t < NB; ++t) m = fmaxf(m, aa[L.z + t]);
-    float sum = 0.f;
-    for (int t = 0; t < NB; ++t) sum += expf(aa[L.z + t] - m);
-    aa[L.y + tid] = expf(aa[L.z + tid] - m) / sum;
-  }
-  __syncthreads();
-  for (int j = tid; j < A; j += FT) {
-    float acc = 0.f;
-    for (int t = 0; t < NB; ++t) acc += aa[L.y + t] * F2[t * A + j];
-    enc_a[j] = acc;
-  }
-  if (d.has_exp && tid >= FT - 6) {
-    const int q = tid - (FT - 6);
-    float acc;
-    if (q < 5) {
-      acc = 0.f;
-      for (int h = 0; h < 16; ++h) acc += sw[aw.e2 + q * 16 + h] * aa[L.eh + h];
-    } else {
-      acc = e[5];
-    }
-    enc_e[q] = acc;
-  }
+  // activations in FrameLayout order from xt on: aa[L.<act>] for act in xt .. eh
+  attention_forward<FT, false>(act + Y.f2, act + Y.att - L.xt, L, sw, aw, A, e, enc_a, enc_e, d.has_exp);
   for (int i = tid; i < Y.end - Y.z2; i += FT) saved[Y.z2 + i] = act[Y.z2 + i];
 }
 
@@ -826,58 +774,14 @@ frame_code_ave_backward_kernel(AveDims d, AveParamPtrs P, AveGradPtrs G, const f
   const AttW aw = att_layout(A);
   for (int i = tid; i < NB * AVE_IN; i += FT) xa[i] = a[i];
   for (int i = tid; i < Y.end; i += FT) act[i] = saved[i];
-  {
-    const int cin[6] = {A, 16, 8, 4, 2, 8}, cout[6] = {16, 8, 4, 2, 1, 8}, K[6] = {3, 3, 3, 3, 3, 1};
-    for (int i = 0; i < 6; ++i) stage(sw + aw.w[i], P.p[6 + 2 * i], cout[i] * cin[i] * K[i]);
-    if (d.has_exp) stage(sw + aw.e2, P.p[19], 80);
-  }
-  stage(w3, P.p[4], A * AVE_H2);
+  stage_attention<FT>(sw, aw, P.p + 6, A, d.has_exp, true);
+  stage<FT>(w3, P.p[4], A * AVE_H2);
   __syncthreads();
-  const float* F2 = act + Y.f2;
   float* gF2 = g + Y.f2;
-  const float* sa = act + Y.att - L.xt;         // sa[L.<act>], ga[L.<act>] for act in xt .. eh
-  float* ga = g + Y.att - L.xt;
   auto G0 = [&](int i) -> float* { return first ? G.p[i] : nullptr; };
-
-  // enc_a = sum_t y[t] feat[t]: d_y, d_feat; then softmax
-  if (tid < NB) {
-    float acc = 0.f;
-    for (int j = 0; j < A; ++j) acc += d_enc_a[j] * F2[tid * A + j];
-    ga[L.y + tid] = acc;
-  }
-  for (int i = tid; i < NB * A; i += FT) gF2[i] = sa[L.y + i / A] * d_enc_a[i % A];
-  if (d.has_exp && first) {
-    // enc_e[q<5] = sum_h W2[q][h] eh[h], eh = relu(W1 e[:5]); 80 + 80 threads own one weight each
-    const int t = tid - 64;
-    if (t >= 0 && t < 80) {
-      const int q = t / 16, h = t % 16;
-      G.p[19][t] = (d_enc_e ? d_enc_e[q] : 0.f) * sa[L.eh + h];
-    } else if (t >= 80 && t < 160) {
-      const int i = (t - 80) % 5, h = (t - 80) / 5;
-      float dh = 0.f;
-      if (d_enc_e && sa[L.eh + h] > 0.f)
-        for (int q = 0; q < 5; ++q) dh += sw[aw.e2 + q * 16 + h] * d_enc_e[q];
-      G.p[18][h * 5 + i] = dh * e[i];
-    }
-  }
-  __syncthreads();
-  if (tid < NB) {
-    float dot = 0.f;
-    for (int t = 0; t < NB; ++t) dot += sa[L.y + t] * ga[L.y + t];
-    ga[L.z + tid] = sa[L.y + tid] * (ga[L.y + tid] - dot);
-  }
-  __syncthreads();
-  conv_backward<1, 1>(sa + L.c5, ga + L.z, sw + aw.w[5], G0(16), G0(17), ga + L.c5, 1, NB, NB, 1, 1, true);   __syncthreads();
-  conv_backward<3, 1>(sa + L.c4, ga + L.c5, sw + aw.w[4], G0(14), G0(15), ga + L.c4, 1, 2, 1, NB, NB, true);  __syncthreads();
-  conv_backward<3, 1>(sa + L.c3, ga + L.c4, sw + aw.w[3], G0(12), G0(13), ga + L.c3, 1, 4, 2, NB, NB, true);  __syncthreads();
-  conv_backward<3, 1>(sa + L.c2, ga + L.c3, sw + aw.w[2], G0(10), G0(11), ga + L.c2, 1, 8, 4, NB, NB, true);  __syncthreads();
-  conv_backward<3, 1>(sa + L.c1, ga + L.c2, sw + aw.w[1], G0(8), G0(9), ga + L.c1, 1, 16, 8, NB, NB, true);   __syncthreads();
-  conv_backward<3, 1>(sa + L.xt, ga + L.c1, sw + aw.w[0], G0(6), G0(7), ga + L.xt, 1, A, 16, NB, NB, false);
-  __syncthreads();
-  for (int i = tid; i < NB * A; i += FT) {      // feat[t][j] also feeds xt[j][t]
-    const int j = i % A, t = i / A;
-    gF2[i] += ga[L.xt + j * NB + t];
-  }
+  // sa[L.<act>], ga[L.<act>] for act in xt .. eh
+  attention_backward(act + Y.f2, gF2, act + Y.att - L.xt, g + Y.att - L.xt, L, sw, aw, A, e, d_enc_a, d_enc_e, G.p + 6,
+                     first, d.has_exp);
   __syncthreads();
   // fc3 (no activation behind it): dW3, db3 once, d z2 (before its LeakyReLU) in every workgroup
   conv_backward<1, 1>(act + Y.z2, gF2, w3, G0(4), G0(5), g + Y.z2, NB, AVE_H2, A, 1, 1, true);
@@ -963,6 +867,18 @@ inline int set_ave_lds_limit() {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The n parameter pointers of an entry point into P and, for a backward pass, the gradient pointers into G (else
+// G == grads == nullptr).  Only the last two, the expression weights, may be NULL, and only without the branch.
+inline int gather_params(const float** P, float** G, const float* const* params, float* const* grads, int n,
+                         bool has_exp, const char* error) {
+  for (int i = 0; i < n; ++i) {
+    P[i] = params[i];
+    if (G) G[i] = grads[i];
+    INSTAG_REQUIRE((P[i] && (!G || G[i])) || (i >= n - 2 && !has_exp), error);
+  }
+  return INSTAG_OK;
+}
+
 }  // namespace
 }  // namespace instag
 
@@ -984,10 +900,8 @@ int instag_frame_code_forward(const float* a, const float* e, const float* const
   INSTAG_REQUIRE((e == nullptr) == (enc_e == nullptr), "frame_code_forward: e and enc_e go together");
   const int has_exp = e != nullptr;
   ParamPtrs P;
-  for (int i = 0; i < NPARAM; ++i) {
-    P.p[i] = params[i];
-    INSTAG_REQUIRE(P.p[i] || (i >= 24 && !has_exp), "frame_code_forward: NULL parameter");
-  }
+  if (int rc = gather_params(P.p, nullptr, params, nullptr, NPARAM, has_exp, "frame_code_forward: NULL parameter"))
+    return rc;
   if (int rc = set_lds_limit()) return rc;
   const FrameLayout L = frame_layout(dim_in, mid, dim_aud);
   const FrameDims d{dim_in, mid, dim_aud, has_exp};
@@ -1020,11 +934,9 @@ int instag_frame_code_backward(const float* a, const float* e, const float* cons
   const int has_exp = e != nullptr;
   ParamPtrs P;
   GradPtrs G;
-  for (int i = 0; i < NPARAM; ++i) {
-    P.p[i] = params[i];
-    G.p[i] = grads[i];
-    INSTAG_REQUIRE((P.p[i] && G.p[i]) || (i >= 24 && !has_exp), "frame_code_backward: NULL parameter / gradient");
-  }
+  if (int rc = gather_params(P.p, G.p, params, grads, NPARAM, has_exp,
+                             "frame_code_backward: NULL parameter / gradient"))
+    return rc;
   if (int rc = set_lds_limit()) return rc;
   const FrameLayout L = frame_layout(dim_in, mid, dim_aud);
   const FrameDims d{dim_in, mid, dim_aud, has_exp};
@@ -1057,10 +969,9 @@ int instag_frame_code_ave_forward(const float* a, const float* e, const float* c
   INSTAG_REQUIRE((e == nullptr) == (enc_e == nullptr), "frame_code_ave_forward: e and enc_e go together");
   const int has_exp = e != nullptr;
   AveParamPtrs P;
-  for (int i = 0; i < AVE_NPARAM; ++i) {
-    P.p[i] = params[i];
-    INSTAG_REQUIRE(P.p[i] || (i >= 18 && !has_exp), "frame_code_ave_forward: NULL parameter");
-  }
+  if (int rc = gather_params(P.p, nullptr, params, nullptr, AVE_NPARAM, has_exp,
+                             "frame_code_ave_forward: NULL parameter"))
+    return rc;
   if (int rc = set_ave_lds_limit()) return rc;
   const AveDims d{dim_aud, has_exp};
   const int vec = (aligned16(P.p[0]) ? 1 : 0) | (aligned16(P.p[2]) ? 2 : 0) | (aligned16(P.p[4]) ? 4 : 0);
@@ -1081,11 +992,9 @@ int instag_frame_code_ave_backward(const float* a, const float* e, const float* 
   const int has_exp = e != nullptr;
   AveParamPtrs P;
   AveGradPtrs G;
-  for (int i = 0; i < AVE_NPARAM; ++i) {
-    P.p[i] = params[i];
-    G.p[i] = grads[i];
-    INSTAG_REQUIRE((P.p[i] && G.p[i]) || (i >= 18 && !has_exp), "frame_code_ave_backward: NULL parameter / gradient");
-  }
+  if (int rc = gather_params(P.p, G.p, params, grads, AVE_NPARAM, has_exp,
+                             "frame_code_ave_backward: NULL parameter / gradient"))
+    return rc;
   if (int rc = set_ave_lds_limit()) return rc;
   const AveDims d{dim_aud, has_exp};
   frame_code_ave_backward_kernel<<<AVE_WG, FT, ave_backward_floats(dim_aud) * sizeof(float), (hipStream_t)stream>>>(

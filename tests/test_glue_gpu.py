@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 def _close(a, b, name, tol=2e-5):
     err = float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
     scale = max(1.0, float(b.detach().abs().max()))
+    print(f"{name}: err {err:.3e} scale {scale:.3e} rel {err / scale:.3e}")
     assert err <= tol * scale, f"{name}: err {err} scale {scale}"
 
 
@@ -117,16 +118,22 @@ def test_multi_tensor_adam_matches_torch():
             assert float((a - b).abs().max()) <= 2e-6 * max(1.0, float(b.abs().max()))
 
 
-@pytest.mark.parametrize("split", [True, False], ids=["bwd-8wg", "bwd-1wg"])
+# the backward forms are crossed with the default forward form only
+@pytest.mark.parametrize("form,split", [("arrivals", True), ("arrivals", False), ("one-workgroup", True),
+                                        ("lds-fallback", True)],
+                         ids=["bwd-8wg", "bwd-1wg", "one-workgroup", "lds-fallback"])
 @pytest.mark.parametrize("extractor,net", [("deepspeech", "umf"), ("esperanto", "pmf")])
-def test_frame_codes_match_torch_modules(extractor, net, split, monkeypatch):
+def test_frame_codes_match_torch_modules(extractor, net, form, split, monkeypatch):
     """AudioNet + AudioAttNet + expression MLP as fused kernels vs the nn.Module chain (fp64, CPU); backward with one
-    workgroup per audio window (default) and as a single workgroup."""
+    workgroup per audio window (default) and as a single workgroup.  Forward forms: `arrivals` = one workgroup per
+    window (the default), `one-workgroup` = the Function applied without an arrival word, `lds-fallback` = an AudioNet
+    of 96 input channels, whose split form needs 169,920 bytes of LDS (> 160 KB; 162,752 at 80 channels still fit), so
+    that the C side takes the single-workgroup kernel by itself."""
     import copy
     from types import SimpleNamespace
     from instag_amd import audio as A
     monkeypatch.setattr(A, "SPLIT_BACKWARD", split)
-    from instag_amd.motion_net import MotionNetwork, PersonalizedMotionNetwork, audio_in_dim
+    from instag_amd.motion_net import AudioNet, MotionNetwork, PersonalizedMotionNetwork, audio_in_dim
 
     class NoEncoder(torch.nn.Module):          # the tri-plane encoders play no part in the per-frame branch
         def __init__(self, **kw):
@@ -136,19 +143,28 @@ def test_frame_codes_match_torch_modules(extractor, net, split, monkeypatch):
     torch.manual_seed(3)
     args = SimpleNamespace(audio_extractor=extractor, type="face")
     cls = MotionNetwork if net == "umf" else PersonalizedMotionNetwork
-    ref = cls(args=args, encoder_cls=NoEncoder).double()
+    ref = cls(args=args, encoder_cls=NoEncoder)
+    dim_in = audio_in_dim(extractor)
+    if form == "lds-fallback":
+        dim_in = 96
+        ref.audio_net = AudioNet(dim_in=96, dim_aud=32)
+    ref = ref.double()
     with torch.no_grad():
         for p in ref.parameters():             # biases and weights large enough to exercise both LeakyReLU sides
             p.mul_(2.0)
     dev = copy.deepcopy(ref).float().cuda()
-    a = torch.randn(8, audio_in_dim(extractor), 16)
+    a = torch.randn(8, dim_in, 16)
     e = torch.rand(6)
     wa, we = torch.randn(1, 32), torch.randn(6)
 
     enc_a_r, enc_e_r = ref.encode_frame(a.double(), e.double())
     ((enc_a_r * wa.double()).sum() + (enc_e_r * we.double()).sum()).backward()
     assert A.supported(dev, a.cuda(), e.cuda())
-    enc_a_h, enc_e_h = dev.encode_frame(a.cuda(), e.cuda())
+    if form == "one-workgroup":
+        enc_a_h, enc_e_h = A._FrameCodes.apply(a.cuda(), e.cuda(), A._STOCK, (dim_in, 32, 32), None,
+                                               *A._module_params(dev))
+    else:
+        enc_a_h, enc_e_h = dev.encode_frame(a.cuda(), e.cuda())
     ((enc_a_h * wa.cuda()).sum() + (enc_e_h * we.cuda()).sum()).backward()
     _close(enc_a_h, enc_a_r, "enc_a")
     _close(enc_e_h, enc_e_r, "enc_e")
