@@ -802,6 +802,47 @@ int instag_infer_compose(const float* face, const float* a_face, const float* mo
                          int32_t H, int32_t W, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The 8-bit frame store (csrc/frames.hip): a processed identity's frames kept compact in device memory.
+ *
+ * Store layout: frame f at byte f * instag_frame_store_stride(H,W) of a 256-byte aligned buffer; inside it
+ *   rgb [H*W*3] u8, bg [H*W*3] u8, mask [H*W] u8, each plane padded to a multiple of 256 bytes.
+ *   records: instag_frame_record_dwords() (= 48) dwords per frame: world_view_transform 0..15,
+ *   full_proj_transform 16..31, camera_center 32..34, au_exp 35..40 (fp32), lips_rect 41..44 (int32).
+ * frame_ingest (load time): gt [F,H,W,3], torso [F,H,W,4] (RGBA), bc [H,W,3] (shared), parsing [F,H,W,3],
+ *   teeth [F,H,W] (non-zero = set), all u8 and 4-byte aligned.  rgb = gt; bg = the per-camera background of
+ *   dataset_readers.py:232-235, (torso_rgb * a / 255.0 + bc * (1 - a / 255.0)).astype(uint8), evaluated
+ *   as numpy does (fp64, that order, each operation rounded once, truncation); mask bit 0 face =
+ *   ((B > 254) & (R == 0) & (G == 0)) ^ teeth, bit 1 hair = R, G, B all < 1, bit 2 mouth = (R, G, B all
+ *   == 100) | teeth (dataset_readers.py:247-249).  counts int32 [F,3]: pixels set per mask (cleared by
+ *   the call; wave-level reduction, then integer atomics: independent of order).
+ * frame_unpack (every step): frame idx of a store into the byte buffer `dst` (dst_bytes long) of a packed
+ *   Frame, in ONE launch.  off_*: byte offsets of the destination tensors inside dst (multiples of 4; -1
+ *   for background / normal / depth = the layout has none).  original_image and background [3,H,W] fp32 =
+ *   u8 / 255.0, one correctly rounded fp32 division; face / hair / mouth masks [H,W] bool bytes; the
+ *   record tensors copied; auds [8, audio_row] = rows audio_index - 4 .. audio_index + 3 of the table
+ *   audio [T, audio_row] fp32, zero rows outside it (utils/audio_utils.py:38-73, mode 2); normal
+ *   [F,3,H,W] / depth [F,H,W] fp32 copied when the layout has them (then the store must: else E_ARG).
+ *   No byte of dst outside these tensors is written.  16-byte stores where H*W % 4 == 0.
+ *   INSTAG_E_ARG for a NULL tensor, idx outside [0,F), audio_index outside [0,T], H,W <= 0, or a layout
+ *   that does not fit dst / asks for priors the store lacks.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_frame_unpack_args {
+  const uint8_t* store; const float* records; const float* normal; const float* depth; const float* audio;
+  uint8_t* dst;
+  int64_t dst_bytes;
+  int64_t off_image, off_background, off_face, off_hair, off_mouth;
+  int64_t off_world_view, off_full_proj, off_camera_center, off_au_exp, off_lips_rect;
+  int64_t off_auds, off_normal, off_depth;
+  int32_t F, H, W, idx, audio_index, T, audio_row, reserved;
+} instag_frame_unpack_args;
+int64_t instag_frame_store_stride(int32_t H, int32_t W);
+int32_t instag_frame_record_dwords(void);
+int instag_frame_ingest(const uint8_t* gt, const uint8_t* torso, const uint8_t* bc, const uint8_t* parsing,
+                        const uint8_t* teeth, int32_t F, int32_t H, int32_t W, uint8_t* store, int32_t* counts,
+                        instag_stream_t stream);
+int instag_frame_unpack(const instag_frame_unpack_args* args, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named
  * kernel with hipEvents on the launch stream; instag_prof_read synchronises those events and
  * returns accumulated milliseconds and launch count since the last reset.

@@ -39,6 +39,17 @@ class AveEncoderWeights(C.Structure):
     _fields_ = [("w", vp * 13), ("scale", vp * 13), ("shift", vp * 13)]
 
 
+class FrameUnpackArgs(C.Structure):
+    """struct instag_frame_unpack_args (include/instag_hip.h)."""
+    _fields_ = [("store", vp), ("records", vp), ("normal", vp), ("depth", vp), ("audio", vp), ("dst", vp),
+                ("dst_bytes", i64),
+                ("off_image", i64), ("off_background", i64), ("off_face", i64), ("off_hair", i64), ("off_mouth", i64),
+                ("off_world_view", i64), ("off_full_proj", i64), ("off_camera_center", i64), ("off_au_exp", i64),
+                ("off_lips_rect", i64), ("off_auds", i64), ("off_normal", i64), ("off_depth", i64),
+                ("F", i32), ("H", i32), ("W", i32), ("idx", i32), ("audio_index", i32), ("T", i32), ("audio_row", i32),
+                ("reserved", i32)]
+
+
 class WgradJob(C.Structure):
     """struct instag_wgrad_job (include/instag_hip.h)."""
     _fields_ = [("dz", vp), ("inp", vp), ("dw", vp), ("N", i32), ("O", i32), ("K", i32)]
@@ -332,6 +343,10 @@ _PROTOS = {
     "instag_frame_metrics": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "instag_meter_add": (C.c_int, [vp, i32, vp, vp]),
     "instag_infer_compose": (C.c_int, [vp] * 6 + [i32, vp, vp, i32, i32, vp]),
+    "instag_frame_store_stride": (C.c_int64, [i32, i32]),
+    "instag_frame_record_dwords": (i32, []),
+    "instag_frame_ingest": (C.c_int, [vp] * 5 + [i32] * 3 + [vp, vp, vp]),
+    "instag_frame_unpack": (C.c_int, [C.POINTER(FrameUnpackArgs), vp]),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

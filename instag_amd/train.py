@@ -97,6 +97,11 @@ class Frame:
         assert (self.image_height, self.image_width) == (other.image_height, other.image_width)
         assert abs(self.FoVx - other.FoVx) < 1e-12 and abs(self.FoVy - other.FoVy) < 1e-12, \
             "graph mode bakes the field of view into the captured launches"
+        if not isinstance(other, Frame):
+            from .frame_store import StoredFrame
+            if isinstance(other, StoredFrame):         # a frame of a device-resident 8-bit store: one unpack launch
+                other.store.unpack_into(self, other.index)
+                return
         if getattr(self, "_buf", None) is not None and getattr(other, "_buf", None) is not None \
                 and self._layout == other._layout:
             self._buf.copy_(other._buf, non_blocking=True)
