@@ -843,6 +843,39 @@ int instag_frame_ingest(const uint8_t* gt, const uint8_t* torso, const uint8_t* 
 int instag_frame_unpack(const instag_frame_unpack_args* args, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Preparing an identity (csrc/prepare.hip): the shared background, the ground-truth and the torso frames
+ * from decoded frames and parsing maps (data_utils/process.py:89-176, 199-374).  All images u8, RGB:
+ * head (0,0,255), neck (0,255,0), torso (255,0,0), background (255,255,255).
+ *
+ * prep_background: ori, parsing [S,H,W,3] (the samples) -> bc [H,W,3]; max_d2, arg [H,W] int32 (also the
+ *   state carried between chunks of samples: always written).  max_d2 = max over s of the exact squared
+ *   Euclidean distance to the nearest non-background pixel of sample s, arg = the first s attaining it.
+ *   Pixels with max_d2 > 25 are known and take ori[arg]; every other pixel takes the colour of its nearest
+ *   known pixel: smallest squared distance, then smallest row, then smallest column.  H, W <= 2048.
+ *   workspace: instag_prep_background_workspace_bytes(S,H,W) bytes, 4-byte aligned.  The call waits for
+ *   the stream (it reads two data conditions back) and returns INSTAG_E_ARG when a sample has no
+ *   non-background pixel or no pixel is known; INSTAG_E_SPACE for a short workspace.
+ * prep_frames: ori, parsing [F,H,W,3], bc [H,W,3], table [53,256] u8 (table[k][v] = the fp64 product
+ *   v * 0.98**k truncated, built on the host) -> gt [F,H,W,3], torso [F,H,W,4] RGBA (4-byte aligned);
+ *   cols: workspace of F*W*2 int32.  H >= 64 (the 53-row paint wraps at most once), W >= 3, F <= 65535.
+ *   1 gt = ori, bc where parsing is background.  2 t = gt, bc where head.  3 every column whose topmost
+ *   torso pixel (y,x) has head at row y-1: rows y-k, k = 0..8, = table[k][gt[y,x]].  4 neck dilated by 3
+ *   rows each way (nothing beyond the border); every column whose topmost dilated-neck pixel (y,x) has
+ *   head at row y-1, with c dilated-neck pixels and o = min(c-1, 4): rows y+o-k, k = 0..52, =
+ *   table[k][gt[y+o,x]] (over step 3).  Rows are taken modulo H throughout.  5 the pixels painted in 4
+ *   become the 5x5 Gaussian of the image after 4: per axis weights 48 53 54 53 48 (/256: sigma 4,
+ *   rounded, the centre takes the remainder), reflect-101 border, (sum + 32768) >> 16.  6 mask = dilated
+ *   neck | torso | painted: RGB and alpha 0 outside it, alpha 255 inside.  Every byte of gt and torso is
+ *   written.  Two launches on `stream`, no host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+size_t instag_prep_background_workspace_bytes(int32_t S, int32_t H, int32_t W);
+int instag_prep_background(const uint8_t* ori, const uint8_t* parsing, int32_t S, int32_t H, int32_t W, uint8_t* bc,
+                           int32_t* max_d2, int32_t* arg, void* workspace, size_t workspace_bytes,
+                           instag_stream_t stream);
+int instag_prep_frames(const uint8_t* ori, const uint8_t* parsing, const uint8_t* bc, const uint8_t* table, int32_t F,
+                       int32_t H, int32_t W, uint8_t* gt, uint8_t* torso, int32_t* cols, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named
  * kernel with hipEvents on the launch stream; instag_prof_read synchronises those events and
  * returns accumulated milliseconds and launch count since the last reset.

@@ -347,6 +347,9 @@ _PROTOS = {
     "instag_frame_record_dwords": (i32, []),
     "instag_frame_ingest": (C.c_int, [vp] * 5 + [i32] * 3 + [vp, vp, vp]),
     "instag_frame_unpack": (C.c_int, [C.POINTER(FrameUnpackArgs), vp]),
+    "instag_prep_background_workspace_bytes": (sz, [i32, i32, i32]),
+    "instag_prep_background": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "instag_prep_frames": (C.c_int, [vp] * 4 + [i32] * 3 + [vp] * 4),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

@@ -51,6 +51,7 @@ SOURCES = {
     "ave_encoder.hip": [],
     # frames: the background composite is fp64 in numpy's operation order, every operation rounded once
     "frames.hip": ["-ffp-contract=off"],
+    "prepare.hip": [],
 }
 
 
