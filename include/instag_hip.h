@@ -876,6 +876,79 @@ int instag_prep_frames(const uint8_t* ori, const uint8_t* parsing, const uint8_t
                        int32_t H, int32_t W, uint8_t* gt, uint8_t* torso, int32_t* cols, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Head-pose tracking from landmarks (csrc/track.hip): the landmark stages of the reference's 3DMM fit
+ * (data_utils/face_tracking/face_tracker.py:62-205).  All tensors on the device, fp32, contiguous, unless
+ * marked (host).
+ *
+ * The model is reduced to the M = 68 + 16 P points the fit touches: point j < 68 is keyinds[j]; point
+ * 68 + s P + p is candidate p of contour slot s (slots 0..7: left_contour rows, landmarks 0..7, smallest
+ * projected x wins; slots 8..15: right_contour rows, landmarks 9..16, largest projected x wins; among
+ * equal candidates the first).  basis [K, 3M], K = id_dim + exp_dim: the rows of base_id then base_exp,
+ * each already multiplied by its sig_id / sig_exp entry; basis_t [3M, K] its transpose; mu [3M].
+ *
+ * G groups (1 .. instag_track_max_groups()) share one call: group g owns frames group_start[g] ..
+ * group_start[g+1] (host, G+1 entries, 0 .. F, none empty), its own focal[g] (host) and its own id row.
+ * lms [F,68,2]; id [G,id_dim]; exp [F,exp_dim]; pose [F,6] = euler (theta, phi, psi), trans (x, y, z);
+ * R = Rx(theta) Ry(phi) Rz(psi) as util.py:18-49 builds it, x = -f X / Z + cx, y = f Y / Z + cy.
+ * loss_lan[g] = mean over the group's F_g x 68 x 2 residuals squared; the joint loss adds
+ * 0.5 mean(id[g]^2) + 0.4 mean(exp[group g]^2).
+ *
+ * Adam (beta 0.9 / 0.999, eps 1e-8, bias correction; torch's arithmetic: fp64 step scalars, fp32 tensors).
+ * m_* / v_* are the moments of pose, exp and id.  state [G,8] fp64 holds per group {steps, beta1^steps,
+ * beta2^steps} of the pose optimizer, the same three of the id / exp optimizer, and the two learning rates
+ * the running segment uses; a fresh optimizer is {0, 1, 1}.  A call runs one constant-learning-rate segment
+ * of n iterations and leaves everything in the buffers, so the next segment continues bit-exactly.
+ *
+ * track_geometry: geo [F,3M] = mu + (id of the frame's group, exp[f]) x basis.
+ * track_fit_pose: n pose-only iterations (id / exp fixed): geometry, then ONE launch in which one wave per
+ *   frame runs all n iterations, then per group the step counters and loss [G].  frame_loss [F]: the frame's sum of
+ *   squared residuals at the last iteration (before its step), loss [G] their mean by the joint iteration's tree; sel [F,16] int32 (may be NULL): its contour choices.
+ * track_fit_joint: n joint iterations, two launches each: per frame (geometry, choice, loss, gradients of
+ *   the 68 chosen points to pose, exp and a d id partial in did [F,id_dim]; pose and exp updated), then per
+ *   group (did and frame_loss summed in a fixed order, id updated, loss [G] = loss_lan, counters advanced).
+ *   loss therefore holds the loss_lan evaluated before the last step.
+ * track_loss_grad: the joint iteration's forward and backward with the updates switched off: loss [G],
+ *   g_id [G,id_dim], g_exp [F,exp_dim], g_pose [F,6] (gradients of the sum over groups of the joint loss).
+ *   Moments may be NULL.
+ * INSTAG_E_ARG before any device work: NULL tensor, P outside 1..64, id_dim / exp_dim outside 1..128,
+ * n_landmarks != 68, G outside 1..16, F outside 1..2^20, an empty group, n < 0.  No host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_track_args {
+  const float* basis;
+  const float* basis_t;
+  const float* mu;
+  const float* lms;
+  float* id;
+  float* exp;
+  float* pose;
+  float* m_pose;
+  float* v_pose;
+  float* m_exp;
+  float* v_exp;
+  float* m_id;
+  float* v_id;
+  double* state;
+  float* geo;        /* workspace [F,3M] */
+  float* did;        /* workspace [F,id_dim] */
+  float* frame_loss; /* [F] */
+  float* loss;       /* [G] */
+  int32_t* sel;      /* [F,16] or NULL */
+  float* g_id;
+  float* g_exp;
+  float* g_pose;
+  const int32_t* group_start; /* (host) [G+1] */
+  const float* focal;         /* (host) [G] */
+  int32_t G, F, id_dim, exp_dim, P, n_landmarks;
+  float cx, cy;
+} instag_track_args;
+int instag_track_max_groups(void);
+int instag_track_geometry(const instag_track_args* args, instag_stream_t stream);
+int instag_track_fit_pose(const instag_track_args* args, int32_t n, double lr, instag_stream_t stream);
+int instag_track_fit_joint(const instag_track_args* args, int32_t n, double lr_pose, double lr_idexp,
+                           instag_stream_t stream);
+int instag_track_loss_grad(const instag_track_args* args, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named
  * kernel with hipEvents on the launch stream; instag_prof_read synchronises those events and
  * returns accumulated milliseconds and launch count since the last reset.

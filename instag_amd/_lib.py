@@ -50,6 +50,15 @@ class FrameUnpackArgs(C.Structure):
                 ("reserved", i32)]
 
 
+class TrackArgs(C.Structure):
+    """struct instag_track_args (include/instag_hip.h)."""
+    _fields_ = [(n, vp) for n in ("basis", "basis_t", "mu", "lms", "id", "exp", "pose", "m_pose", "v_pose", "m_exp",
+                                  "v_exp", "m_id", "v_id", "state", "geo", "did", "frame_loss", "loss", "sel", "g_id",
+                                  "g_exp", "g_pose")] + \
+               [("group_start", C.POINTER(i32)), ("focal", C.POINTER(f32))] + \
+               [(n, i32) for n in ("G", "F", "id_dim", "exp_dim", "P", "n_landmarks")] + [("cx", f32), ("cy", f32)]
+
+
 class WgradJob(C.Structure):
     """struct instag_wgrad_job (include/instag_hip.h)."""
     _fields_ = [("dz", vp), ("inp", vp), ("dw", vp), ("N", i32), ("O", i32), ("K", i32)]
@@ -350,6 +359,11 @@ _PROTOS = {
     "instag_prep_background_workspace_bytes": (sz, [i32, i32, i32]),
     "instag_prep_background": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "instag_prep_frames": (C.c_int, [vp] * 4 + [i32] * 3 + [vp] * 4),
+    "instag_track_max_groups": (C.c_int, []),
+    "instag_track_geometry": (C.c_int, [C.POINTER(TrackArgs), vp]),
+    "instag_track_fit_pose": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, vp]),
+    "instag_track_fit_joint": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, C.c_double, vp]),
+    "instag_track_loss_grad": (C.c_int, [C.POINTER(TrackArgs), vp]),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),
