@@ -949,6 +949,46 @@ int instag_track_fit_joint(const instag_track_args* args, int32_t n, double lr_p
 int instag_track_loss_grad(const instag_track_args* args, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The 3DMM mesh renderer of the photometric tracking stages (instag_amd/mesh_render.py states what it
+ * computes; csrc/mesh_render.hip).  All tensors fp32 on the device unless noted; tris [T,3] and
+ * vert_tris [V,M] int32, face ids [B,H,W,2] int32 (-1: empty slot).  screen [B,V,3] = (u, v, z): pixel
+ * position and depth of every vertex.  Per-vertex and per-pixel evaluation runs in fp64.
+ *
+ *   vertex stage  colours [B,V,3] = texture x SH lighting of the vertex normals taken through vert_tris.
+ *                 The backward overwrites d_rott_geo, d_texture [B,V,3] and d_light [B,27]; d_light is
+ *                 reduced in a fixed order through the workspace (bit-repeatable), d_rott_geo is
+ *                 accumulated with float atomics.
+ *   select        ids of the K = 2 candidate faces of smallest depth per pixel; keys: scratch of
+ *                 B H W 2 64-bit words.
+ *   blend         out [B,H,W,4] = clamp((rgb, alpha), 0, 255); the backward overwrites d_screen and
+ *                 d_colours [B,V,3] (float atomics).
+ *
+ * INSTAG_E_ARG before any device work: NULL pointer, odd W, K != 2, sizes out of range, settings out
+ * of range; INSTAG_E_SPACE for a short workspace.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_mesh_settings {
+  int32_t H, W, K, reserved;
+  double sigma, gamma, blur_radius, znear, zfar, eps;
+  double bg_r, bg_g, bg_b;
+} instag_mesh_settings;
+int instag_mesh_vertex_forward(const float* rott_geo, const float* texture, const float* light, const int32_t* tris,
+                               const int32_t* vert_tris, int32_t B, int32_t V, int32_t T, int32_t M, float* colours,
+                               instag_stream_t stream);
+size_t instag_mesh_vertex_backward_workspace_bytes(int32_t B, int32_t V);
+int instag_mesh_vertex_backward(const float* rott_geo, const float* texture, const float* light, const int32_t* tris,
+                                const int32_t* vert_tris, const float* d_colours, int32_t B, int32_t V, int32_t T, int32_t M,
+                                float* d_rott_geo, float* d_texture, float* d_light, void* workspace, size_t workspace_bytes,
+                                instag_stream_t stream);
+int instag_mesh_select(const instag_mesh_settings* settings, const float* screen, const int32_t* tris, int32_t B, int32_t V,
+                       int32_t T, void* keys, int32_t* ids, instag_stream_t stream);
+int instag_mesh_blend_forward(const instag_mesh_settings* settings, const float* screen, const float* colours,
+                              const int32_t* tris, const int32_t* ids, int32_t B, int32_t V, int32_t T, float* out,
+                              instag_stream_t stream);
+int instag_mesh_blend_backward(const instag_mesh_settings* settings, const float* screen, const float* colours,
+                               const int32_t* tris, const int32_t* ids, const float* d_out, int32_t B, int32_t V, int32_t T,
+                               float* d_screen, float* d_colours, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing (bench.py roofline leg).  When enabled, the launcher brackets the named
  * kernel with hipEvents on the launch stream; instag_prof_read synchronises those events and
  * returns accumulated milliseconds and launch count since the last reset.

@@ -59,6 +59,12 @@ class TrackArgs(C.Structure):
                [(n, i32) for n in ("G", "F", "id_dim", "exp_dim", "P", "n_landmarks")] + [("cx", f32), ("cy", f32)]
 
 
+class MeshSettings(C.Structure):
+    """struct instag_mesh_settings (include/instag_hip.h)."""
+    _fields_ = [(n, i32) for n in ("H", "W", "K", "reserved")] + \
+               [(n, C.c_double) for n in ("sigma", "gamma", "blur_radius", "znear", "zfar", "eps", "bg_r", "bg_g", "bg_b")]
+
+
 class WgradJob(C.Structure):
     """struct instag_wgrad_job (include/instag_hip.h)."""
     _fields_ = [("dz", vp), ("inp", vp), ("dw", vp), ("N", i32), ("O", i32), ("K", i32)]
@@ -364,6 +370,12 @@ _PROTOS = {
     "instag_track_fit_pose": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, vp]),
     "instag_track_fit_joint": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, C.c_double, vp]),
     "instag_track_loss_grad": (C.c_int, [C.POINTER(TrackArgs), vp]),
+    "instag_mesh_vertex_forward": (C.c_int, [vp] * 5 + [i32] * 4 + [vp, vp]),
+    "instag_mesh_vertex_backward_workspace_bytes": (sz, [i32, i32]),
+    "instag_mesh_vertex_backward": (C.c_int, [vp] * 6 + [i32] * 4 + [vp] * 4 + [sz, vp]),
+    "instag_mesh_select": (C.c_int, [C.POINTER(MeshSettings), vp, vp, i32, i32, i32, vp, vp, vp]),
+    "instag_mesh_blend_forward": (C.c_int, [C.POINTER(MeshSettings), vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "instag_mesh_blend_backward": (C.c_int, [C.POINTER(MeshSettings), vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "instag_prof_enable": (C.c_int, [C.c_int]),
     "instag_prof_reset": (C.c_int, []),
     "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

@@ -53,6 +53,7 @@ SOURCES = {
     "frames.hip": ["-ffp-contract=off"],
     "prepare.hip": [],
     "track.hip": [],
+    "mesh_render.hip": [],
 }
 
 

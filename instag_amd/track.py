@@ -16,11 +16,11 @@ same launches.
 ``*_torch`` state in plain torch (any device, fp32 or fp64) what the kernels compute; they serve a CPU device and are
 the reference of the GPU tests.
 
+The two photometric stages that follow (face_tracker.py:207-406: light fit, frame-wise fine fit) are in mesh_render.py
+and run with ``track_identity(..., photometric=True)``; without it the poses written are the reference's poses as they
+stand at its line 205.
+
 Stated deviations from the reference:
-  * the two photometric stages that follow (face_tracker.py:207-406: light fit, frame-wise fine fit) are not built: they
-    need a differentiable mesh renderer with SH lighting.  The focal length is final after the landmark stages and
-    save_transforms reads only focal, euler and trans, so the poses written here are the reference's poses as they
-    stand at its line 205, not the photometrically refined ones.
   * frames are the ``<i>.lms`` files in ascending numeric order (the reference walks range(frame_num), frame_num being
     the number of jpgs: the same frames whenever the ids are dense).
   * the kernels fold sig_id / sig_exp into the basis rows and rotate by Rz, Ry, Rx in turn instead of by their product:
@@ -47,12 +47,14 @@ TRANS_Z0 = -7.0
 
 # ---- the model -----------------------------------------------------------------------------------------------------------
 class Face3DMM:
-    """What facemodel.py:15-47 loads, minus texture: base_id [id_dim,3N], base_exp [exp_dim,3N], mu [3N] (mu_shape +
+    """What facemodel.py:15-47 loads (texture, rigid_ids and the topology of render_3dmm.py:97-101 are optional keyword
+    arguments: a model without them still serves the landmark fit): base_id [id_dim,3N], base_exp [exp_dim,3N], mu [3N] (mu_shape +
     mu_exp, centred per axis; all three / 1e5), sig_id, sig_exp, keyinds [68], left_contour, right_contour [8,P] (host,
     fp64 / int64).  ``points`` [M] lists the M = 68 + 16 P model points the landmark fit touches (keyinds, the left
     candidates slot-major, the right ones); only their basis rows go to a device."""
 
-    def __init__(self, base_id, base_exp, mu, sig_id, sig_exp, keyinds, left_contour, right_contour):
+    def __init__(self, base_id, base_exp, mu, sig_id, sig_exp, keyinds, left_contour, right_contour, *, base_tex=None,
+                 mu_tex=None, sig_tex=None, rigid_ids=None, tris=None, vert_tris=None):
         self.base_id, self.base_exp, self.mu = (np.asarray(a, dtype=np.float64) for a in (base_id, base_exp, mu))
         self.sig_id, self.sig_exp = np.asarray(sig_id, dtype=np.float64), np.asarray(sig_exp, dtype=np.float64)
         self.keyinds = np.asarray(keyinds, dtype=np.int64).reshape(-1)
@@ -79,23 +81,89 @@ class Face3DMM:
             raise ValueError("point index outside the model")
         self.M = int(self.points.shape[0])
         self._cache = {}
+        self.N = n3 // 3
+        # texture and topology (facemodel.py:30-35, :47; render_3dmm.py:97-101): only the photometric stages read them
+        self.base_tex = self.mu_tex = self.sig_tex = self.rigid_ids = self.tris = self.vert_tris = None
+        self.tex_dim = 0
+        if base_tex is not None:
+            self.base_tex, self.mu_tex = np.asarray(base_tex, dtype=np.float64), np.asarray(mu_tex, dtype=np.float64).reshape(-1)
+            self.sig_tex = np.asarray(sig_tex, dtype=np.float64).reshape(-1)
+            self.tex_dim = int(self.base_tex.shape[0])
+            if self.base_tex.shape != (self.tex_dim, n3) or self.mu_tex.shape != (n3,) or self.sig_tex.shape != (self.tex_dim,):
+                raise ValueError("base_tex [tex_dim,3N], mu_tex [3N], sig_tex [tex_dim]")
+        if rigid_ids is not None:
+            self.rigid_ids = np.asarray(rigid_ids, dtype=np.int64).reshape(-1)
+            if self.rigid_ids.size == 0 or self.rigid_ids.min() < 0 or self.rigid_ids.max() >= self.N:
+                raise ValueError("rigid_ids outside the model")
+        if tris is not None:
+            self.tris, self.vert_tris = np.asarray(tris, dtype=np.int64), np.asarray(vert_tris, dtype=np.int64)
+            if self.tris.ndim != 2 or self.tris.shape[1] != 3 or self.tris.shape[0] < 1 or self.tris.min() < 0 or \
+                    self.tris.max() >= self.N:
+                raise ValueError("tris must be [T,3] with vertex indices in [0, N)")
+            T = self.tris.shape[0]
+            # vert_tris is used literally (render_3dmm.py:109): no padding rule is assumed, so every entry must name a triangle
+            if self.vert_tris.ndim != 2 or self.vert_tris.shape[0] != self.N or self.vert_tris.shape[1] < 1 or \
+                    self.vert_tris.min() < 0 or self.vert_tris.max() >= T:
+                raise ValueError(f"vert_tris must be [N,M] with every entry in [0, {T})")
+
+    has_texture = property(lambda self: self.base_tex is not None)
+    has_topology = property(lambda self: self.tris is not None)
 
     @classmethod
-    def from_arrays(cls, info: dict, keys: dict, id_dim: int = 100, exp_dim: int = 79):
-        """info: the 3DMM_info dictionary (b_shape, mu_shape, b_exp, mu_exp, sig_shape, sig_exp); keys: keys_info
-        (keyinds, left_contour, right_contour)."""
+    def from_arrays(cls, info: dict, keys: dict, id_dim: int = 100, exp_dim: int = 79, *, topo: dict = None,
+                    tex_dim: int = 100):
+        """info: the 3DMM_info dictionary (b_shape, mu_shape, b_exp, mu_exp, sig_shape, sig_exp; b_tex, mu_tex, sig_tex
+        if it has them); keys: keys_info (keyinds, left_contour, right_contour; rigid_ids if it has them); topo:
+        topology_info (tris, vert_tris) or None."""
+        extra = {}
+        if "b_tex" in info:
+            extra.update(base_tex=np.asarray(info["b_tex"], dtype=np.float64)[:tex_dim], mu_tex=info["mu_tex"],
+                         sig_tex=np.asarray(info["sig_tex"]).reshape(-1)[:tex_dim])
+        if "rigid_ids" in keys:
+            extra.update(rigid_ids=keys["rigid_ids"])
+        if topo is not None:
+            extra.update(tris=topo["tris"], vert_tris=topo["vert_tris"])
         mu = (np.asarray(info["mu_shape"], dtype=np.float64) + np.asarray(info["mu_exp"], dtype=np.float64)).reshape(-1, 3)
         mu = (mu - mu.mean(axis=0, keepdims=True)).reshape(-1)
         return cls(np.asarray(info["b_shape"], dtype=np.float64)[:id_dim] / 1e5,
                    np.asarray(info["b_exp"], dtype=np.float64)[:exp_dim] / 1e5, mu / 1e5,
                    np.asarray(info["sig_shape"]).reshape(-1)[:id_dim], np.asarray(info["sig_exp"]).reshape(-1)[:exp_dim],
-                   keys["keyinds"], keys["left_contour"], keys["right_contour"])
+                   keys["keyinds"], keys["left_contour"], keys["right_contour"], **extra)
 
     @classmethod
-    def load(cls, directory, id_dim: int = 100, exp_dim: int = 79):
+    def load(cls, directory, id_dim: int = 100, exp_dim: int = 79, *, tex_dim: int = 100):
         info = np.load(os.path.join(directory, "3DMM_info.npy"), allow_pickle=True).item()
         keys = np.load(os.path.join(directory, "keys_info.npy"), allow_pickle=True).item()
-        return cls.from_arrays(info, keys, id_dim, exp_dim)
+        topo = os.path.join(directory, "topology_info.npy")
+        topo = np.load(topo, allow_pickle=True).item() if os.path.exists(topo) else None
+        return cls.from_arrays(info, keys, id_dim, exp_dim, topo=topo, tex_dim=tex_dim)
+
+    def full_tensors(self, device, dtype):
+        """(base_id [I,3N], base_exp [E,3N], mu [3N], sig_id, sig_exp) of the whole mesh, for the photometric stages."""
+        key = ("full", str(device), dtype)
+        if key not in self._cache:
+            self._cache[key] = tuple(torch.as_tensor(a, dtype=dtype, device=device) for a in
+                                     (self.base_id, self.base_exp, self.mu, self.sig_id, self.sig_exp))
+        return self._cache[key]
+
+    def texture_tensors(self, device, dtype):
+        """(base_tex [tex_dim,3N], mu_tex [3N], sig_tex [tex_dim])."""
+        if not self.has_texture:
+            raise ValueError("this Face3DMM was loaded without texture (b_tex, mu_tex, sig_tex of 3DMM_info)")
+        key = ("tex", str(device), dtype)
+        if key not in self._cache:
+            self._cache[key] = tuple(torch.as_tensor(a, dtype=dtype, device=device) for a in
+                                     (self.base_tex, self.mu_tex, self.sig_tex))
+        return self._cache[key]
+
+    def topology_tensors(self, device):
+        """(tris [T,3], vert_tris [N,M]) int64."""
+        if not self.has_topology:
+            raise ValueError("this Face3DMM was loaded without topology (tris, vert_tris of topology_info.npy)")
+        key = ("topo", str(device))
+        if key not in self._cache:
+            self._cache[key] = tuple(torch.as_tensor(a, dtype=torch.int64, device=device) for a in (self.tris, self.vert_tris))
+        return self._cache[key]
 
     def _columns(self):
         return (3 * self.points[:, None] + np.arange(3)[None, :]).reshape(-1)
@@ -536,13 +604,24 @@ def _image_size(ori_imgs_dir):
 
 
 def track_identity(path, model, device="cuda", write=True, h=None, w=None, focals=FOCALS, every=40,
-                   focal_iters=(2000, 2500), coarse_iters=(1500, 2000)):
+                   focal_iters=(2000, 2500), coarse_iters=(1500, 2000), photometric=False, photo_batch=32, light_iters=71,
+                   fine_iters=50, **render_settings):
     """ori_imgs/<i>.lms of ``path`` -> {"id" [1,I], "exp" [F,E], "euler" [F,3], "trans" [F,3], "focal" [1]} (CPU fp32:
     the keys and shapes of the reference's track_params.pt).  ``write``: also track_params.pt and the two transforms
     files.  h, w: the image size (default: read from the first ori_imgs/*.jpg).  The iteration counts default to the
-    reference's; a CPU device runs the plain statements."""
+    reference's; a CPU device runs the plain statements.  ``photometric``: also the light fit and the frame-wise fine fit
+    against ``ori_imgs/<i>.jpg`` (mesh_render.py; face_tracker.py:207-406), which need a model with texture, rigid_ids and
+    topology and at least ``photo_batch`` frames; ``render_settings`` (sigma, gamma, blur_radius, ...) go to the renderer."""
     ori = os.path.join(path, "ori_imgs")
-    lms, _ = read_landmarks(ori)
+    lms, frame_ids = read_landmarks(ori)
+    if photometric:
+        from . import mesh_render
+        if not (model.has_texture and model.has_topology) or model.rigid_ids is None:
+            raise ValueError("photometric=True needs a Face3DMM with texture (b_tex, mu_tex, sig_tex), rigid_ids and topology "
+                             "(topology_info.npy)")
+        if len(frame_ids) < photo_batch:
+            raise ValueError(f"photometric=True needs at least {photo_batch} frames, got {len(frame_ids)}")
+        images = mesh_render.jpg_loader(ori, frame_ids)
     if h is None or w is None:
         h, w = _image_size(ori)
     device = torch.device(device)
@@ -552,6 +631,9 @@ def track_identity(path, model, device="cuda", write=True, h=None, w=None, focal
         params = _params(tracker.coarse_fit(lms, focal, h, w, coarse_iters), focal)
     else:
         params = track_torch(model, lms, h, w, focals, every, focal_iters, coarse_iters, device)
+    if photometric:
+        params = mesh_render.refine(model, params, lms, images, h, w, device, photo_batch, light_iters, fine_iters,
+                                    **render_settings)
     if write:
         torch.save(params, os.path.join(path, "track_params.pt"))
         save_transforms(path, params, h, w)
