@@ -28,6 +28,9 @@ COMMON = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-fno-gpu-rdc"
 
 # per-file extra flags.  raster_preprocess must not fuse mul+add: its integer outputs (radii, tile
 # rectangles, sort keys) are checked bit-for-bit against the CPU oracle.
+# The helpers of csrc/device_math.hpp are inlined and so take the flags of the file that includes them: a kernel keeps
+# its rounding only while it stays in its file.  Do not merge look-alike kernels across files whose flags differ
+# (mouth_activate in glue.hip contracts to FMAs, pretrain_mouth_deform in the contract-off pretrain.hip does not).
 SOURCES = {
     "raster_preprocess.hip": ["-ffp-contract=off"],
     # raster_blend: SLP pairing of scalars ACROSS Gaussians costs a dozen v_mov per group of four in the forward loop

@@ -22,6 +22,7 @@
 // Frame are 16-byte aligned exactly when H*W % 4 == 0 (float4 stores); otherwise a plane is only 4-byte aligned and
 // the four values go out one by one, the last group of a plane only as far as the plane reaches.
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
@@ -117,8 +118,7 @@ __global__ void __launch_bounds__(256) frame_ingest_kernel(IngestArgs A) {
     reinterpret_cast<uint32_t*>(fr + 2 * P3)[g] = mask;
   }
   // (uniform from here: every lane of the wave takes part in the butterfly; at most 4 * 64 = 256 < 1024 per field)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) packed += __shfl_xor(packed, o);
+  packed = wave_sum(packed);
   if ((threadIdx.x & 63) == 0 && packed != 0u) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {

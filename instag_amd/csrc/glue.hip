@@ -11,6 +11,7 @@
 //                     rotations = normalize(rotation + h[:,3:7]), opacity = sigmoid(opacity_raw)
 //  motion_l1_reg    train_face.py:510-514: sum of the five mean-|.| regularisers of the motion outputs
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
@@ -152,11 +153,7 @@ motion_glue_backward_kernel(GlueDims d, const float* __restrict__ d_h_in, const 
   }
 }
 
-// ---- deform + activations ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(__expf(x)); }
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
-
+// ---- deform + activations (the activations themselves: device_math.hpp) -------------------------------------------
 __global__ void __launch_bounds__(GB)
 deform_activate_forward_kernel(int N, const float* __restrict__ xyz, const float* __restrict__ scaling,
                                const float* __restrict__ rotation, const float* __restrict__ opacity,
@@ -173,15 +170,13 @@ deform_activate_forward_kernel(int N, const float* __restrict__ xyz, const float
     for (int k = 0; k < 3; ++k) {
       const float ps = tanhf(pr[3 + k] * 0.2f) * 0.25f + 1.0f;
       means3D[3 * r + k] = xyz[3 * r + k] + (hr[k] * 1e-2f) * ps;
-      scales[3 * r + k] = softplus_f(scaling[3 * r + k] + hr[8 + k]);
+      scales[3 * r + k] = softplus(scaling[3 * r + k] + hr[8 + k]);
     }
     float q[4], n2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { q[k] = rotation[4 * r + k] + hr[3 + k]; n2 += q[k] * q[k]; }
-    const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rots[4 * r + k] = q[k] * inv;
-    opac[r] = sigmoid_f(opacity[r]);
+    quat_normalize(q, n2, rots + 4 * r);
+    opac[r] = sigmoid(opacity[r]);
     if (reg_partials) {
       // the motion regulariser of train_face.py:510-514 rides along.  Its d_xyz term sees the displacement AFTER the
       // reference's in-place d_xyz *= p_scale (gaussian_renderer/__init__.py:217 mutates the returned dictionary's
@@ -196,11 +191,8 @@ deform_activate_forward_kernel(int N, const float* __restrict__ xyz, const float
     }
   }
   if (reg_partials) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) reg += __shfl_xor(reg, o);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = reg;
-    __syncthreads();
-    if (threadIdx.x == 0) reg_partials[blockIdx.x] = reg_weight * (((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]);
+    reg = block_sum_256(reg, s_red);
+    if (threadIdx.x == 0) reg_partials[blockIdx.x] = reg_weight * reg;
   }
 }
 
@@ -215,20 +207,18 @@ mouth_activate_forward_kernel(int N, const float* __restrict__ xyz, const float*
                               float* __restrict__ rots, float* __restrict__ opac) {
   const int r = blockIdx.x * GB + threadIdx.x;
   if (r >= N) return;
-  const float sg = sigmoid_f(hs[r]);
+  const float sg = sigmoid(hs[r]);
   const float xs[3] = {sx, sy, sz};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     means3D[3 * r + k] = xyz[3 * r + k] + ((h[(size_t)r * 7 + k] * xs[k]) * sg) * 2.0f;
-    scales[3 * r + k] = softplus_f(scaling[3 * r + k]);
+    scales[3 * r + k] = softplus(scaling[3 * r + k]);
   }
   float q[4], n2 = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) { q[k] = rotation[4 * r + k]; n2 += q[k] * q[k]; }
-  const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) rots[4 * r + k] = q[k] * inv;
-  opac[r] = sigmoid_f(opacity[r]);
+  quat_normalize(q, n2, rots + 4 * r);
+  opac[r] = sigmoid(opacity[r]);
 }
 
 __global__ void __launch_bounds__(GB)
@@ -242,37 +232,29 @@ mouth_activate_backward_kernel(int N, const float* __restrict__ scaling, const f
                                float* __restrict__ d_hs /*[N,1]*/) {
   const int r = blockIdx.x * GB + threadIdx.x;
   if (r >= N) return;
-  const float sg = sigmoid_f(hs[r]);
+  const float sg = sigmoid(hs[r]);
   const float xs[3] = {sx, sy, sz};
   float dgate = 0.f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const float gm = g_means ? g_means[3 * r + k] : 0.f;
+    const float gm = load_or_zero(g_means, 3 * r + k);
     d_xyz[3 * r + k] = gm;
     d_h[(size_t)r * 7 + k] = gm * 2.0f * sg * xs[k];
     dgate += gm * 2.0f * (h[(size_t)r * 7 + k] * xs[k]);
-    const float gs = g_scales ? g_scales[3 * r + k] : 0.f;
-    d_scaling[3 * r + k] = gs * sigmoid_f(scaling[3 * r + k]);           // d softplus = sigmoid
+    d_scaling[3 * r + k] = load_or_zero(g_scales, 3 * r + k) * sigmoid(scaling[3 * r + k]);   // d softplus = sigmoid
   }
 #pragma unroll
   for (int k = 3; k < 7; ++k) d_h[(size_t)r * 7 + k] = 0.f;            // d_rot is not applied by the mouth render
   d_hs[r] = dgate * sg * (1.f - sg);
-  float q[4], n2 = 0.f, dot = 0.f, gr[4];
+  float q[4], gr[4], n2 = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     q[k] = rotation[4 * r + k];
     n2 += q[k] * q[k];
-    gr[k] = g_rots ? g_rots[4 * r + k] : 0.f;
+    gr[k] = load_or_zero(g_rots, 4 * r + k);
   }
-  const float nrm = sqrtf(n2);
-  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) dot += gr[k] * q[k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    d_rotation[4 * r + k] = nrm > 1e-12f ? (gr[k] - q[k] * inv * dot * inv) * inv : gr[k] * inv;
-  const float so = sigmoid_f(opacity[r]);
-  d_opacity[r] = (g_opac ? g_opac[r] : 0.f) * so * (1.f - so);
+  quat_normalize_backward(q, n2, gr, d_rotation + 4 * r);
+  d_opacity[r] = sigmoid_backward(load_or_zero(g_opac, r), opacity[r]);
 }
 
 // ---- mean |x[:, :ncols] * scale| as per-workgroup partial sums (train_mouth.py:203 `p_xyz.abs().mean()` on the raw
@@ -287,11 +269,8 @@ abs_mean_forward_kernel(int N, int stride, int ncols, float scale, const float* 
   float acc = 0.f;
   for (int r = blockIdx.x * GB + threadIdx.x; r < N; r += gridDim.x * GB)
     for (int c = 0; c < ncols; ++c) acc += fabsf(x[(size_t)r * stride + c] * scale);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = w * (((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]);
+  acc = block_sum_256(acc, s_red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = w * acc;
 }
 
 __global__ void __launch_bounds__(GB)
@@ -418,37 +397,27 @@ deform_activate_backward_kernel(int N, const float* __restrict__ scaling, const 
   for (int k = 0; k < 6; ++k) dp[k] = 0.f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const float gm = g_means ? g_means[3 * r + k] : 0.f;
+    const float gm = load_or_zero(g_means, 3 * r + k);
     const float th = tanhf(pr[3 + k] * 0.2f);
     const float ps = th * 0.25f + 1.0f;
     d_xyz[3 * r + k] = gm;
     dh[k] = gm * ps * 1e-2f;
     dp[3 + k] = gm * (hr[k] * 1e-2f) * 0.25f * (1.f - th * th) * 0.2f;
-    const float gs = g_scales ? g_scales[3 * r + k] : 0.f;
-    const float sg = gs * sigmoid_f(scaling[3 * r + k] + hr[8 + k]);      // d softplus = sigmoid
+    const float sg = load_or_zero(g_scales, 3 * r + k) * sigmoid(scaling[3 * r + k] + hr[8 + k]);   // d softplus = sigmoid
     d_scaling[3 * r + k] = sg;
     dh[8 + k] = sg;
   }
-  float q[4], n2 = 0.f, dot = 0.f, gr[4];
+  float q[4], gr[4], n2 = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     q[k] = rotation[4 * r + k] + hr[3 + k];
     n2 += q[k] * q[k];
-    gr[k] = g_rots ? g_rots[4 * r + k] : 0.f;
+    gr[k] = load_or_zero(g_rots, 4 * r + k);
   }
-  const float nrm = sqrtf(n2);
-  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+  quat_normalize_backward(q, n2, gr, dh + 3);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) dot += gr[k] * q[k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    // y = q / max(|q|, eps):  dq = (g - y <g, y>) / |q|   (for |q| > eps)
-    const float dq = nrm > 1e-12f ? (gr[k] - q[k] * inv * dot * inv) * inv : gr[k] * inv;
-    d_rotation[4 * r + k] = dq;
-    dh[3 + k] = dq;
-  }
-  const float so = sigmoid_f(opacity[r]);
-  d_opacity[r] = (g_opac ? g_opac[r] : 0.f) * so * (1.f - so);
+  for (int k = 0; k < 4; ++k) d_rotation[4 * r + k] = dh[3 + k];
+  d_opacity[r] = sigmoid_backward(load_or_zero(g_opac, r), opacity[r]);
   if (g_reg) {
     const float go = g_reg[0] * reg_weight;
     const float w_xyz = go * 1e-2f / (3.f * N), w_rot = go / (4.f * N), w_opa = go / (float)N, w_sc = go / (3.f * N);
@@ -487,11 +456,8 @@ motion_l1_reg_forward_kernel(int N, const float* __restrict__ h, const float* __
     acc += w_sc * (fabsf(hr[8]) + fabsf(hr[9]) + fabsf(hr[10]));
     acc += w_xyz * (fabsf(pr[0]) + fabsf(pr[1]) + fabsf(pr[2]));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+  acc = block_sum_256(acc, s_red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 __global__ void __launch_bounds__(GB)

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
@@ -275,8 +276,7 @@ grid_backward_kernel(const float* __restrict__ grad, const float* __restrict__ i
       const float gv = grad[(size_t)l * B * C + i];
       gmax = fmaxf(gmax, gv != gv ? INFINITY : fabsf(gv));
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
+  gmax = wave_max(gmax);
   if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = gmax;
   __syncthreads();
   gmax = s_wmax[0];
@@ -827,8 +827,7 @@ triplane_backward_kernel(TriPlaneArgs a, const float* __restrict__ grad /*[N,3L]
 #pragma unroll 4
     for (uint32_t k = 0; k < 3 * a.L; ++k) gmax = fmaxf(gmax, fabsf(g[k]));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
+  gmax = wave_max(gmax);
   if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = gmax;
   __syncthreads();
   gmax = s_wmax[0];
@@ -959,8 +958,7 @@ triplane_backward_cached_kernel(TriPlaneArgs a, const float* __restrict__ grad /
 #pragma unroll
     for (int k = 0; k < 3 * LC; ++k) gc[k] = 0.f;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
+  gmax = wave_max(gmax);
   if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = gmax;
   __syncthreads();
   gmax = s_wmax[0];
@@ -1221,8 +1219,7 @@ triplane_level_backward_kernel(TriPlaneArgs a, const float* __restrict__ grad /*
   const float* __restrict__ gcol = grad + (size_t)plane * a.L + level;
   float gmax = 0.f;
   for (uint32_t b = b0 + threadIdx.x; b < b1; b += TPL_BLOCK) gmax = fmaxf(gmax, fabsf(gcol[(size_t)b * 3 * a.L]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
+  gmax = wave_max(gmax);
   if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = gmax;
   for (uint32_t i = threadIdx.x; i < cells; i += TPL_BLOCK) s_lvl[i] = 0ull;
   __syncthreads();

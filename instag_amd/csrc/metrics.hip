@@ -17,6 +17,7 @@
 // instag_infer_compose: synthesize_fuse.py:65-76 in one forward-only launch -- the optional dilation of the mouth alpha
 // (a running maximum from an LDS tile), both compositions, the clamp and the 8-bit frame.
 #include "common.hpp"
+#include "device_math.hpp"
 
 #include <cmath>
 
@@ -46,12 +47,6 @@ __device__ __forceinline__ float quantise(float x) {
 __device__ __forceinline__ float prepare(float v, bool clamp, bool quant) {
   if (quant) return quantise(v);
   return clamp ? fminf(fmaxf(v, 0.f), 1.f) : v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // partials [B][3][tiles][3] doubles: (SSIM map sum, sum |d|, sum d^2) of one tile of one channel of one frame

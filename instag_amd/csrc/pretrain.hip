@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
@@ -32,10 +33,6 @@ namespace {
 constexpr int PB = 256;
 constexpr int PRETRAIN_MAX_OTHERS = 15;
 struct OtherHeads { const float* h[PRETRAIN_MAX_OTHERS]; };
-
-__device__ __forceinline__ float sgn_f(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-__device__ __forceinline__ float softplus_pf(float x) { return x > 20.f ? x : log1pf(__expf(x)); }
-__device__ __forceinline__ float sigmoid_pf(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // c_j = sum_c (h_j[c] * 1e-2) * (h_p[c] * 1e-2), evaluated like the reference: both displacements scaled, multiplied,
 // the three products added left to right; no contraction into fused multiply-adds
@@ -64,7 +61,7 @@ pretrain_deform_forward_kernel(int N, const float* __restrict__ xyz, const float
       dx[k] = __fadd_rn(__fmul_rn(u[k], 1e-2f), __fmul_rn(p[k], 1e-2f));
       ds[k] = u[8 + k] + p[8 + k];
       means3D[3 * r + k] = xyz[3 * r + k] + dx[k];
-      scales[3 * r + k] = softplus_pf(scaling[3 * r + k] + ds[k]);
+      scales[3 * r + k] = softplus(scaling[3 * r + k] + ds[k]);
     }
     float dr[4];
 #pragma unroll
@@ -73,10 +70,12 @@ pretrain_deform_forward_kernel(int N, const float* __restrict__ xyz, const float
       q[k] = rotation[4 * r + k] + dr[k];
       n2 += q[k] * q[k];
     }
-    const float den = fmaxf(sqrtf(n2), 1e-12f);
+    // this kernel DIVIDES by the clamped norm where quat_normalize multiplies by its reciprocal.  The two round
+    // differently: keep the division, or the pretraining step's bits change
+    const float den = fmaxf(sqrtf(n2), QUAT_EPS);
 #pragma unroll
     for (int k = 0; k < 4; ++k) rots[4 * r + k] = q[k] / den;
-    opac[r] = sigmoid_pf(opacity[r]);
+    opac[r] = sigmoid(opacity[r]);
     if (reg_partials) {
       const float w3 = 1e-5f / (3.f * N), w4 = 1e-5f / (4.f * N), w1 = 1e-5f / (float)N;
       const float umf = w3 * (fabsf(dx[0]) + fabsf(dx[1]) + fabsf(dx[2])) + w4 * (fabsf(dr[0]) + fabsf(dr[1]) + fabsf(dr[2]) + fabsf(dr[3]))
@@ -90,11 +89,8 @@ pretrain_deform_forward_kernel(int N, const float* __restrict__ xyz, const float
     }
   }
   if (reg_partials) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) reg += __shfl_xor(reg, o);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = reg;
-    __syncthreads();
-    if (threadIdx.x == 0) reg_partials[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    reg = block_sum_256(reg, s_red);
+    if (threadIdx.x == 0) reg_partials[blockIdx.x] = reg;
   }
 }
 
@@ -120,59 +116,51 @@ pretrain_deform_backward_kernel(int N, const float* __restrict__ scaling, const 
   for (int k = 0; k < 3; ++k) {
     dx[k] = __fadd_rn(__fmul_rn(u[k], 1e-2f), __fmul_rn(p[k], 1e-2f));
     ds[k] = u[8 + k] + p[8 + k];
-    const float gm = g_means ? g_means[3 * r + k] : 0.f;
+    const float gm = load_or_zero(g_means, 3 * r + k);
     d_xyz[3 * r + k] = gm;
     du[k] = gm * 1e-2f;
     dp[k] = gm * 1e-2f;
-    const float gs = g_scales ? g_scales[3 * r + k] : 0.f;
-    const float sg = gs * sigmoid_pf(scaling[3 * r + k] + ds[k]);      // d softplus = sigmoid
+    const float sg = load_or_zero(g_scales, 3 * r + k) * sigmoid(scaling[3 * r + k] + ds[k]);      // d softplus = sigmoid
     d_scaling[3 * r + k] = sg;
     du[8 + k] = sg;
     dp[8 + k] = sg;
   }
-  float q[4], dr[4], gr[4], n2 = 0.f, dot = 0.f;
+  float q[4], dr[4], gr[4], n2 = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     dr[k] = u[3 + k] + p[3 + k];
     q[k] = rotation[4 * r + k] + dr[k];
     n2 += q[k] * q[k];
-    gr[k] = g_rots ? g_rots[4 * r + k] : 0.f;
+    gr[k] = load_or_zero(g_rots, 4 * r + k);
   }
-  const float nrm = sqrtf(n2);
-  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) dot += gr[k] * q[k];
+  quat_normalize_backward(q, n2, gr, du + 3);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    // y = q / max(|q|, eps):  dq = (g - y <g, y>) / |q|   (for |q| > eps)
-    const float dq = nrm > 1e-12f ? (gr[k] - q[k] * inv * dot * inv) * inv : gr[k] * inv;
-    d_rotation[4 * r + k] = dq;
-    du[3 + k] = dq;
-    dp[3 + k] = dq;
+    d_rotation[4 * r + k] = du[3 + k];
+    dp[3 + k] = du[3 + k];
   }
-  const float so = sigmoid_pf(opacity[r]);
-  d_opacity[r] = (g_opac ? g_opac[r] : 0.f) * so * (1.f - so);
+  d_opacity[r] = sigmoid_backward(load_or_zero(g_opac, r), opacity[r]);
   if (g_reg) {
     const float go = g_reg[0];
     const float w3 = go * 1e-5f / (3.f * N), w4 = go * 1e-5f / (4.f * N), w1 = go * 1e-5f / (float)N;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       // UMF d_xyz (= the sum of both fields' displacements): |.| passes sgn * 1e-2 to both heads
-      const float gx = w3 * sgn_f(dx[k]) * 1e-2f;
+      const float gx = w3 * sgn(dx[k]) * 1e-2f;
       du[k] += gx;
-      dp[k] += gx + w3 * sgn_f(p[k]) * 1e-2f;
-      const float gsc = w3 * sgn_f(ds[k]);
+      dp[k] += gx + w3 * sgn(p[k]) * 1e-2f;
+      const float gsc = w3 * sgn(ds[k]);
       du[8 + k] += gsc;
-      dp[8 + k] += gsc + w3 * sgn_f(p[8 + k]);
+      dp[8 + k] += gsc + w3 * sgn(p[8 + k]);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float grt = w4 * sgn_f(dr[k]);
+      const float grt = w4 * sgn(dr[k]);
       du[3 + k] += grt;
-      dp[3 + k] += grt + w4 * sgn_f(p[3 + k]);
+      dp[3 + k] += grt + w4 * sgn(p[3 + k]);
     }
-    du[7] += w1 * sgn_f(u[7]);
-    dp[7] += w1 * sgn_f(p[7]);
+    du[7] += w1 * sgn(u[7]);
+    dp[7] += w1 * sgn(p[7]);
     // contrast: the reference zeroes the entries < 0 in place, so the gradient passes where c_j >= 0
     const float wc = go / (float)N;
     for (int j = 0; j < n_others; ++j) {
@@ -206,22 +194,20 @@ pretrain_mouth_deform_forward_kernel(int N, const float* __restrict__ xyz, const
     float u[7], p[7];
 #pragma unroll
     for (int k = 0; k < 7; ++k) { u[k] = h[(size_t)r * 7 + k]; p[k] = hp[(size_t)r * 7 + k]; }
-    const float sg = sigmoid_pf(hs[r]);
+    const float sg = sigmoid(hs[r]);
     const float xs[3] = {sx, sy, sz};
     float dx[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       dx[k] = ((u[k] * xs[k]) * sg) * 2.0f + p[k] * 1e-2f;          // (no contraction: -ffp-contract=off)
       means3D[3 * r + k] = xyz[3 * r + k] + dx[k];
-      scales[3 * r + k] = softplus_pf(scaling[3 * r + k]);
+      scales[3 * r + k] = softplus(scaling[3 * r + k]);
     }
     float q[4], n2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { q[k] = rotation[4 * r + k]; n2 += q[k] * q[k]; }
-    const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rots[4 * r + k] = q[k] * inv;
-    opac[r] = sigmoid_pf(opacity[r]);
+    quat_normalize(q, n2, rots + 4 * r);
+    opac[r] = sigmoid(opacity[r]);
     if (reg_partials) {
       const float w3 = 1e-5f / (3.f * N), w4 = 1e-5f / (4.f * N);
       const float umf = w3 * (fabsf(dx[0]) + fabsf(dx[1]) + fabsf(dx[2]))
@@ -233,11 +219,8 @@ pretrain_mouth_deform_forward_kernel(int N, const float* __restrict__ xyz, const
     }
   }
   if (reg_partials) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) reg += __shfl_xor(reg, o);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = reg;
-    __syncthreads();
-    if (threadIdx.x == 0) reg_partials[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    reg = block_sum_256(reg, s_red);
+    if (threadIdx.x == 0) reg_partials[blockIdx.x] = reg;
   }
 }
 
@@ -260,7 +243,7 @@ pretrain_mouth_deform_backward_kernel(int N, const float* __restrict__ scaling, 
     u[k] = h[(size_t)r * 7 + k]; p[k] = hp[(size_t)r * 7 + k];
     du[k] = 0.f; dp[k] = 0.f;
   }
-  const float sg = sigmoid_pf(hs[r]);
+  const float sg = sigmoid(hs[r]);
   const float xs[3] = {sx, sy, sz};
   const bool with_reg = g_reg != nullptr;
   const float go = with_reg ? g_reg[0] : 0.f;
@@ -268,26 +251,25 @@ pretrain_mouth_deform_backward_kernel(int N, const float* __restrict__ scaling, 
   float dgate = 0.f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const float gm = g_means ? g_means[3 * r + k] : 0.f;
+    const float gm = load_or_zero(g_means, 3 * r + k);
     d_xyz[3 * r + k] = gm;
     // the gradient of the COMBINED displacement: the render's, and |.| of the first regulariser, into both fields
     float G = gm;
     if (with_reg) {
       const float dxk = ((u[k] * xs[k]) * sg) * 2.0f + p[k] * 1e-2f;
-      G += w3 * sgn_f(dxk);
+      G += w3 * sgn(dxk);
     }
     du[k] = G * 2.0f * sg * xs[k];
     dgate += G * 2.0f * (u[k] * xs[k]);
     dp[k] = G * 1e-2f;
-    if (with_reg) dp[k] += w3 * sgn_f(p[k] * 1e-2f) * 1e-2f;
-    const float gs = g_scales ? g_scales[3 * r + k] : 0.f;
-    d_scaling[3 * r + k] = gs * sigmoid_pf(scaling[3 * r + k]);           // d softplus = sigmoid
+    if (with_reg) dp[k] += w3 * sgn(p[k] * 1e-2f) * 1e-2f;
+    d_scaling[3 * r + k] = load_or_zero(g_scales, 3 * r + k) * sigmoid(scaling[3 * r + k]);   // d softplus = sigmoid
   }
   if (with_reg) {
 #pragma unroll
     for (int k = 3; k < 7; ++k) {          // d_rot is regularised but never applied
-      du[k] = w4 * sgn_f(u[k]);
-      dp[k] = w4 * sgn_f(p[k]);
+      du[k] = w4 * sgn(u[k]);
+      dp[k] = w4 * sgn(p[k]);
     }
     if (hq) {
       // contrast: the reference zeroes the entries < 0 in place, so the gradient passes where c >= 0
@@ -299,22 +281,15 @@ pretrain_mouth_deform_backward_kernel(int N, const float* __restrict__ scaling, 
       }
     }
   }
-  float q[4], n2 = 0.f, dot = 0.f, gr[4];
+  float q[4], gr[4], n2 = 0.f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     q[k] = rotation[4 * r + k];
     n2 += q[k] * q[k];
-    gr[k] = g_rots ? g_rots[4 * r + k] : 0.f;
+    gr[k] = load_or_zero(g_rots, 4 * r + k);
   }
-  const float nrm = sqrtf(n2);
-  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) dot += gr[k] * q[k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    d_rotation[4 * r + k] = nrm > 1e-12f ? (gr[k] - q[k] * inv * dot * inv) * inv : gr[k] * inv;
-  const float so = sigmoid_pf(opacity[r]);
-  d_opacity[r] = (g_opac ? g_opac[r] : 0.f) * so * (1.f - so);
+  quat_normalize_backward(q, n2, gr, d_rotation + 4 * r);
+  d_opacity[r] = sigmoid_backward(load_or_zero(g_opac, r), opacity[r]);
   d_hs[r] = dgate * sg * (1.f - sg);
 #pragma unroll
   for (int k = 0; k < 7; ++k) {

@@ -9,15 +9,17 @@
 // One workgroup per image row; the statistics of all rows are re-reduced by every workgroup (H values) instead of by
 // one more launch.  Sums run in a fixed order: bitwise reproducible.
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
 
 constexpr int PB = 256;
 
+// Deliberately NOT device_math.hpp's block_sum_256: the waves' sums are added pairwise, (s0 + s1) + (s2 + s3), and a
+// leading barrier lets one s_red serve back-to-back calls.  The result bits depend on the association: keep it.
 __device__ __forceinline__ float block_sum(float v, float* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -124,8 +126,6 @@ prior_finalize_kernel(const float* __restrict__ parts, int H, int use_depth, flo
     out[0] = loss; out[1] = s[0]; out[2] = s[1]; out[3] = s[2]; out[4] = s[3];
   }
 }
-
-__device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
 // row sums of the gradient that reaches the normalised depth: A_r = sum g, B_r = sum g (d - mean_r); also writes the
 // gradient of the normal image (it has no cross-pixel coupling)

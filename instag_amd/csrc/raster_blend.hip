@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "device_math.hpp"
 #include "raster_internal.hpp"
 
 namespace instag {
@@ -225,8 +226,7 @@ blend_forward_kernel(Camera c, const int32_t* __restrict__ ranges, const uint32_
     // work list of the backward pass: the segments in front of the tile's last contributor
     __shared__ uint32_t s_last[BLOCK / 64], s_base;
     uint32_t m = inside ? last_contributor : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    m = wave_max(m);
     if ((tid & 63) == 0) s_last[tid >> 6] = m;
     __syncthreads();
     const uint32_t tile_last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
@@ -695,8 +695,7 @@ blend_forward_claim_kernel(Camera c, const int32_t* __restrict__ ranges, const u
   {
     __shared__ uint32_t s_last[BLOCK / 64], s_base;
     uint32_t m = inside ? sums.last : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+    m = wave_max(m);
     if ((tid & 63) == 0) s_last[tid >> 6] = m;
     __syncthreads();
     const uint32_t tile_last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
@@ -840,8 +839,7 @@ blend_backward_segment(const int tile, const int seg, const Camera& c, const int
   // only the first max(last_contributor) Gaussians of the list reached any pixel of this tile; a pixel whose
   // incoming gradient is exactly zero contributes nothing (a masked loss leaves most tiles of an image untouched)
   int m = live ? last_contributor : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if (lane == 0) s_max[wave] = m;
   __syncthreads();
   const int n = min(end - start, max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));

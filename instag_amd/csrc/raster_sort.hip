@@ -21,6 +21,7 @@
 // Ranking inside a block is the wave64 "match" scheme: log2(radix) ballots give every lane the set of lanes holding
 // the same digit; the lowest such lane bumps the wave's LDS counter once for all of them.  Keys are then reordered
 // through LDS so that every digit's run leaves as one contiguous store.  Stable and deterministic.
+#include "device_math.hpp"
 #include "raster_internal.hpp"
 
 namespace instag {
@@ -548,10 +549,7 @@ scan_counts_kernel(int N, const uint32_t* __restrict__ order, const uint32_t* __
         if ((st & SB_FLAGS) == 0ull) st = ld_agent64(lb + pb);
       }
       if (!settled && tid == 0) atomicAdd(&g_sort_stalls, 1u);                 // gave up: the offsets are wrong, say so
-      uint64_t v = (tid <= fc) ? (st & ~SB_FLAGS) : 0ull;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      excl += v;
+      excl += wave_sum<uint64_t>((tid <= fc) ? (st & ~SB_FLAGS) : 0ull);
       if (fc < 64) break;
       b -= 64;
     }

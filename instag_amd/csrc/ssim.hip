@@ -9,6 +9,7 @@
 // the three derivative maps dS/dmu1, dS/dE[x^2], dS/dE[xy]; backward filters them with the same
 // (symmetric) window and adds the L1 sign term, so the whole loss gradient is ONE kernel.
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
@@ -23,15 +24,6 @@ constexpr float C2 = 0.03f * 0.03f;
 __device__ constexpr float GW[11] = {0.0010283801f, 0.0075987581f, 0.0360007721f, 0.1093606895f, 0.2130055377f,
                                      0.2660117249f, 0.2130055377f, 0.1093606895f, 0.0360007721f, 0.0075987581f,
                                      0.0010283801f};
-
-__device__ __forceinline__ float block_sum_256(float v, float* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-  __syncthreads();
-  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
 
 __global__ void __launch_bounds__(256)
 l1_ssim_forward_kernel(const float* __restrict__ img1, const float* __restrict__ img2, int H, int W,
@@ -305,14 +297,12 @@ __device__ __forceinline__ void face_loss_partial_sums(const float* __restrict__
     float acc = 0.f;
 #pragma unroll 8
     for (int i = lane; i < n; i += 64) acc += p[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     if (lane == 0) s_sum[k] = acc;
     if (k == 7) {                       // the shortest array's wave also adds up the `extra` terms
       float e = 0.f;
       for (int i = lane; i < n_extra; i += 64) e += extra[i];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+      e = wave_sum(e);
       if (lane == 0) s_sum[8] = e;
     }
   }

@@ -23,6 +23,7 @@
 // all carry the same arguments: {step, beta1^step, beta2^step} of the pose optimizer, the same of the id / exp
 // optimizer, lr_pose, lr_idexp.
 #include "common.hpp"
+#include "device_math.hpp"
 
 namespace instag {
 namespace {
@@ -108,12 +109,6 @@ __device__ __forceinline__ Fwd transform(const Rot& r, double x, double y, doubl
 }
 __device__ __forceinline__ double project_x(const Fwd& w, double focal, double cx) { return -(focal * w.X) / w.Z + cx; }
 __device__ __forceinline__ double project_y(const Fwd& w, double focal, double cy) { return (focal * w.Y) / w.Z + cy; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // One wave evaluates one frame on the candidates geo[M][3] (LDS).  pose: theta, phi, psi, tx, ty, tz.  lm0 / lm1: the
 // lane's landmark l and (lanes 0..3) 64 + l.  scale = 1 / (136 F_group).  Returns on every lane the seven sums

@@ -201,6 +201,32 @@ def motion_glue_supported(enc_x, aud, eye_pre) -> bool:
             and enc_x.shape[1] + aud.shape[1] + eye_pre.shape[1] <= 256)
 
 
+# ---- what the four "deform + activate" operators below share ------------------------------------------------------------
+def _rows(N, dev, *widths):
+    return tuple(torch.empty(N, k, dtype=torch.float32, device=dev) for k in widths)
+
+
+def _activated(N, dev, n_partials=None):
+    """-> (means3D [N,3], scales [N,3], rots [N,4], opac [N,1]) and the regulariser's partial sums (None without)"""
+    reg = None if n_partials is None else torch.empty(n_partials, dtype=torch.float32, device=dev)
+    return _rows(N, dev, 3, 3, 4, 1), reg
+
+
+def _param_grads(N, dev, *head_widths):
+    """-> d_xyz, d_scaling, d_rotation, d_opacity, then one [N, w] gradient per head"""
+    return _rows(N, dev, 3, 3, 4, 1, *head_widths)
+
+
+def _upstream(*grads):
+    """the outputs' upstream gradients, contiguous; None (-> a NULL pointer) where nothing read that output"""
+    return [None if g is None else _c(g) for g in grads]
+
+
+def _reg_upstream(g_reg):
+    # every partial sum of the regulariser feeds the same scalar: its upstream gradient is one number
+    return None if g_reg is None else g_reg.reshape(-1)[:1].contiguous().float()
+
+
 class _DeformActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, scaling, rotation, opacity, h, p, reg_weight):
@@ -208,46 +234,30 @@ class _DeformActivate(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         xyz, scaling, rotation, opacity, h, p = (_c(t) for t in (xyz, scaling, rotation, opacity, h, p))
         N = xyz.shape[0]
-        dev = xyz.device
-        means3D = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        rots = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        reg = None
-        if reg_weight is not None:
-            reg = torch.empty(L.instag_deform_activate_num_reg_partials(N), dtype=torch.float32, device=dev)
+        outs, reg = _activated(N, xyz.device,
+                               None if reg_weight is None else L.instag_deform_activate_num_reg_partials(N))
         check(L.instag_deform_activate_forward(ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(p),
-                                               ptr(means3D), ptr(scales), ptr(rots), ptr(opac), ptr(reg),
+                                               *map(ptr, outs), ptr(reg),
                                                0.0 if reg_weight is None else float(reg_weight), N,
                                                _lib.current_stream()), "deform_activate_forward")
         ctx.save_for_backward(scaling, rotation, opacity, h, p)
         ctx.reg_weight = reg_weight
-        if reg is None:
-            return means3D, scales, rots, opac
-        return means3D, scales, rots, opac, reg
+        return outs if reg is None else outs + (reg,)
 
     @staticmethod
     def backward(ctx, g_means, g_scales, g_rots, g_opac, g_reg=None):
         L = _lib.lib()
         scaling, rotation, opacity, h, p = ctx.saved_tensors
         N = scaling.shape[0]
-        dev = scaling.device
-        gs = [None if g is None else _c(g) for g in (g_means, g_scales, g_rots, g_opac)]
-        # every partial sum of the regulariser feeds the same scalar: its upstream gradient is one number
-        g_reg1 = None if g_reg is None else g_reg.reshape(-1)[:1].contiguous().float()
-        d_xyz = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        d_op = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        d_h = torch.empty(N, 11, dtype=torch.float32, device=dev)
-        d_p = torch.empty(N, 6, dtype=torch.float32, device=dev)
-        check(L.instag_deform_activate_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(p), ptr(gs[0]),
-                                                ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(d_xyz), ptr(d_scaling),
-                                                ptr(d_rot), ptr(d_op), ptr(d_h), ptr(d_p), ptr(g_reg1),
+        gs = _upstream(g_means, g_scales, g_rots, g_opac)
+        g_reg1 = _reg_upstream(g_reg)
+        grads = _param_grads(N, scaling.device, 11, 6)
+        check(L.instag_deform_activate_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(p),
+                                                *map(ptr, gs), *map(ptr, grads), ptr(g_reg1),
                                                 0.0 if ctx.reg_weight is None else float(ctx.reg_weight), N,
                                                 _lib.current_stream()),
               "deform_activate_backward")
-        return d_xyz, d_scaling, d_rot, d_op, d_h, d_p, None
+        return grads + (None,)
 
 
 def deform_activate(xyz, scaling, rotation, opacity, h, p, reg_weight=None):
@@ -264,44 +274,30 @@ class _PretrainDeform(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         xyz, scaling, rotation, opacity, h_u, h_p = (_c(t) for t in (xyz, scaling, rotation, opacity, h_u, h_p))
         others = [_c(t) for t in others]
-        N, dev = xyz.shape[0], xyz.device
-        means3D = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        rots = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        reg = torch.empty(L.instag_pretrain_deform_num_partials(N), dtype=torch.float32, device=dev) if with_reg else None
+        N = xyz.shape[0]
+        outs, reg = _activated(N, xyz.device, L.instag_pretrain_deform_num_partials(N) if with_reg else None)
         heads = (C.c_void_p * max(1, len(others)))(*[t.data_ptr() for t in others])
         check(L.instag_pretrain_deform_forward(ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(h_u), ptr(h_p),
-                                               C.cast(heads, C.c_void_p), len(others), ptr(means3D), ptr(scales),
-                                               ptr(rots), ptr(opac), ptr(reg), N, _lib.current_stream()),
-              "pretrain_deform_forward")
+                                               C.cast(heads, C.c_void_p), len(others), *map(ptr, outs), ptr(reg), N,
+                                               _lib.current_stream()), "pretrain_deform_forward")
         ctx.save_for_backward(scaling, rotation, opacity, h_u, h_p, *others)
         ctx.n_inputs = 7 + len(others)
-        if reg is None:
-            return means3D, scales, rots, opac
-        return means3D, scales, rots, opac, reg
+        return outs if reg is None else outs + (reg,)
 
     @staticmethod
     def backward(ctx, g_means, g_scales, g_rots, g_opac, g_reg=None):
         L = _lib.lib()
         scaling, rotation, opacity, h_u, h_p, *others = ctx.saved_tensors
-        N, dev = scaling.shape[0], scaling.device
-        gs = [None if g is None else _c(g) for g in (g_means, g_scales, g_rots, g_opac)]
-        # every partial sum feeds the same scalar: its upstream gradient is one number
-        g_reg1 = None if g_reg is None else g_reg.reshape(-1)[:1].contiguous().float()
-        d_xyz = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        d_op = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        d_hu = torch.empty(N, 11, dtype=torch.float32, device=dev)
-        d_hp = torch.empty(N, 11, dtype=torch.float32, device=dev)
+        N = scaling.shape[0]
+        gs = _upstream(g_means, g_scales, g_rots, g_opac)
+        g_reg1 = _reg_upstream(g_reg)
+        grads = _param_grads(N, scaling.device, 11, 11)
         heads = (C.c_void_p * max(1, len(others)))(*[t.data_ptr() for t in others])
         check(L.instag_pretrain_deform_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h_u), ptr(h_p),
-                                                C.cast(heads, C.c_void_p), len(others), ptr(gs[0]), ptr(gs[1]),
-                                                ptr(gs[2]), ptr(gs[3]), ptr(g_reg1), ptr(d_xyz), ptr(d_scaling),
-                                                ptr(d_rot), ptr(d_op), ptr(d_hu), ptr(d_hp), N,
-                                                _lib.current_stream()), "pretrain_deform_backward")
-        return (d_xyz, d_scaling, d_rot, d_op, d_hu, d_hp, None) + (None,) * (ctx.n_inputs - 7)
+                                                C.cast(heads, C.c_void_p), len(others), *map(ptr, gs), ptr(g_reg1),
+                                                *map(ptr, grads), N, _lib.current_stream()),
+              "pretrain_deform_backward")
+        return grads + (None,) * (ctx.n_inputs - 6)
 
 
 def pretrain_deform(xyz, scaling, rotation, opacity, h_u, h_p, others=(), with_reg=True):
@@ -325,47 +321,31 @@ class _PretrainMouthDeform(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         xyz, scaling, rotation, opacity, h, hs, h_p = (_c(t) for t in (xyz, scaling, rotation, opacity, h, hs, h_p))
         h_q = None if h_q is None else _c(h_q)
-        N, dev = xyz.shape[0], xyz.device
-        means3D = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        rots = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        reg = torch.empty(L.instag_pretrain_mouth_deform_num_partials(N), dtype=torch.float32, device=dev) \
-            if with_reg else None
+        N = xyz.shape[0]
+        outs, reg = _activated(N, xyz.device, L.instag_pretrain_mouth_deform_num_partials(N) if with_reg else None)
         sx, sy, sz = xyz_scale
         check(L.instag_pretrain_mouth_deform_forward(ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(hs),
-                                                     ptr(h_p), ptr(h_q), sx, sy, sz, ptr(means3D), ptr(scales), ptr(rots),
-                                                     ptr(opac), ptr(reg), N, _lib.current_stream()),
-              "pretrain_mouth_deform_forward")
+                                                     ptr(h_p), ptr(h_q), sx, sy, sz, *map(ptr, outs), ptr(reg), N,
+                                                     _lib.current_stream()), "pretrain_mouth_deform_forward")
         ctx.save_for_backward(scaling, rotation, opacity, h, hs, h_p, *([h_q] if h_q is not None else []))
         ctx.xyz_scale = (sx, sy, sz)
-        if reg is None:
-            return means3D, scales, rots, opac
-        return means3D, scales, rots, opac, reg
+        return outs if reg is None else outs + (reg,)
 
     @staticmethod
     def backward(ctx, g_means, g_scales, g_rots, g_opac, g_reg=None):
         L = _lib.lib()
         scaling, rotation, opacity, h, hs, h_p, *rest = ctx.saved_tensors
         h_q = rest[0] if rest else None
-        N, dev = scaling.shape[0], scaling.device
-        gs = [None if g is None else _c(g) for g in (g_means, g_scales, g_rots, g_opac)]
-        # every partial sum feeds the same scalar: its upstream gradient is one number
-        g_reg1 = None if g_reg is None else g_reg.reshape(-1)[:1].contiguous().float()
-        d_xyz = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        d_op = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        d_h = torch.empty(N, 7, dtype=torch.float32, device=dev)
-        d_hs = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        d_hp = torch.empty(N, 7, dtype=torch.float32, device=dev)
+        N = scaling.shape[0]
+        gs = _upstream(g_means, g_scales, g_rots, g_opac)
+        g_reg1 = _reg_upstream(g_reg)
+        grads = _param_grads(N, scaling.device, 7, 1, 7)
         sx, sy, sz = ctx.xyz_scale
         check(L.instag_pretrain_mouth_deform_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(hs), ptr(h_p),
-                                                      ptr(h_q), sx, sy, sz, ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]),
-                                                      ptr(g_reg1), ptr(d_xyz), ptr(d_scaling), ptr(d_rot), ptr(d_op),
-                                                      ptr(d_h), ptr(d_hs), ptr(d_hp), N, _lib.current_stream()),
+                                                      ptr(h_q), sx, sy, sz, *map(ptr, gs), ptr(g_reg1),
+                                                      *map(ptr, grads), N, _lib.current_stream()),
               "pretrain_mouth_deform_backward")
-        return d_xyz, d_scaling, d_rot, d_op, d_h, d_hs, d_hp, None, None, None
+        return grads + (None, None, None)
 
 
 def pretrain_mouth_deform(xyz, scaling, rotation, opacity, h, hs, h_p, h_q=None, with_reg=True,
@@ -430,37 +410,27 @@ class _MouthActivate(torch.autograd.Function):
         L = _lib.lib()
         ctx.set_materialize_grads(False)
         xyz, scaling, rotation, opacity, h, hs = (_c(t) for t in (xyz, scaling, rotation, opacity, h, hs))
-        N, dev = xyz.shape[0], xyz.device
-        means3D = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        rots = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        opac = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        N = xyz.shape[0]
+        outs, _ = _activated(N, xyz.device)
         sx, sy, sz = xyz_scale
         check(L.instag_mouth_activate_forward(ptr(xyz), ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(hs), sx, sy,
-                                              sz, ptr(means3D), ptr(scales), ptr(rots), ptr(opac), N,
-                                              _lib.current_stream()), "mouth_activate_forward")
+                                              sz, *map(ptr, outs), N, _lib.current_stream()), "mouth_activate_forward")
         ctx.save_for_backward(scaling, rotation, opacity, h, hs)
         ctx.xyz_scale = (sx, sy, sz)
-        return means3D, scales, rots, opac
+        return outs
 
     @staticmethod
     def backward(ctx, g_means, g_scales, g_rots, g_opac):
         L = _lib.lib()
         scaling, rotation, opacity, h, hs = ctx.saved_tensors
-        N, dev = scaling.shape[0], scaling.device
-        gs = [None if g is None else _c(g) for g in (g_means, g_scales, g_rots, g_opac)]
-        d_xyz = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_scaling = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        d_rot = torch.empty(N, 4, dtype=torch.float32, device=dev)
-        d_op = torch.empty(N, 1, dtype=torch.float32, device=dev)
-        d_h = torch.empty(N, 7, dtype=torch.float32, device=dev)
-        d_hs = torch.empty(N, 1, dtype=torch.float32, device=dev)
+        N = scaling.shape[0]
+        gs = _upstream(g_means, g_scales, g_rots, g_opac)
+        grads = _param_grads(N, scaling.device, 7, 1)
         sx, sy, sz = ctx.xyz_scale
         check(L.instag_mouth_activate_backward(ptr(scaling), ptr(rotation), ptr(opacity), ptr(h), ptr(hs), sx, sy, sz,
-                                               ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(d_xyz), ptr(d_scaling),
-                                               ptr(d_rot), ptr(d_op), ptr(d_h), ptr(d_hs), N, _lib.current_stream()),
+                                               *map(ptr, gs), *map(ptr, grads), N, _lib.current_stream()),
               "mouth_activate_backward")
-        return d_xyz, d_scaling, d_rot, d_op, d_h, d_hs, None
+        return grads + (None,)
 
 
 def mouth_activate(xyz, scaling, rotation, opacity, h, hs, xyz_scale=(1e-2 / 5, 1e-2, 1e-2 / 5)):
