@@ -1,22 +1,26 @@
-"""Render composition on the MI355X operators: ``render`` and ``render_motion``.
+"""Render composition on the MI355X operators: ``render``, ``render_motion``, ``render_motion_mouth_con``, ``render_fuse``.
 
-Counterpart of /root/reference/gaussian_renderer/__init__.py: render :37-133, render_motion :151-298
-(same argument meaning and returned dictionary keys).  ``viewpoint_camera`` needs the attributes the
-reference reads: FoVx, FoVy, image_height, image_width, world_view_transform, full_proj_transform,
+Counterpart of the reference's gaussian_renderer/__init__.py: render :37-133, render_motion :151-298,
+render_motion_mouth_con :302-435 (same argument meaning and returned dictionary keys).  ``viewpoint_camera`` needs the
+attributes the reference reads: FoVx, FoVy, image_height, image_width, world_view_transform, full_proj_transform,
 camera_center, and ``talking_dict`` with ``auds`` [8,29,16] and ``au_exp`` [6] for render_motion.
+
+Both motion renders are one sequence of stages: evaluate the fields (_evaluate_fields) ->
+choose and run one deformation path (-> _Deformed) -> publish the reference's in-place updates (_publish, called by
+the path) -> rasterize, with the attention passes (_render_passes) -> package.
 """
 from __future__ import annotations
 
 import math
+import os as _os
+from typing import NamedTuple
 
 import torch
 
 from . import _keepalive
 from .diff_gauss import GaussianRasterizationSettings, GaussianRasterizer
-from .motion_net import MotionNetwork as _MotionNetwork
+from .motion_net import LazyOutputs, MotionNetwork as _MotionNetwork
 
-CONCURRENT_PASSES = True      # fork the attention raster pass(es) onto a second stream
-SHARED_ATTN_PASS = True       # attention map as an auxiliary colour set of the main raster pass
 # Fuse stage (training): the mouth pass on a second stream beside the face pass (1.45 -> 1.26 ms per captured step in
 # round 2).  Round 2 shipped it switched off behind a segmentation fault inside hipGraphLaunch of a LATER, unrelated
 # face-step graph that only a soak of the stage tests showed.  Round 3 removed the two ownership defects the bisect
@@ -26,18 +30,13 @@ SHARED_ATTN_PASS = True       # attention map as an auxiliary colour set of the 
 # captured steps kept their loss -- hence their autograd graph and every parameter's gradient accumulator -- alive, bound
 # to a per-capture stream that later backward passes then hopped to inside an open capture (one capture stream, detached
 # outputs).  The GPU suite passes with the switch on; INSTAG_CONCURRENT_FUSE=0 switches it off.
-import os as _os
 CONCURRENT_FUSE_PASSES = _os.environ.get("INSTAG_CONCURRENT_FUSE", "1") == "1"
 
 
-def _side_stream(device):
-    """Second HIP stream per device: independent work (the attention raster pass) is forked onto it so that it
-    overlaps the main pass -- both blend kernels are bound by their longest tile and leave most CUs idle.
-    ``device`` may be a (device, tag) pair: a separate stream per purpose (all from _lib.side_stream's registry)."""
+def _side_stream(device, tag="attn"):
+    """Second HIP stream per device and purpose (from _lib.side_stream's registry) for work forked beside the main pass
+    (an attention raster pass, the fuse stage's mouth pass): a pass alone leaves most CUs idle, bound by its longest tile."""
     from . import _lib
-    tag = "attn"
-    if isinstance(device, tuple):
-        device, tag = device
     return _lib.side_stream(device, ("renderer", tag))
 
 
@@ -49,52 +48,120 @@ def _settings(cam, pc, bg_color, scaling_modifier, debug=False):
         sh_degree=pc.active_sh_degree, campos=cam.camera_center, prefiltered=False, debug=debug)
 
 
-_ZEROS = {}
+# ---- constants -------------------------------------------------------------------------------------------------------
+_CONSTANTS = {}          # kind -> {(device, shape, dtype): tensor}
+_CARRIER_COUNTS = 8      # gradient-carrier buffers kept (Gaussian counts of past density-control events are dropped)
+
+
+def _constant(kind, like, make, keep=None):
+    """Read-only ``make(like)`` (torch.zeros_like / torch.ones_like), created once per kind, device, shape and dtype.
+    While the current stream is capturing, a constant that is not there yet is returned fresh and NOT kept: it could
+    only come from the capture's pool and would be replayed as a fill.  ``keep``: the most entries of THIS kind; one more
+    drops them (the other kinds' are not touched)."""
+    kept = _CONSTANTS.setdefault(kind, {})
+    key = (like.device, tuple(like.shape), like.dtype)
+    t = kept.get(key)
+    if t is None:
+        t = make(like)
+        if not (like.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if keep is not None and len(kept) >= keep:
+                kept.clear()
+            kept[key] = t
+    return t
 
 
 def prepare_screenspace(pc):
-    """Allocate the zeros behind _screenspace_points for this Gaussian count now (a trainer calls it in front of a stream
-    capture: inside one, a first use could only allocate from the capture's pool and would be replayed as a fill)."""
-    xyz = pc.get_xyz
-    key = (xyz.device, xyz.shape[0], xyz.dtype)
-    z = _ZEROS.get(key)
-    if z is None:
-        if len(_ZEROS) >= 8:
-            _ZEROS.clear()               # (Gaussian counts of past density-control events)
-        z = _ZEROS[key] = torch.zeros(xyz.shape, dtype=xyz.dtype, device=xyz.device)
-    return z
+    """Allocate the zeros behind the screen-space gradient carrier for this Gaussian count now (a trainer calls it in
+    front of a stream capture, where a first use would fall under _constant's capture rule)."""
+    return _constant("carrier", pc.get_xyz, torch.zeros_like, keep=_CARRIER_COUNTS)
 
 
-def _screenspace_points(pc):
+def _gradient_carrier(pc):
     # gradient carrier of the screen-space means (gaussian_renderer/__init__.py:47-52 builds it as zeros + 0 with
     # retain_grad(); a leaf receives the same .grad and saves a launch).  Nothing reads or writes its VALUE -- the
-    # rasterizer takes it for the gradient's sake only -- so on the GPU every step's leaf is a fresh view of one zeroed
-    # buffer per Gaussian count instead of a fill launch at the head of the step (4 us + a launch gap on the chain)
-    xyz = pc.get_xyz
-    if not xyz.is_cuda:
-        return torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True)
-    key = (xyz.device, xyz.shape[0], xyz.dtype)
-    z = _ZEROS.get(key)
-    if z is None:
-        if torch.cuda.is_current_stream_capturing():
-            return torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True)
-        z = prepare_screenspace(pc)
-    return z.detach().requires_grad_(True)
+    # rasterizer takes it for the gradient's sake only -- so every step's leaf is a fresh view of one zeroed buffer per
+    # Gaussian count instead of a fill launch at the head of the step (4 us + a launch gap on the chain)
+    return prepare_screenspace(pc).detach().requires_grad_(True)
+
+
+def _neutral_expression(cam, dev):
+    """Read-only zeros of the frame's ``au_exp``: the neutral expression the mouth branch feeds the face field."""
+    return _constant("neutral", cam.talking_dict["au_exp"].to(dev, non_blocking=True), torch.zeros_like)
+
+
+def _begin(cam, pc, pipe, bg_color, scaling_modifier):          # -> (gradient carrier, rasterizer) of one render
+    debug = getattr(pipe, "debug", False)
+    return _gradient_carrier(pc), GaussianRasterizer(_settings(cam, pc, bg_color, scaling_modifier, debug))
 
 
 def render(viewpoint_camera, pc, pipe=None, bg_color=None, scaling_modifier=1.0, override_color=None):
     """Static render (no motion fields)."""
-    screenspace_points = _screenspace_points(pc)
-    rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
-                                              getattr(pipe, "debug", False)))
+    screenspace_points, rasterizer = _begin(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     opacity = pc.get_opacity
     shs, colors = (pc.get_features, None) if override_color is None else (None, override_color)
     image, depth, normal, alpha, radii, extra = rasterizer(
         means3D=pc.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors, opacities=opacity,
-        scales=pc.get_scaling, rotations=pc.get_rotation, cov3Ds_precomp=None,
-        extra_attrs=torch.ones_like(opacity))
+        scales=pc.get_scaling, rotations=pc.get_rotation, cov3Ds_precomp=None, extra_attrs=torch.ones_like(opacity))
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
             "depth": depth, "alpha": alpha, "normal": normal, "radii": radii}
+
+
+# ---- stage 1: the fields ---------------------------------------------------------------------------------------------
+class _Fields(NamedTuple):
+    motion: dict             # the universal field's predictions
+    p_motion: object         # the personalised field's, None when neither personalized nor align
+    xyz_route: object        # the positions as the last encode handed them on (gridencoder.passthrough)
+    p_route: object          # likewise the fused shift's operand, None without one
+
+
+def _evaluate_fields(cam, pc, motion_net, personalized, align, condition, *, announce, fused_shift, p_exp=None,
+                     flush_on_shift_grad=False):
+    """Frame inputs, the personalised and the universal field -> _Fields.  What the two renders do differently is a
+    parameter: ``condition`` = the universal field's third argument, or a callable(audio_feat) that makes it right before
+    that call; ``announce(audio_feat)`` = the render's start_audio calls (device only); ``fused_shift(p_preds)`` = the raw
+    alignment head if the universal field can add it to the positions inside its tri-plane kernel, else None (device
+    only); ``p_exp`` = the expression the personalised field takes as well, None for none; ``flush_on_shift_grad``."""
+    from . import gridencoder as _ge
+    xyz = xyz_route = pc.get_xyz
+    dev = xyz.device
+    audio_feat = cam.talking_dict["auds"].to(dev, non_blocking=True)
+    if xyz.is_cuda:
+        announce(audio_feat)
+    # The Gaussians' positions feed three operators (personalised field, universal field, deformation): on the device
+    # each encode hands the position on as one of its outputs, so the three gradients are summed inside the encoders'
+    # backward kernels instead of by autograd add launches on the tail of the step (gridencoder.passthrough)
+    carrier, p_preds, x_shift = {}, None, None
+    if personalized or align:
+        with _ge.passthrough(carrier):
+            p_preds = pc.neural_motion_grid(pc.get_xyz, audio_feat, *(() if p_exp is None else (p_exp,)))
+        xyz = xyz_route = carrier.pop("xyz", xyz_route)
+    if align:
+        p_raw = fused_shift(p_preds) if xyz.is_cuda else None
+        if p_raw is not None:
+            x_shift = (p_raw, 1e-2)           # xyz + p_xyz (= p[:, :3] * 1e-2) is formed inside the tri-plane kernel
+            if flush_on_shift_grad and p_raw.requires_grad:
+                # backward reaches p when the universal field is done and the personalised field's chain is about to
+                # start: the weight gradients queued so far can run beside it (instag_amd/deferred.py)
+                from . import deferred
+                p_raw.register_hook(lambda g, dev=dev: deferred.flush_async(dev))
+        else:
+            xyz = xyz + p_preds["p_xyz"]
+    cond = condition(audio_feat) if callable(condition) else condition
+    with _ge.passthrough(carrier):
+        preds = motion_net(xyz, audio_feat, cond, **({} if x_shift is None else {"x_shift": x_shift}))
+    if x_shift is not None or not align:
+        xyz_route = carrier.pop("xyz", xyz_route)     # (align without the fused shift encodes xyz + p_xyz, not xyz)
+    return _Fields(preds, p_preds, xyz_route, carrier.pop("shift", None))
+
+
+# ---- stages 2 and 3: one deformation path, which publishes what the reference updates in place -------------------------
+class _Deformed(NamedTuple):
+    means3D: object
+    scales: object
+    rotations: object
+    opacity: object
+    motion_reg: object = None     # partial sums of the step's regularisers, when the path's operator computes them
+    cut: object = None            # outputs of the _BackwardCut node (fused face path with backward_cut=True)
 
 
 class _BackwardCut(torch.autograd.Function):
@@ -115,41 +182,208 @@ class _BackwardCut(torch.autograd.Function):
         return grads
 
 
-MARK_BACKWARD_CUT = False     # set by FaceTrainer._forward_backward_cut around its render_motion call
+def _publish(motion_preds, motion_net, raw, **formulas):
+    """The reference updates its result in place (d_xyz += ..., d_xyz *= p_scale, gaussian_renderer/__init__.py:207-217,
+    :387): the dictionary it returns under "motion" -- and motion_net.cache, the same object, which the mouth branch reads
+    at inference (:362-363) -- holds the combined, scaled values, and so do the regularisers of train_face.py:508-514.
+    The operators never materialise them: entry ``key`` becomes ``formulas[key](*raw)``, built on first access, in
+    ``motion_preds`` from the attached tensors and, if the network keeps one, in its cache from the detached ones."""
+    cache = getattr(motion_net, "cache", None)
+    detached = tuple(t.detach() for t in raw)
+    for key, formula in formulas.items():
+        motion_preds[key] = lambda formula=formula: formula(*raw)
+        if cache is not None:
+            cache[key] = lambda formula=formula: formula(*detached)
 
 
-_ONES = {}
+def _aligned_d_xyz(h, p):
+    """d_xyz * p_scale (:217) from an 11-column head output and the raw alignment head."""
+    return (h[..., :3] * 1e-2) * (torch.tanh(p[..., 3:] / 5) * 0.25 + 1)
 
 
-_ZEROS = {}
+# The clauses of the paths' predicates.  (Before they were shared, some sites asked ``is not None`` and some
+# ``torch.is_tensor``, some through LazyOutputs.get and some through dict.get: for what the networks return -- an eager
+# tensor or no entry -- these agree.  Only the personalised field's head is lazy, and _present does not run it.)
+def _raw(preds, key, cols=None):
+    """preds[key] if it is a tensor (of ``cols`` columns), else None."""
+    t = preds.get(key) if preds is not None else None
+    return t if torch.is_tensor(t) and (cols is None or t.shape[-1] == cols) else None
 
 
-def _zeros_const(like):
-    """Read-only zero tensor of ``like``'s shape (the neutral expression the mouth branch feeds the face field), created
-    once per (device, shape, dtype) outside any graph capture."""
-    key = (like.device, tuple(like.shape), like.dtype)
-    t = _ZEROS.get(key)
-    if t is None:
-        if like.is_cuda and torch.cuda.is_current_stream_capturing():
-            return torch.zeros_like(like)
-        t = _ZEROS[key] = torch.zeros_like(like)
-    return t
+def _present(preds, key):
+    """Whether preds has the entry, without evaluating a lazy one."""
+    return preds is not None and dict.get(preds, key) is not None
 
 
-def _ones(like):
-    """Constant extra_attrs column, created once per (device, N) outside any graph capture."""
-    key = (like.device, tuple(like.shape))
-    t = _ONES.get(key)
-    if t is None:
-        if like.is_cuda and torch.cuda.is_current_stream_capturing():
-            return torch.ones_like(like)
-        t = _ONES[key] = torch.ones_like(like)
-    return t
+def _face_operator_ok(pc, f, detach_motion):
+    """On the device, with gradients into the fields, and an 11-column universal head: what every face operator needs."""
+    return pc.get_xyz.is_cuda and not detach_motion and _raw(f.motion, "_h", 11) is not None
+
+
+def _pretrain_face_applies(pc, f, personalized, align, detach_motion):
+    return personalized and not align and _face_operator_ok(pc, f, detach_motion) and _present(f.p_motion, "_h")
+
+
+def _deform_pretrain_face(pc, motion_net, f, others, with_reg):
+    """The pretraining operator (glue.pretrain_deform): both heads and the other identities' in one kernel per pass."""
+    from .glue import pretrain_deform
+    h_u, h_p = f.motion["_h"], f.p_motion["_h"]
+    outs = pretrain_deform(f.xyz_route, pc._scaling, pc._rotation, pc._opacity, h_u, h_p, others, with_reg=with_reg)
+    _publish(f.motion, motion_net, (h_u, h_p), d_xyz=lambda u, p: u[..., :3] * 1e-2 + p[..., :3] * 1e-2,
+             d_scale=lambda u, p: u[..., 8:11] + p[..., 8:11], d_rot=lambda u, p: u[..., 3:7] + p[..., 3:7])
+    return _Deformed(*outs[:4], motion_reg=outs[4] if with_reg else None)
+
+
+def _fused_pers_applies(pc, f, personalized, align, detach_motion, motion_reg_weight):
+    return (align and personalized and motion_reg_weight is None and _face_operator_ok(pc, f, detach_motion)
+            and _present(f.p_motion, "_p") and _present(f.p_motion, "_h"))
+
+
+def _deform_fused_pers(pc, motion_net, f):
+    """personalized + align (synthesize_fuse.py:55 with --personalized): the two fields' head outputs add before
+    everything the deform operator does ((d_xyz + p.d_xyz) * p_scale, scaling + d_scale + p.d_scale, ...), so the same
+    operator serves with h + h_p -- one add launch instead of ~20 elementwise ones each way."""
+    from .glue import deform_activate
+    h_sum = f.motion["_h"] + f.p_motion["_h"]
+    p = f.p_route if f.p_route is not None else f.p_motion["_p"]
+    outs = deform_activate(f.xyz_route, pc._scaling, pc._rotation, pc._opacity, h_sum, p)
+    _publish(f.motion, motion_net, (h_sum, p), d_xyz=_aligned_d_xyz, d_scale=lambda h, p: h[..., 8:11],
+             d_rot=lambda h, p: h[..., 3:7])
+    return _Deformed(*outs[:4])
+
+
+def _fused_applies(pc, f, personalized, align, detach_motion):
+    return align and not personalized and _face_operator_ok(pc, f, detach_motion) and _present(f.p_motion, "_p")
+
+
+def _deform_fused(pc, motion_net, f, motion_reg_weight, backward_cut, with_attn):
+    """align: deltas + softplus / normalize / sigmoid in one HIP kernel per pass (glue.deform_activate), which also
+    computes the regulariser (on the scaled displacement) when given its weight."""
+    from .glue import deform_activate
+    xyz, h, cut = f.xyz_route, f.motion["_h"], None
+    p = f.p_route if f.p_route is not None else f.p_motion["_p"]
+    if backward_cut:
+        # every tensor through which a gradient crosses from the rasterizer side (deform operator, attention
+        # colours) to the motion fields goes through one identity node: the three-segment step's cut
+        amb = f.motion["_amb3"] if with_attn else None
+        cut = list(_BackwardCut.apply(*[t for t in (xyz, h, p, amb) if t is not None]))
+        xyz, h, p = cut[:3]
+    outs = deform_activate(xyz, pc._scaling, pc._rotation, pc._opacity, h, p, motion_reg_weight)
+    _publish(f.motion, motion_net, (f.motion["_h"], f.p_motion["_p"]), d_xyz=_aligned_d_xyz)
+    return _Deformed(*outs[:4], motion_reg=outs[4] if motion_reg_weight is not None else None, cut=cut)
+
+
+def _deform_composed_face(pc, motion_net, f, personalized, align, detach_motion):
+    """The reference's lines with torch operators: every combination the operators above do not take."""
+    m, pm = f.motion, f.p_motion
+    d_xyz, d_scale, d_rot = m["d_xyz"], m["d_scale"], m["d_rot"]
+    own = {}
+    if personalized:
+        d_xyz, d_scale, d_rot = d_xyz + pm["d_xyz"], d_scale + pm["d_scale"], d_rot + pm["d_rot"]
+        own.update(d_scale=lambda x, s, r: s, d_rot=lambda x, s, r: r)
+    if align:
+        d_xyz = d_xyz * pm["p_scale"]
+    if personalized or align:
+        _publish(m, motion_net, (d_xyz, d_scale, d_rot), d_xyz=lambda x, s, r: x, **own)
+    if detach_motion:
+        d_xyz, d_scale, d_rot = d_xyz.detach(), d_scale.detach(), d_rot.detach()
+    return _Deformed(f.xyz_route + d_xyz, pc.scaling_activation(pc._scaling + d_scale),
+                     pc.rotation_activation(pc._rotation + d_rot), pc.get_opacity)
+
+
+def _mouth_scale(motion_net):
+    return getattr(motion_net, "XYZ_SCALE", (1e-2 / 5, 1e-2, 1e-2 / 5))
+
+
+def _deform_pretrain_mouth(pc, motion_net, f, other, with_reg):
+    """The mouth pretraining operator (glue.pretrain_mouth_deform); render_motion_mouth_con's guard is its predicate."""
+    h, hs, h_p = _raw(f.motion, "_h", 7), _raw(f.motion, "_hs"), _raw(f.p_motion, "_h", 7)
+    if h is None or hs is None or h_p is None:
+        raise RuntimeError("pretrain_other / pretrain_reg: both fields' raw 7-column heads are needed")
+    from .glue import pretrain_mouth_deform
+    scale = _mouth_scale(motion_net)
+    outs = pretrain_mouth_deform(f.xyz_route, pc._scaling, pc._rotation, pc._opacity, h, hs, h_p, other,
+                                 with_reg=with_reg, xyz_scale=scale)
+    _publish(f.motion, motion_net, (h, hs, h_p),
+             d_xyz=lambda h, hs, h_p: (h[..., :3] * h.new_tensor(scale)) * torch.sigmoid(hs) * 2 + h_p[..., :3] * 1e-2)
+    return _Deformed(*outs[:4], motion_reg=outs[4] if with_reg else None)
+
+
+def _mouth_activate_applies(f, personalized):
+    h = _raw(f.motion, "_h", 7)
+    return not personalized and h is not None and h.is_cuda and _raw(f.motion, "_hs") is not None
+
+
+def _deform_mouth_activate(pc, motion_net, f):
+    """Gated displacement + softplus / normalize / sigmoid in one HIP kernel per pass (glue.mouth_activate)."""
+    from .glue import mouth_activate
+    return _Deformed(*mouth_activate(f.xyz_route, pc._scaling, pc._rotation, pc._opacity, f.motion["_h"],
+                                     f.motion["_hs"], _mouth_scale(motion_net)))
+
+
+def _deform_composed_mouth(pc, f, personalized):
+    # (unlike :387, and the pretraining path above, this path has never written the sum back to the dictionary)
+    d_xyz = f.motion["d_xyz"]
+    if personalized:
+        d_xyz = d_xyz + f.p_motion["d_xyz"]
+    return _Deformed(f.xyz_route + d_xyz, pc.get_scaling, pc.rotation_activation(pc._rotation), pc.get_opacity)
+
+
+# ---- stage 4: the raster passes --------------------------------------------------------------------------------------
+def _attention_colors(preds):
+    if preds.get("_amb3") is not None:
+        return preds["_amb3"]
+    eye = preds["ambient_eye"]
+    return torch.cat([preds["ambient_aud"], eye, torch.zeros_like(eye)], dim=-1)
+
+
+def _render_passes(rasterizer, pc, screenspace_points, d, f, return_attn=False, personalized=False, need_geometry=True):
+    """The main pass and the attention maps -> (the main pass's outputs, attn, p_attn, forked).  The universal field's
+    map is rendered over the same (detached) geometry as the image, so it rides along the main pass as an auxiliary
+    colour set (one preprocess / binning / sort instead of two); the personalised field's is a pass of its own."""
+    from . import _lib
+    dev = d.means3D.device
+    ones = _constant("ones", d.opacity, torch.ones_like)       # the extra_attrs column
+
+    def p_attn_pass(carrier):
+        return rasterizer(means3D=d.means3D.detach(), means2D=carrier, shs=None,
+                          colors_precomp=_attention_colors(f.p_motion), opacities=d.opacity.detach(),
+                          scales=d.scales.detach(), rotations=d.rotations.detach(), cov3Ds_precomp=None,
+                          extra_attrs=ones)[0]
+
+    p_attn = None
+    fork = return_attn and personalized and d.means3D.is_cuda and _lib.may_fork(dev)
+    if fork:
+        # the personalised pass only shares inputs with the main pass: it runs on a second stream
+        main_stream, side = torch.cuda.current_stream(dev), _side_stream(dev)
+        # The screen-space gradient carrier is a leaf that the side-stream pass AND the main pass write a gradient to.
+        # A leaf's gradient accumulator runs on ONE stream (the one current at the leaf's first use): fed directly from
+        # two streams, one of the producers always mismatches ("AccumulateGrad node's stream does not match").  The side
+        # pass therefore gets a view made HERE, on the main stream: its gradient reaches the leaf through the view's
+        # backward node, which runs where the view was made.
+        side_carrier = screenspace_points.view_as(screenspace_points)
+        side.wait_stream(main_stream)
+        with torch.cuda.stream(side):
+            p_attn = p_attn_pass(side_carrier)
+    # (dc and rest coefficients as the pair the model stores: no concatenation, no slice copies in backward)
+    shs = pc.get_features_pair if (d.means3D.is_cuda and hasattr(pc, "get_features_pair")) else pc.get_features
+    extra = {} if need_geometry else {"geometry": False}
+    if return_attn:
+        # (with the cut, the attention colours are its fourth output -- absent if the field has no ``_amb3``)
+        extra["aux_colors"] = _attention_colors(f.motion) if d.cut is None else (d.cut[3] if len(d.cut) > 3 else None)
+    outs = rasterizer(means3D=d.means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=d.opacity,
+                      scales=d.scales, rotations=d.rotations, cov3Ds_precomp=None, extra_attrs=ones, **extra)
+    if fork:
+        main_stream.wait_stream(side)
+        _keepalive.cross_stream(p_attn, main_stream)
+    elif return_attn and personalized:
+        p_attn = p_attn_pass(screenspace_points)
+    return outs, (outs[6] if return_attn else None), p_attn, fork
 
 
 def render_motion(viewpoint_camera, pc, motion_net, pipe=None, bg_color=None, scaling_modifier=1.0, frame_idx=None,
                   return_attn=False, personalized=False, align=False, detach_motion=False, motion_reg_weight=None,
-                  pretrain_heads=None, pretrain_reg=True, need_geometry=True):
+                  pretrain_heads=None, pretrain_reg=True, need_geometry=True, backward_cut=False):
     """Render with the universal (motion_net) and personalised (pc.neural_motion_grid) motion fields.
     ``motion_reg_weight`` (extension): also return ``motion_reg`` = partial sums of weight * the motion regulariser of
     train_face.py:510-514, computed inside the fused deform operator (None when that operator is not used).
@@ -158,222 +392,46 @@ def render_motion(viewpoint_camera, pc, motion_net, pipe=None, bg_color=None, sc
     (glue.pretrain_deform) and ``motion_reg`` holds partial sums of that step's regularisers and contrast term
     (``pretrain_reg=False``: not computed, ``motion_reg`` is None).
     ``need_geometry=False`` (extension): the caller reads neither ``depth`` nor ``normal`` -- both are None and the
-    rasterizer runs its colour-only forward blend; everything else is bit-identical."""
-    screenspace_points = _screenspace_points(pc)
-    rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
-                                              getattr(pipe, "debug", False)))
-    dev = pc.get_xyz.device
-    audio_feat = viewpoint_camera.talking_dict["auds"].to(dev, non_blocking=True)
-    exp_feat = viewpoint_camera.talking_dict["au_exp"].to(dev, non_blocking=True)
+    rasterizer runs its colour-only forward blend; everything else is bit-identical.
+    ``backward_cut=True`` (extension, FaceTrainer's three-segment step): the fused align path routes what it reads of
+    the fields through one _BackwardCut node, whose outputs are returned under ``_cut`` (None on every other path)."""
+    screenspace_points, rasterizer = _begin(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    exp_feat = viewpoint_camera.talking_dict["au_exp"].to(pc.get_xyz.device, non_blocking=True)
 
-    xyz = pc.get_xyz
-    p_motion_preds = None
-    cut_tensors = amb_cut = None
-    if xyz.is_cuda and hasattr(motion_net, "start_audio"):
+    def announce(audio_feat):
         # both networks' audio branches depend only on the frame: start them now, each on its own side stream
-        motion_net.start_audio(audio_feat, 1, exp_feat)
-        if personalized and hasattr(pc.neural_motion_grid, "start_audio"):
-            # (with align only, the personalised field's deformation head is never read: motion_net.py)
-            pc.neural_motion_grid.start_audio(audio_feat, 2, exp_feat)
-    # The Gaussians' positions feed three operators (personalised field, universal field, deformation): on the device
-    # each encode hands the position on as one of its outputs, so the three gradients are summed inside the encoders'
-    # backward kernels instead of by autograd add launches on the tail of the step (gridencoder.passthrough)
-    from . import gridencoder as _ge
-    carrier = {}
-    xyz_route = pc.get_xyz
-    if personalized or align:
-        with _ge.passthrough(carrier):
-            p_motion_preds = pc.neural_motion_grid(pc.get_xyz, audio_feat, exp_feat)
-        xyz_route = carrier.pop("xyz", xyz_route)
-        xyz = xyz_route
-    x_shift = None
-    p_route = None
-    if align:
-        p_raw = p_motion_preds.get("_p")
-        if p_raw is not None and xyz.is_cuda and isinstance(motion_net, _MotionNetwork):
-            # xyz + p_xyz (= p[:, :3] * 1e-2) is formed inside the tri-plane kernel
-            x_shift = (p_raw, 1e-2)
-            if p_raw.requires_grad:
-                # backward reaches p when the universal field is done and the personalised field's chain is about to
-                # start: the weight gradients queued so far can run beside it (instag_amd/deferred.py)
-                from . import deferred
-                p_raw.register_hook(lambda g, dev=dev: deferred.flush_async(dev))
-        else:
-            xyz = xyz + p_motion_preds["p_xyz"]
-    with _ge.passthrough(carrier):
-        if x_shift is not None:
-            motion_preds = motion_net(xyz, audio_feat, exp_feat, x_shift=x_shift)
-        else:
-            motion_preds = motion_net(xyz, audio_feat, exp_feat)
-    if x_shift is not None or not align:
-        xyz_route = carrier.pop("xyz", xyz_route)     # (align without the fused shift encodes xyz + p_xyz, not xyz)
-    p_route = carrier.pop("shift", None)
-    motion_reg = None
+        if hasattr(motion_net, "start_audio"):
+            motion_net.start_audio(audio_feat, 1, exp_feat)
+            if personalized and hasattr(pc.neural_motion_grid, "start_audio"):
+                # (with align only, the personalised field's deformation head is never read: motion_net.py)
+                pc.neural_motion_grid.start_audio(audio_feat, 2, exp_feat)
 
-    fused = (align and not personalized and not detach_motion and pc.get_xyz.is_cuda
-             and motion_preds.get("_h") is not None and dict.get(p_motion_preds, "_p") is not None
-             and motion_preds["_h"].shape[-1] == 11)
-    # personalized + align (synthesize_fuse.py:55 with --personalized): the two fields' head outputs add
-    # before everything the deform operator does ((d_xyz + p.d_xyz) * p_scale, scaling + d_scale + p.d_scale, ...), so the
-    # same operator serves with h + h_p -- one add launch instead of ~20 elementwise ones each way
-    fused_pers = (align and personalized and not detach_motion and pc.get_xyz.is_cuda and motion_reg_weight is None
-                  and motion_preds.get("_h") is not None and dict.get(p_motion_preds, "_p") is not None
-                  and dict.get(p_motion_preds, "_h") is not None and motion_preds["_h"].shape[-1] == 11)
+    # (the fused shift asks for the universal field's class and a non-None ``_p`` here, for an XYZ_SCALE attribute and a
+    # tensor ``_p`` in the mouth render, and only this render flushes the deferred weight gradients from the shift's
+    # gradient hook.  The first two look accidental; all three are kept as found -- unifying them is a behaviour change)
+    f = _evaluate_fields(viewpoint_camera, pc, motion_net, personalized, align, exp_feat, announce=announce,
+                         fused_shift=lambda p: p.get("_p") if isinstance(motion_net, _MotionNetwork) else None,
+                         p_exp=exp_feat, flush_on_shift_grad=True)
     if pretrain_heads is not None:
-        if not (personalized and not align and not detach_motion and pc.get_xyz.is_cuda
-                and torch.is_tensor(motion_preds.get("_h")) and motion_preds["_h"].shape[-1] == 11
-                and dict.get(p_motion_preds, "_h") is not None):
+        if not _pretrain_face_applies(pc, f, personalized, align, detach_motion):
             raise RuntimeError("pretrain_heads: the pretraining deform operator needs personalized=True, align=False, "
                                "both fields' fused heads and the GPU")
-        from .glue import pretrain_deform
-        h_u, h_p = motion_preds["_h"], p_motion_preds["_h"]
-        outs_d = pretrain_deform(xyz_route, pc._scaling, pc._rotation, pc._opacity, h_u, h_p, pretrain_heads,
-                                 with_reg=pretrain_reg)
-        means3D, scales, rotations, opacity = outs_d[:4]
-        motion_reg = outs_d[4] if pretrain_reg else None
-        # (the reference's in-place additions to the returned dictionary / motion_net.cache, rebuilt on access)
-        motion_preds["d_xyz"] = lambda: h_u[..., :3] * 1e-2 + h_p[..., :3] * 1e-2
-        motion_preds["d_scale"] = lambda: h_u[..., 8:11] + h_p[..., 8:11]
-        motion_preds["d_rot"] = lambda: h_u[..., 3:7] + h_p[..., 3:7]
-        if getattr(motion_net, "cache", None) is not None:
-            hd, pd = h_u.detach(), h_p.detach()
-            motion_net.cache["d_xyz"] = lambda: hd[..., :3] * 1e-2 + pd[..., :3] * 1e-2
-            motion_net.cache["d_scale"] = lambda: hd[..., 8:11] + pd[..., 8:11]
-            motion_net.cache["d_rot"] = lambda: hd[..., 3:7] + pd[..., 3:7]
-    elif fused_pers:
-        from .glue import deform_activate
-        h_sum = motion_preds["_h"] + p_motion_preds["_h"]
-        p_ = p_route if p_route is not None else p_motion_preds["_p"]
-        means3D, scales, rotations, opacity = deform_activate(xyz_route, pc._scaling, pc._rotation, pc._opacity, h_sum, p_)
-        # (the reference's in-place updates of the returned dictionary / motion_net.cache, :207-217, rebuilt on access)
-        motion_preds["d_xyz"] = lambda: (h_sum[..., :3] * 1e-2) * (torch.tanh(p_[..., 3:] / 5) * 0.25 + 1)
-        motion_preds["d_scale"], motion_preds["d_rot"] = h_sum[..., 8:11], h_sum[..., 3:7]
-        if getattr(motion_net, "cache", None) is not None:
-            hd, pd = h_sum.detach(), p_.detach()
-            motion_net.cache["d_xyz"] = lambda: (hd[..., :3] * 1e-2) * (torch.tanh(pd[..., 3:] / 5) * 0.25 + 1)
-            motion_net.cache["d_scale"], motion_net.cache["d_rot"] = hd[..., 8:11], hd[..., 3:7]
-    elif fused:
-        # deltas + softplus / normalize / sigmoid in one HIP kernel per pass (instag_amd/glue.py)
-        from .glue import deform_activate
-        p_in = p_route if p_route is not None else p_motion_preds["_p"]
-        h_in, amb_cut = motion_preds["_h"], None
-        if MARK_BACKWARD_CUT:
-            # every tensor through which a gradient crosses from the rasterizer side (deform operator, attention
-            # colours) to the motion fields goes through one identity node: the three-segment step's cut
-            amb_in = motion_preds["_amb3"] if (return_attn and SHARED_ATTN_PASS) else None
-            ins = [t for t in (xyz_route, h_in, p_in, amb_in) if t is not None]
-            cut_tensors = list(_BackwardCut.apply(*ins))
-            xyz_c, h_in, p_in = cut_tensors[0], cut_tensors[1], cut_tensors[2]
-            amb_cut = cut_tensors[3] if amb_in is not None else None
-        else:
-            xyz_c = xyz_route
-        outs_d = deform_activate(xyz_c, pc._scaling, pc._rotation, pc._opacity, h_in, p_in, motion_reg_weight)
-        means3D, scales, rotations, opacity = outs_d[:4]
-        motion_reg = outs_d[4] if motion_reg_weight is not None else None
-        # The reference scales the universal field's displacement IN PLACE (d_xyz *= p_scale, :217): the dictionary it
-        # returns under "motion" -- and motion_net.cache, the same object, which the mouth branch reads at inference
-        # (:362-363) -- holds the scaled value.  The fused operator never materialises it; the entries are rebuilt on
-        # first access (the regulariser inside deform_activate uses the scaled value too).
-        h_, p_ = motion_preds["_h"], p_motion_preds["_p"]
-        motion_preds["d_xyz"] = lambda: (h_[..., :3] * 1e-2) * (torch.tanh(p_[..., 3:] / 5) * 0.25 + 1)
-        if getattr(motion_net, "cache", None) is not None:
-            hd, pd = h_.detach(), p_.detach()
-            motion_net.cache["d_xyz"] = lambda: (hd[..., :3] * 1e-2) * (torch.tanh(pd[..., 3:] / 5) * 0.25 + 1)
+        d = _deform_pretrain_face(pc, motion_net, f, pretrain_heads, pretrain_reg)
+    elif _fused_pers_applies(pc, f, personalized, align, detach_motion, motion_reg_weight):
+        d = _deform_fused_pers(pc, motion_net, f)
+    elif _fused_applies(pc, f, personalized, align, detach_motion):
+        d = _deform_fused(pc, motion_net, f, motion_reg_weight, backward_cut, return_attn)
     else:
-        d_xyz, d_scale, d_rot = motion_preds["d_xyz"], motion_preds["d_scale"], motion_preds["d_rot"]
-        if personalized:
-            d_xyz = d_xyz + p_motion_preds["d_xyz"]
-            d_scale = d_scale + p_motion_preds["d_scale"]
-            d_rot = d_rot + p_motion_preds["d_rot"]
-        if align:
-            d_xyz = d_xyz * p_motion_preds["p_scale"]
-        # in-place semantics of the reference (d_xyz += ..., d_xyz *= p_scale mutate the entries of the returned
-        # dictionary and of motion_net.cache, gaussian_renderer/__init__.py:207-217): the regularisers of
-        # train_face.py:508-514 and the mouth branch's jaw feature at inference see the combined, scaled values
-        if personalized or align:
-            motion_preds["d_xyz"] = d_xyz
-            if personalized:
-                motion_preds["d_scale"], motion_preds["d_rot"] = d_scale, d_rot
-            cache = getattr(motion_net, "cache", None)
-            if cache is not None:
-                cache["d_xyz"] = d_xyz.detach()
-                if personalized:
-                    cache["d_scale"], cache["d_rot"] = d_scale.detach(), d_rot.detach()
-        if detach_motion:
-            d_xyz, d_scale, d_rot = d_xyz.detach(), d_scale.detach(), d_rot.detach()
-        means3D = xyz_route + d_xyz
-        opacity = pc.get_opacity
-        scales = pc.scaling_activation(pc._scaling + d_scale)
-        rotations = pc.rotation_activation(pc._rotation + d_rot)
-    ones = _ones(opacity)
-
-    def attn_colors(preds):
-        if preds.get("_amb3") is not None:
-            return preds["_amb3"]
-        eye = preds["ambient_eye"]
-        return torch.cat([preds["ambient_aud"], eye, torch.zeros_like(eye)], dim=-1)
-
-    def attn_pass(preds, carrier=None):
-        out = rasterizer(means3D=means3D.detach(), means2D=screenspace_points if carrier is None else carrier, shs=None,
-                         colors_precomp=attn_colors(preds), opacities=opacity.detach(), scales=scales.detach(),
-                         rotations=rotations.detach(), cov3Ds_precomp=None, extra_attrs=ones)
-        return out[0]
-
-    rendered_attn = p_rendered_attn = None
-    # The attention map is rendered over the same (detached) geometry as the image: on the device it rides along
-    # the main pass as an auxiliary colour set (one preprocess / binning / sort instead of two).
-    shared = return_attn and means3D.is_cuda and SHARED_ATTN_PASS
-    from . import _lib
-    fork = return_attn and means3D.is_cuda and CONCURRENT_PASSES and (personalized or not shared) \
-        and _lib.may_fork(dev)
-    if fork:
-        # remaining attention pass(es) only share inputs with the main pass: run them on a second stream
-        main_stream = torch.cuda.current_stream(dev)
-        side = _side_stream(dev)
-        # The screen-space gradient carrier is a leaf that the side-stream pass(es) AND the main pass write a gradient to.
-        # A leaf's gradient accumulator runs on ONE stream (the one current at the leaf's first use): fed directly from
-        # two streams, one of the producers always mismatches ("AccumulateGrad node's stream does not match").  The side
-        # passes therefore get a view made HERE, on the main stream: their gradient reaches the leaf through the view's
-        # backward node, which runs where the view was made.
-        side_carrier = screenspace_points.view_as(screenspace_points)
-        side.wait_stream(main_stream)
-        with torch.cuda.stream(side):
-            if not shared:
-                rendered_attn = attn_pass(motion_preds, side_carrier)
-            if personalized:
-                p_rendered_attn = attn_pass(p_motion_preds, side_carrier)
-
-    shs = pc.get_features_pair if (means3D.is_cuda and hasattr(pc, "get_features_pair")) else pc.get_features
-    aux = attn_colors(motion_preds) if shared else None
-    if cut_tensors is not None and shared:
-        aux = amb_cut
-    outs = rasterizer(
-        means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=opacity,
-        scales=scales, rotations=rotations, cov3Ds_precomp=None, extra_attrs=ones,
-        **({"aux_colors": aux} if shared else {}), **({} if need_geometry else {"geometry": False}))
-    image, depth, normal, alpha, radii, extra = outs[:6]
-    if shared:
-        rendered_attn = outs[6]
-
-    if fork:
-        main_stream.wait_stream(side)
-        for t in (rendered_attn, p_rendered_attn):
-            if t is not None:
-                _keepalive.cross_stream(t, main_stream)
-    elif return_attn:
-        if not shared:
-            rendered_attn = attn_pass(motion_preds)
-        if personalized:
-            p_rendered_attn = attn_pass(p_motion_preds)
-
-    from .motion_net import LazyOutputs
+        d = _deform_composed_face(pc, motion_net, f, personalized, align, detach_motion)
+    outs, rendered_attn, p_rendered_attn, forked = _render_passes(
+        rasterizer, pc, screenspace_points, d, f, return_attn, personalized, need_geometry)
+    image, depth, normal, alpha, radii = outs[:5]
     return LazyOutputs({"render": image, "viewspace_points": screenspace_points,
             "visibility_filter": lambda: radii > 0,      # one launch, only when somebody reads it
-            "depth": depth, "alpha": alpha, "normal": normal, "radii": radii, "motion": motion_preds,
-            "p_motion": p_motion_preds if personalized or align else None, "attn": rendered_attn,
-            "p_attn": p_rendered_attn, "motion_reg": motion_reg,
-            # (fused shared-pass path only; None otherwise)
-            "_cut": cut_tensors if (cut_tensors is not None and shared and not fork) else None})
+            "depth": depth, "alpha": alpha, "normal": normal, "radii": radii, "motion": f.motion,
+            "p_motion": f.p_motion if personalized or align else None, "attn": rendered_attn,
+            "p_attn": p_rendered_attn, "motion_reg": d.motion_reg,
+            "_cut": d.cut if (return_attn and not forked) else None})
 
 
 def _top_values(v, kmax, largest):
@@ -423,6 +481,35 @@ def _jaw_feature(h, column, scale, k):
     return out
 
 
+@torch.no_grad()
+def _jaw_movement(pc_face, motion_net_face, audio_feat, neutral, k):
+    """[1,3] jaw-movement feature of the mouth branch: [max, min, max - min] * 1e2 of the k-th largest / smallest vertical
+    displacement the FACE field predicts -- for a neutral expression, or (``neutral`` None: inference) as the face pass
+    left it in its cache.  (gaussian_renderer/__init__.py:361 evaluates the face field with autograd on and then reads
+    it under no_grad only, :365-372: no gradient can reach it.  Evaluated without a graph here: same values, no
+    activations saved, and -- when this pass runs on a stream of its own beside the face pass -- no gradient accumulators
+    of the face field's parameters created on that stream.)"""
+    preds = motion_net_face.cache if neutral is None else motion_net_face(pc_face.get_xyz, audio_feat, neutral)
+    h_face = None if neutral is None else dict.get(preds, "_h")
+    if (torch.is_tensor(h_face) and h_face.is_cuda and h_face.dim() == 2 and h_face.is_contiguous()
+            and h_face.dtype == torch.float32 and h_face.shape[0] >= 1 and (torch.is_tensor(k) or 1 <= int(k) <= 64)
+            and (not torch.is_tensor(k) or (k.is_cuda and k.dtype == torch.int64))):
+        # d_xyz[:, 1] = h[:, 1] * 1e-2 (scene/motion_net.py:330): selection, gather and the three products in one operator
+        return _jaw_feature(h_face.detach(), 1, 1e-2, k)
+    dy = preds["d_xyz"][..., 1]
+    if torch.is_tensor(k):
+        # k on the device (int64 [1], 1 <= k <= 50): a captured step draws a new k per replay without a host
+        # round trip -- the 50 largest / smallest once, the k-th of them by index
+        kmax = min(50, dy.shape[0])
+        kidx = (k.reshape(1) - 1).clamp(0, kmax - 1)
+        top, bottom = _extreme_values(dy, kmax)
+        motion_max, motion_min = top.gather(0, kidx)[0], bottom.gather(0, kidx)[0]
+    else:
+        top, bottom = _extreme_values(dy, k)
+        motion_max, motion_min = top[-1], bottom[-1]
+    return torch.stack([motion_max, motion_min, motion_max - motion_min]).reshape(1, 3) * 1e2
+
+
 def render_motion_mouth_con(viewpoint_camera, pc, motion_net, pc_face, motion_net_face, pipe=None, bg_color=None,
                             scaling_modifier=1.0, frame_idx=None, return_attn=False, personalized=False, align=False,
                             k=10, inference=False, pretrain_other=None, pretrain_reg=None):
@@ -440,121 +527,35 @@ def render_motion_mouth_con(viewpoint_camera, pc, motion_net, pc_face, motion_ne
                            "personalized=True, align=False, inference=False and the GPU")
     if pretrain_other is not None and not pretrain_reg:
         raise RuntimeError("pretrain_other: the contrast term is part of the partial sums (pretrain_reg=True)")
-    screenspace_points = _screenspace_points(pc)
-    rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
-                                              getattr(pipe, "debug", False)))
-    dev = pc.get_xyz.device
-    audio_feat = viewpoint_camera.talking_dict["auds"].to(dev, non_blocking=True)
-    xyz = pc.get_xyz
-    exp_feat = None
-    if xyz.is_cuda:
+    screenspace_points, rasterizer = _begin(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    neutral = None if inference else _neutral_expression(viewpoint_camera, pc.get_xyz.device)
+
+    def announce(audio_feat):
         # the per-frame branches of both fields depend on the frame only: announce them now, each on its own side stream
         if hasattr(motion_net, "start_audio"):
             motion_net.start_audio(audio_feat, 2)
         if not inference and hasattr(motion_net_face, "start_audio"):
-            exp_feat = _zeros_const(viewpoint_camera.talking_dict["au_exp"].to(dev, non_blocking=True))
-            motion_net_face.start_audio(audio_feat, 1, exp_feat)
-    p_motion_preds = None
-    # (as in render_motion: the positions feed the personalised field, the mouth field and the activation operator; each
-    # encode hands them on as an output, so their three gradients are summed inside the encoders' backward kernels
-    # instead of by two autograd add launches -- gridencoder.passthrough)
-    from . import gridencoder as _ge
-    carrier = {}
-    xyz_route = pc.get_xyz
-    if personalized or align:
-        with _ge.passthrough(carrier):
-            p_motion_preds = pc.neural_motion_grid(pc.get_xyz, audio_feat)
-        xyz_route = carrier.pop("xyz", xyz_route)
-        xyz = xyz_route
-    x_shift = None
-    if align:
-        p_raw = dict.get(p_motion_preds, "_p")
-        if torch.is_tensor(p_raw) and xyz.is_cuda and getattr(motion_net, "XYZ_SCALE", None) is not None:
-            x_shift = (p_raw, 1e-2)           # xyz + p_xyz (= p[:, :3] * 1e-2) is formed inside the tri-plane kernel
-        else:
-            xyz = xyz + p_motion_preds["p_xyz"]
-    if not inference:
-        if exp_feat is None:
-            exp_feat = _zeros_const(viewpoint_camera.talking_dict["au_exp"].to(dev, non_blocking=True))
-        # (gaussian_renderer/__init__.py:361 evaluates the face field with autograd on and then reads it under no_grad
-        # only, :365-372: no gradient can reach it.  Evaluated without a graph here: same values, no activations saved,
-        # and -- when this pass runs on a stream of its own beside the face pass -- no gradient accumulators of the
-        # face field's parameters created on that stream)
-        with torch.no_grad():
-            motion_preds_face = motion_net_face(pc_face.get_xyz, audio_feat, exp_feat)
-    else:
-        motion_preds_face = motion_net_face.cache
-    h_face = None if inference else dict.get(motion_preds_face, "_h")
-    if (torch.is_tensor(h_face) and h_face.is_cuda and h_face.dim() == 2 and h_face.is_contiguous()
-            and h_face.dtype == torch.float32 and h_face.shape[0] >= 1 and (torch.is_tensor(k) or 1 <= int(k) <= 64)
-            and (not torch.is_tensor(k) or (k.is_cuda and k.dtype == torch.int64))):
-        # d_xyz[:, 1] = h[:, 1] * 1e-2 (scene/motion_net.py:330): selection, gather and the three products in one operator
-        with torch.no_grad():
-            move_feat = _jaw_feature(h_face.detach(), 1, 1e-2, k)
-    else:
-        with torch.no_grad():
-            dy = motion_preds_face["d_xyz"][..., 1]
-            if torch.is_tensor(k):
-                # k on the device (int64 [1], 1 <= k <= 50): a captured step draws a new k per replay without a host
-                # round trip -- the 50 largest / smallest once, the k-th of them by index
-                kmax = min(50, dy.shape[0])
-                kidx = (k.reshape(1) - 1).clamp(0, kmax - 1)
-                top, bottom = _extreme_values(dy, kmax)
-                motion_max = top.gather(0, kidx)[0]
-                motion_min = bottom.gather(0, kidx)[0]
-            else:
-                top, bottom = _extreme_values(dy, k)
-                motion_max, motion_min = top[-1], bottom[-1]
-            move_feat = torch.stack([motion_max, motion_min, motion_max - motion_min]).reshape(1, 3) * 1e2
-    with _ge.passthrough(carrier):
-        if x_shift is not None:
-            motion_preds = motion_net(xyz, audio_feat, move_feat.detach(), x_shift=x_shift)
-        else:
-            motion_preds = motion_net(xyz, audio_feat, move_feat.detach())
-    if x_shift is not None or not align:
-        xyz_route = carrier.pop("xyz", xyz_route)     # (align without the fused shift encodes xyz + p_xyz, not xyz)
-    carrier.pop("shift", None)
-    h_raw, hs_raw = dict.get(motion_preds, "_h"), dict.get(motion_preds, "_hs")
-    motion_reg = None
+            motion_net_face.start_audio(audio_feat, 1, neutral)
+
+    def fused_shift(p_preds):
+        p_raw = dict.get(p_preds, "_p")
+        return p_raw if torch.is_tensor(p_raw) and getattr(motion_net, "XYZ_SCALE", None) is not None else None
+
+    f = _evaluate_fields(viewpoint_camera, pc, motion_net, personalized, align,
+                         lambda audio_feat: _jaw_movement(pc_face, motion_net_face, audio_feat, neutral, k).detach(),
+                         announce=announce, fused_shift=fused_shift)
     if pretrain:
-        h_p = p_motion_preds.get("_h")
-        if not (torch.is_tensor(h_raw) and torch.is_tensor(hs_raw) and h_raw.shape[-1] == 7 and torch.is_tensor(h_p)
-                and h_p.shape[-1] == 7):
-            raise RuntimeError("pretrain_other / pretrain_reg: both fields' raw 7-column heads are needed")
-        from .glue import pretrain_mouth_deform
-        scale = getattr(motion_net, "XYZ_SCALE", (1e-2 / 5, 1e-2, 1e-2 / 5))
-        outs_d = pretrain_mouth_deform(xyz_route, pc._scaling, pc._rotation, pc._opacity, h_raw, hs_raw, h_p,
-                                       pretrain_other, with_reg=bool(pretrain_reg), xyz_scale=scale)
-        means3D, scales, rotations, opacity = outs_d[:4]
-        motion_reg = outs_d[4] if pretrain_reg else None
-        # (the reference's in-place addition to the returned dictionary's entry, :387, rebuilt on access)
-        motion_preds["d_xyz"] = lambda: ((h_raw[..., :3] * h_raw.new_tensor(scale)) * torch.sigmoid(hs_raw) * 2
-                                         + h_p[..., :3] * 1e-2)
-    elif (not personalized and torch.is_tensor(h_raw) and torch.is_tensor(hs_raw) and h_raw.is_cuda
-            and h_raw.shape[-1] == 7):
-        # gated displacement + softplus / normalize / sigmoid in one HIP kernel per pass (instag_amd/glue.py)
-        from .glue import mouth_activate
-        means3D, scales, rotations, opacity = mouth_activate(xyz_route, pc._scaling, pc._rotation, pc._opacity, h_raw,
-                                                             hs_raw, getattr(motion_net, "XYZ_SCALE",
-                                                                             (1e-2 / 5, 1e-2, 1e-2 / 5)))
+        d = _deform_pretrain_mouth(pc, motion_net, f, pretrain_other, bool(pretrain_reg))
+    elif _mouth_activate_applies(f, personalized):
+        d = _deform_mouth_activate(pc, motion_net, f)
     else:
-        d_xyz = motion_preds["d_xyz"]
-        if personalized:
-            d_xyz = d_xyz + p_motion_preds["d_xyz"]
-        means3D = xyz_route + d_xyz
-        opacity = pc.get_opacity
-        scales, rotations = pc.get_scaling, pc.rotation_activation(pc._rotation)
-    # (dc and rest coefficients as the pair the model stores: no concatenation, no slice copies in backward)
-    shs = pc.get_features_pair if (means3D.is_cuda and hasattr(pc, "get_features_pair")) else pc.get_features
-    image, depth, normal, alpha, radii, extra = rasterizer(
-        means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=opacity,
-        scales=scales, rotations=rotations, cov3Ds_precomp=None, extra_attrs=_ones(opacity))
-    from .motion_net import LazyOutputs
+        d = _deform_composed_mouth(pc, f, personalized)
+    image, depth, normal, alpha, radii = _render_passes(rasterizer, pc, screenspace_points, d, f)[0][:5]
     return LazyOutputs({"render": image, "viewspace_points": screenspace_points,
                         "visibility_filter": lambda: radii > 0,          # built on first access
-                        "depth": depth, "alpha": alpha, "radii": radii, "motion": motion_preds,
-                        "p_motion": p_motion_preds if personalized or align else None,
-                        **({"motion_reg": motion_reg} if pretrain else {})})
+                        "depth": depth, "alpha": alpha, "radii": radii, "motion": f.motion,
+                        "p_motion": f.p_motion if personalized or align else None,
+                        **({"motion_reg": d.motion_reg} if pretrain else {})})
 
 
 def render_fuse(viewpoint_camera, pc, motion_net, pc_mouth, motion_net_mouth, pipe=None, bg_color=None,
@@ -571,7 +572,7 @@ def render_fuse(viewpoint_camera, pc, motion_net, pc_mouth, motion_net_mouth, pi
         # pass's cache): the two passes share nothing but parameters, so the mouth pass -- forward here, and with it
         # its whole backward -- runs on a second stream beside the face pass.  Each pass alone is a chain of short
         # kernels that leaves most of the chip idle.
-        main, side = torch.cuda.current_stream(dev), _side_stream((dev, "fuse"))
+        main, side = torch.cuda.current_stream(dev), _side_stream(dev, "fuse")
         _lib.leaf_stream(side)
         side.wait_stream(main)
         with torch.cuda.stream(side):
@@ -601,4 +602,3 @@ def render_fuse(viewpoint_camera, pc, motion_net, pc_mouth, motion_net_mouth, pi
         mouth_image = mr - bg3 * (1.0 - alpha_mouth) + scene_background * (1.0 - alpha_mouth)
         image = fr - bg3 * (1.0 - alpha) + mouth_image * (1.0 - alpha)
     return {"image": image, "mouth_image": mouth_image, "face": face, "mouth": mouth}
-

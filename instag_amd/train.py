@@ -486,12 +486,13 @@ class FaceTrainer:
         return self._p_dev if isinstance(self._lpips_p, str) else self._lpips_p
 
     # ---- one step ---------------------------------------------------------------------------------------------
-    def _forward_backward(self, frame: Frame, phase: FacePhase = C3_PHASE, fold_aux: bool = False):
+    def _forward_loss(self, frame: Frame, phase: FacePhase, backward_cut: bool = False):
+        """render_motion and the loss block of one face step -> (pkg, loss, Ll1)."""
         from .renderer import render_motion
         # (depth and normal are read by the prior terms alone: outside that phase the forward blend is colour-only)
         pkg = render_motion(frame, self.g, self.motion_net, None, self.bg, return_attn=True, personalized=False,
                             align=phase.align, motion_reg_weight=1e-5 if phase.warm else None,
-                            need_geometry=phase.priors)
+                            need_geometry=phase.priors, backward_cut=backward_cut)
         from contextlib import nullcontext
         from .losses import defer_finalize
         # (backward follows at once and the loss value is read after the step: the loss block's scalar stage rides in
@@ -500,6 +501,10 @@ class FaceTrainer:
         with (nullcontext() if (phase.priors or lpips_p is not None) else defer_finalize()):
             loss, Ll1 = self.loss_fn(frame, pkg, warm=phase.warm, hair_mask_iter=phase.hair_mask_iter,
                                      priors=phase.priors, prior_depth=phase.prior_depth, lpips_p=lpips_p)
+        return pkg, loss, Ll1
+
+    def _forward_backward(self, frame: Frame, phase: FacePhase = C3_PHASE, fold_aux: bool = False):
+        pkg, loss, Ll1 = self._forward_loss(frame, phase)
         from . import diff_gauss
         # fold_aux (only callers that run _stats_and_optimizers(pkg) next): the auxiliary image's share of the screen-space
         # gradient is added by the statistics kernel instead of by a launch of its own at the end of backward
@@ -524,25 +529,9 @@ class FaceTrainer:
         100k) are FINAL and in ``.grad``; ``finish()`` runs the rest of the backward pass (motion fields, encoders,
         position).  A data-parallel step exchanges the first bucket while ``finish()`` computes (GraphedStep "early").
         -> (pkg, loss, Ll1, early_params, finish)"""
-        from . import renderer
-        from .renderer import render_motion
         from . import diff_gauss
         assert self.on_gpu
-        renderer.MARK_BACKWARD_CUT = True
-        try:
-            pkg = render_motion(frame, self.g, self.motion_net, None, self.bg, return_attn=True, personalized=False,
-                                align=phase.align, motion_reg_weight=1e-5 if phase.warm else None,
-                                need_geometry=phase.priors)
-        finally:
-            renderer.MARK_BACKWARD_CUT = False
-        from contextlib import nullcontext
-        from .losses import defer_finalize
-        # (backward follows at once and the loss value is read after the step: the loss block's scalar stage rides in
-        # its backward launch -- unless the prior terms are ADDED to the value here, which needs it now)
-        lpips_p = self._lpips_arg()
-        with (nullcontext() if (phase.priors or lpips_p is not None) else defer_finalize()):
-            loss, Ll1 = self.loss_fn(frame, pkg, warm=phase.warm, hair_mask_iter=phase.hair_mask_iter,
-                                     priors=phase.priors, prior_depth=phase.prior_depth, lpips_p=lpips_p)
+        pkg, loss, Ll1 = self._forward_loss(frame, phase, backward_cut=True)
         cut = dict.get(pkg, "_cut")
         if not cut:
             raise RuntimeError("the three-segment step needs render_motion's fused path (align=True on the GPU)")

@@ -581,3 +581,27 @@ def test_segment_local_blending_matches_the_serial_recurrence():
             worst_c = max(worst_c, float(np.abs(C1 - C0).max()))
             worst_t = max(worst_t, abs(float(T1) - float(T0)) / max(float(T0), 1e-30))
     assert worst_c <= 2e-6 and worst_t <= 2e-6, (worst_c, worst_t)
+
+
+def test_renderer_constants_survive_the_carrier_buffers_eviction():
+    """instag_amd.renderer keeps its constants per kind: preparing the gradient carrier's zeros for more Gaussian counts
+    than it keeps drops old carrier buffers only -- the neutral-expression zeros and the extra_attrs ones requested
+    before are still the same objects -- and a carrier for the latest count is a leaf viewing the prepared buffer."""
+    from types import SimpleNamespace
+    from instag_amd import renderer
+    exp = torch.rand(6)
+    cam = SimpleNamespace(talking_dict={"au_exp": exp})
+    neutral = renderer._neutral_expression(cam, exp.device)
+    ones = renderer._constant("ones", torch.empty(77, 1), torch.ones_like)
+    assert torch.equal(neutral, torch.zeros(6)) and torch.equal(ones, torch.ones(77, 1))
+    for n in range(101, 101 + renderer._CARRIER_COUNTS + 3):
+        pc = SimpleNamespace(get_xyz=torch.rand(n, 3, requires_grad=True))
+        buf = renderer.prepare_screenspace(pc)
+        assert buf.shape == (n, 3) and not buf.requires_grad and not buf.any()
+    assert 1 <= len(renderer._CONSTANTS["carrier"]) <= renderer._CARRIER_COUNTS
+    assert renderer._neutral_expression(cam, exp.device) is neutral
+    assert renderer._constant("ones", torch.empty(77, 1), torch.ones_like) is ones
+    assert renderer.prepare_screenspace(pc) is buf
+    carrier = renderer._gradient_carrier(pc)
+    assert carrier.data_ptr() == buf.data_ptr() and carrier.requires_grad and carrier.is_leaf
+    assert carrier is not renderer._gradient_carrier(pc)            # (a fresh leaf per render: each collects its own .grad)

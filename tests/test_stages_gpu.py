@@ -588,7 +588,7 @@ def test_render_motion_branches_match_plain_torch(personalized, align):
     want = _detached(want)
     got = render_motion(frame, tr.g, tr.motion_net, None, tr.bg, return_attn=True, personalized=personalized,
                         align=align)
-    cache_dxyz = tr.motion_net.cache["d_xyz"]
+    cache = {k: tr.motion_net.cache[k] for k in ("d_xyz", "d_scale", "d_rot")}
     loss_of(got).backward()
     mine = _grads(tr)
     for k in ("render", "alpha", "depth", "normal", "attn") + (("p_attn",) if personalized else ()):
@@ -596,8 +596,9 @@ def test_render_motion_branches_match_plain_torch(personalized, align):
     assert torch.equal(got["radii"], want["radii"])
     for k in ("d_xyz", "d_rot", "d_scale"):
         assert float((got["motion"][k] - want["motion"][k]).abs().max()) <= 1e-7, k
-    assert not cache_dxyz.requires_grad
-    assert float((cache_dxyz - want["motion"]["d_xyz"].detach()).abs().max()) <= 1e-7
+    for k, v in cache.items():
+        assert not v.requires_grad, k
+        assert float((v - want["motion"][k].detach()).abs().max()) <= 1e-7, k
     assert set(mine) == set(ref), set(mine) ^ set(ref)
     for k in ref:
         scale = float(ref[k].abs().max())
