@@ -876,6 +876,43 @@ int instag_prep_frames(const uint8_t* ori, const uint8_t* parsing, const uint8_t
                        int32_t H, int32_t W, uint8_t* gt, uint8_t* torso, int32_t* cols, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Face parsing (csrc/parsing.hip): data_utils/face_parsing/test.py:72-106 -- BiSeNet(19) over ResNet-18
+ * (model.py, resnet.py) in eval mode on uint8 frames, the argmax of its classes and the colour map of
+ * parsing/<i>.png.  fp32, forward only, on the caller's stream, no host synchronisation.
+ *
+ *  weights: 32 layers in the order of instag_amd/parsing.py LAYERS (the stem, the eight residual blocks
+ *    as conv1, conv2[, downsample], arm32.conv, arm16.conv, conv_head32, conv_head16, ffm.convblk,
+ *    conv_out.conv, conv_out.conv_out, conv_avg, arm32.conv_atten, arm16.conv_atten, ffm.conv1, ffm.conv2):
+ *    w[l] = [K = cin * kh * kw][cout] with k = (cin, ky, kx), the stem's K = 147 padded with zero rows
+ *    to 160, for layers 0..26; [cout][cin] for the last five (1 x 1 on pooled vectors);
+ *    scale[l], shift[l] = [cout]: BatchNorm (eval) folded by the caller, (1, 0) where the layer
+ *    has none.
+ *  frames u8 [B,H,W,3] RGB, H and W multiples of 32 in [64, 4096], B * 16 * H * W < 2^31.  The stem reads
+ *    them in place as ((u / 255) - mean) / std, mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225).
+ *  Outputs, each may be NULL (not all three): logits8 [B,19,H/8,W/8], the output of conv_out; labels u8
+ *    [B,H,W], the first maximum over the classes of the logits interpolated bilinearly (align_corners)
+ *    to H x W; colours u8 [B,out_h,out_w,3] RGB, pixel (y,x) = the colour of label
+ *    (min(y H / out_h, H - 1), min(x W / out_w, W - 1)) in integers: class 0 (255,255,255), 1-10, 12, 13,
+ *    18 (0,0,255), 11 (100,100,100), 14, 15 (0,255,0), 16 (255,0,0), 17 (0,0,0).
+ *  workspace: instag_parsing_workspace_bytes(B,H,W) bytes (0 = bad argument), 256-byte aligned.
+ *  INSTAG_E_ARG / INSTAG_E_SPACE before any device work.  No atomics, a fixed K order: a frame's outputs
+ *  do not depend on the batch it sat in, and repeated runs give the same bits.
+ * parsing_labels: the final stage alone on logits8 [B,19,H/8,W/8] (H, W multiples of 8): labels and / or
+ *  colours as above, one launch (two when both are asked for at different sizes).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_parsing_weights {
+  const float* w[32];
+  const float* scale[32];
+  const float* shift[32];
+} instag_parsing_weights;
+size_t instag_parsing_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int instag_parsing_forward(const instag_parsing_weights* w, const uint8_t* frames, int32_t B, int32_t H, int32_t W,
+                           int32_t out_h, int32_t out_w, float* logits8, uint8_t* labels, uint8_t* colours,
+                           void* workspace, size_t workspace_bytes, instag_stream_t stream);
+int instag_parsing_labels(const float* logits8, int32_t B, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
+                          uint8_t* labels, uint8_t* colours, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Head-pose tracking from landmarks (csrc/track.hip): the landmark stages of the reference's 3DMM fit
  * (data_utils/face_tracking/face_tracker.py:62-205).  All tensors on the device, fp32, contiguous, unless
  * marked (host).

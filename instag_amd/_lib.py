@@ -39,6 +39,11 @@ class AveEncoderWeights(C.Structure):
     _fields_ = [("w", vp * 13), ("scale", vp * 13), ("shift", vp * 13)]
 
 
+class ParsingWeights(C.Structure):
+    """struct instag_parsing_weights (include/instag_hip.h)."""
+    _fields_ = [("w", vp * 32), ("scale", vp * 32), ("shift", vp * 32)]
+
+
 class FrameUnpackArgs(C.Structure):
     """struct instag_frame_unpack_args (include/instag_hip.h)."""
     _fields_ = [("store", vp), ("records", vp), ("normal", vp), ("depth", vp), ("audio", vp), ("dst", vp),
@@ -365,6 +370,9 @@ _PROTOS = {
     "instag_prep_background_workspace_bytes": (sz, [i32, i32, i32]),
     "instag_prep_background": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "instag_prep_frames": (C.c_int, [vp] * 4 + [i32] * 3 + [vp] * 4),
+    "instag_parsing_workspace_bytes": (sz, [i32, i32, i32]),
+    "instag_parsing_forward": (C.c_int, [C.POINTER(ParsingWeights), vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "instag_parsing_labels": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "instag_track_max_groups": (C.c_int, []),
     "instag_track_geometry": (C.c_int, [C.POINTER(TrackArgs), vp]),
     "instag_track_fit_pose": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, vp]),

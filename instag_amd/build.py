@@ -55,6 +55,7 @@ SOURCES = {
     # frames: the background composite is fp64 in numpy's operation order, every operation rounded once
     "frames.hip": ["-ffp-contract=off"],
     "prepare.hip": [],
+    "parsing.hip": [],
     "track.hip": [],
     "mesh_render.hip": [],
 }

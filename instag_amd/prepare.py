@@ -325,14 +325,19 @@ def list_frames(path):
     return ids
 
 
-def prepare_identity(path, device, every: int = 20, write: bool = True, batch: int = 256):
+def prepare_identity(path, device, every: int = 20, write: bool = True, batch: int = 256, parsing=None):
     """ori_imgs/*.jpg + parsing/*.png of ``path`` -> (bc [H,W,3], gt [N,H,W,3], torso [N,H,W,4]) uint8 on ``device``,
     frames in ascending numeric order, ready for FrameStore.append.  ``write``: also bc.jpg, gt_imgs/<i>.jpg (quality 95)
-    and torso_imgs/<i>.png, after which dataset.open_identity works on the directory."""
+    and torso_imgs/<i>.png, after which dataset.open_identity works on the directory.  ``parsing``: the parsing maps
+    u8 [N,H,W,3] in the same order (a tensor on any device or an array; parsing.parse_identity's result), used in place
+    of reading parsing/*.png."""
     from PIL import Image
     ids = list_frames(path)
     ori = np.stack([np.array(Image.open(os.path.join(path, "ori_imgs", f"{i}.jpg")).convert("RGB")) for i in ids])
-    parsing = np.stack([np.array(Image.open(os.path.join(path, "parsing", f"{i}.png")).convert("RGB")) for i in ids])
+    if parsing is None:
+        parsing = np.stack([np.array(Image.open(os.path.join(path, "parsing", f"{i}.png")).convert("RGB")) for i in ids])
+    elif tuple(parsing.shape) != ori.shape:
+        raise ValueError(f"prepare_identity: parsing {tuple(parsing.shape)}, the frames are {ori.shape}")
     device = torch.device(device)
     bc = extract_background(ori, parsing, every, device)
     gt, torso = gt_and_torso(ori, parsing, bc, batch, device)
