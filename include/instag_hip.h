@@ -913,6 +913,44 @@ int instag_parsing_labels(const float* logits8, int32_t B, int32_t H, int32_t W,
                           uint8_t* labels, uint8_t* colours, instag_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Teeth segmentation (csrc/teeth.hip): data_utils/easyportrait/create_teeth_mask.py with the fpn-fp
+ * config -- ResNetV1c-50, FPN and FPNHead of the vendored mmseg in eval mode on uint8 frames at their own
+ * size, the argmax of the C classes and (label == 7), the mask of teeth_mask/<i>.npy.  fp32, forward only,
+ * on the caller's stream, no host synchronisation.
+ *
+ *  weights: 71 convolutions in the order of instag_amd/teeth.py LAYERS (the three stem convolutions; the
+ *    sixteen bottlenecks as conv1, conv2, conv3[, downsample]; lateral_convs 0..3; fpn_convs 0..3;
+ *    scale_heads 0.0, 1.0, 2.0, 2.2, 3.0, 3.2, 3.4; conv_seg): w[l] = [K = cin * kh * kw][cout] with
+ *    k = (cin, ky, kx), the first stem convolution's K = 27 padded with zero rows to 32; scale[l],
+ *    shift[l] = [cout]: BatchNorm (eval) folded by the caller, (1, bias) for the neck and conv_seg.
+ *  frames u8 [B,H,W,3] RGB, H and W multiples of 32 in [64, 4096], B * 16 * H * W < 2^31.  The stem reads
+ *    them in place as (u - mean) / std, mean (143.55267075, 132.96705975, 126.94924335), std (60.2625333,
+ *    60.32740275, 59.30988645); the padding is zero after normalisation.
+ *  C = the rows of conv_seg, 8 <= C <= 32.
+ *  Outputs, each may be NULL (not all three): logits4 [B,C,H/4,W/4], the output of conv_seg; labels u8
+ *    [B,H,W], the first maximum over the classes of the logits interpolated bilinearly (align_corners =
+ *    False) to H x W -- the softmax the reference applies in between is monotone --; mask u8 [B,H,W] =
+ *    (label == 7).
+ *  workspace: instag_teeth_workspace_bytes(B,H,W) bytes (0 = bad argument; 100 MiB per frame at 512 x 512),
+ *    256-byte aligned.
+ *  INSTAG_E_ARG / INSTAG_E_SPACE before any device work.  No atomics, a fixed K order: a frame's outputs
+ *  do not depend on the batch it sat in, and repeated runs give the same bits.
+ * teeth_labels: the final stage alone on logits4 [B,C,H/4,W/4] (H, W multiples of 4): labels and / or
+ *  mask as above, one launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct instag_teeth_weights {
+  const float* w[71];
+  const float* scale[71];
+  const float* shift[71];
+} instag_teeth_weights;
+size_t instag_teeth_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int instag_teeth_forward(const instag_teeth_weights* w, const uint8_t* frames, int32_t B, int32_t H, int32_t W,
+                         int32_t C, float* logits4, uint8_t* labels, uint8_t* mask, void* workspace,
+                         size_t workspace_bytes, instag_stream_t stream);
+int instag_teeth_labels(const float* logits4, int32_t B, int32_t H, int32_t W, int32_t C, uint8_t* labels,
+                        uint8_t* mask, instag_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Head-pose tracking from landmarks (csrc/track.hip): the landmark stages of the reference's 3DMM fit
  * (data_utils/face_tracking/face_tracker.py:62-205).  All tensors on the device, fp32, contiguous, unless
  * marked (host).

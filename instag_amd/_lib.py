@@ -44,6 +44,11 @@ class ParsingWeights(C.Structure):
     _fields_ = [("w", vp * 32), ("scale", vp * 32), ("shift", vp * 32)]
 
 
+class TeethWeights(C.Structure):
+    """struct instag_teeth_weights (include/instag_hip.h)."""
+    _fields_ = [("w", vp * 71), ("scale", vp * 71), ("shift", vp * 71)]
+
+
 class FrameUnpackArgs(C.Structure):
     """struct instag_frame_unpack_args (include/instag_hip.h)."""
     _fields_ = [("store", vp), ("records", vp), ("normal", vp), ("depth", vp), ("audio", vp), ("dst", vp),
@@ -373,6 +378,9 @@ _PROTOS = {
     "instag_parsing_workspace_bytes": (sz, [i32, i32, i32]),
     "instag_parsing_forward": (C.c_int, [C.POINTER(ParsingWeights), vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "instag_parsing_labels": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "instag_teeth_workspace_bytes": (sz, [i32, i32, i32]),
+    "instag_teeth_forward": (C.c_int, [C.POINTER(TeethWeights), vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "instag_teeth_labels": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
     "instag_track_max_groups": (C.c_int, []),
     "instag_track_geometry": (C.c_int, [C.POINTER(TrackArgs), vp]),
     "instag_track_fit_pose": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, vp]),

@@ -56,6 +56,7 @@ SOURCES = {
     "frames.hip": ["-ffp-contract=off"],
     "prepare.hip": [],
     "parsing.hip": [],
+    "teeth.hip": [],
     "track.hip": [],
     "mesh_render.hip": [],
 }

@@ -4,7 +4,7 @@
 //
 // BatchNorm arrives folded into a per-channel (scale, shift) pair (instag_amd/parsing.py: device_pack), so a
 // convolution block is act(scale * conv(x) + shift [+ residual]).
-//   convolutions  implicit GEMM on the f32-input MFMA (v_mfma_f32_32x32x2_f32) as in lpips.hip / ave_encoder.hip:
+//   convolutions  conv_mfma.hpp (shared with teeth.hip): implicit GEMM on the f32-input MFMA (v_mfma_f32_32x32x2_f32):
 //                 D[cout][m] with m = (frame, oy, ox) tiled jointly -- at 1/32 resolution a frame has a few hundred
 //                 positions and the batch is what fills the tile -- and k = (cin, ky, kx) gathered from NCHW activations.
 //                 Four waves of one or two accumulators of 32 x 32 each; scale, shift, the residual read and the ReLU are
@@ -24,225 +24,19 @@
 // element reads nothing but its own frame: a frame's outputs do not depend on the batch, the chunk or the tile it sat
 // in, and two runs give the same bits.
 #include "common.hpp"
+#include "conv_mfma.hpp"
 
 namespace instag {
 namespace {
 
 constexpr int NLAYER = 32;
 constexpr int NCLS = 19;
-constexpr int TB = 256;
-constexpr int BK = 32;
-constexpr int STEM_K = 147, STEM_K_PADDED = 160;
-constexpr int MIN_BLOCKS = 512;    // two workgroups for each of the 256 CUs
 
 // order of instag_parsing_weights (instag_amd/parsing.py: LAYERS)
 enum Layer {
   L_STEM = 0, L_LAYER1 = 1, L_LAYER2 = 5, L_LAYER3 = 10, L_LAYER4 = 15, L_ARM32 = 20, L_ARM16 = 21, L_HEAD32 = 22,
   L_HEAD16 = 23, L_FFM = 24, L_OUT_MID = 25, L_OUT = 26, L_AVG = 27, L_ATT32 = 28, L_ATT16 = 29, L_FFM1 = 30, L_FFM2 = 31,
 };
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// ---- convolution as implicit GEMM --------------------------------------------------------------------------------------
-struct ConvArgs {
-  const float* in;        // [B, c_split, hi >> up, wi >> up]
-  const float* in2;       // channels c_split .. cin - 1: [B, cin - c_split, hi >> up, wi >> up]; NULL: c_split == cin
-  const uint8_t* frames;  // the stem: [B, hi, wi, 3]
-  const float* mul;       // [B, cin]: the value becomes v * mul + (v | add_bc | add_sp); NULL: v
-  const float* add_bc;    // [B, cin]
-  const float* add_sp;    // [B, cin, hi >> up, wi >> up]
-  const float* wt;        // [K][cout]
-  const float* scale;     // [cout]
-  const float* shift;
-  const float* res;       // [B, cout, ho, wo] added before the ReLU, or NULL
-  float* out;             // [B, cout, ho, wo]
-  int B, cin, c_split, cout, hi, wi, ho, wo, stride, up, self_add, relu;
-};
-
-// KS: 1, 3 (pad KS / 2) or 7 (the stem).  64 output channels x 64 WN positions per workgroup, four waves as 2 x 2,
-// each with WN accumulators of 32 x 32.
-template <int KS, int WN, bool PLAIN>
-__global__ void __launch_bounds__(TB) conv_kernel(ConvArgs a) {
-  constexpr int BM = 64, BN = 64 * WN;
-  constexpr int NA = BK * BM / TB, NB = BK * BN / TB;          // elements a thread stages per K tile
-  constexpr int RA = TB / BM, RB = TB / BN;                    // K rows one pass of the workgroup covers
-  constexpr int PAD = KS / 2;
-  __shared__ float As[BK][BM];
-  __shared__ float Bs[BK][BN];
-  __shared__ float lut[KS == 7 ? 3 * 256 : 1];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1;
-  if constexpr (KS == 7) {
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdev[3] = {0.229f, 0.224f, 0.225f};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) lut[c * 256 + t] = ((float)t / 255.f - mean[c]) / stdev[c];   // TB == 256
-  }
-  const int HWo = a.ho * a.wo;
-  const int N = a.B * HWo;
-  const int n0 = blockIdx.x * BN, c0 = blockIdx.y * BM;
-  const int ta = t % BM, ka = t / BM;
-  const int tb = t % BN, kb = t / BN;
-  const int hs = a.hi >> a.up, ws = a.wi >> a.up;
-  const int c2 = a.cin - a.c_split;
-
-  // this thread's column of the gathered operand: one output position of one frame
-  const int ng = n0 + tb;
-  const bool nv = ng < N;
-  int img = 0, oy = 0, ox = 0;
-  if (nv) {
-    img = ng / HWo;
-    const int pos = ng - img * HWo;
-    oy = pos / a.wo;
-    ox = pos - oy * a.wo;
-  }
-  const int iy0 = oy * a.stride - PAD, ix0 = ox * a.stride - PAD;
-  const bool wv = c0 + ta < a.cout;
-  // PLAIN (one source, no upsample, no attention): bit r of `inside` = tap r = ky KS + kx lies inside the image
-  uint32_t inside = 0;
-  const int plane = a.hi * a.wi;
-  int64_t off0 = 0;
-  if constexpr (PLAIN) {
-    static_assert(KS * KS <= 32, "one bit per tap");
-    if (nv)
-#pragma unroll
-      for (int r = 0; r < KS * KS; ++r) {
-        const int iy = iy0 + r / KS, ix = ix0 + r % KS;
-        if (iy >= 0 && iy < a.hi && ix >= 0 && ix < a.wi) inside |= 1u << r;
-      }
-    off0 = (int64_t)img * a.cin * plane + iy0 * a.wi + ix0;
-  }
-
-  auto gather = [&](int k) -> float {
-    const int ci = k / (KS * KS);
-    const int r = k - ci * (KS * KS);
-    const int ky = r / KS, kx = r - ky * KS;
-    if constexpr (PLAIN) {
-      if (!((inside >> r) & 1u)) return 0.f;
-      return a.in[off0 + (ci * plane + ky * a.wi + kx)];
-    }
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    if (!nv || iy < 0 || iy >= a.hi || ix < 0 || ix >= a.wi) return 0.f;
-    if constexpr (KS == 7) {
-      if (k >= STEM_K) return 0.f;
-      return lut[ci * 256 + a.frames[((size_t)(img * a.hi + iy) * a.wi + ix) * 3 + ci]];
-    }
-    const int sy = iy >> a.up, sx = ix >> a.up;
-    size_t idx;
-    const float* src;
-    if (ci < a.c_split) {
-      src = a.in;
-      idx = ((size_t)(img * a.c_split + ci) * hs + sy) * ws + sx;
-    } else {
-      src = a.in2;
-      idx = ((size_t)(img * c2 + ci - a.c_split) * hs + sy) * ws + sx;
-    }
-    float v = src[idx];
-    if (a.mul) {
-      const int bc = img * a.cin + ci;
-      const float other = a.self_add ? v : a.add_bc ? a.add_bc[bc] : a.add_sp[idx];
-      v = v * a.mul[bc] + other;
-    }
-    return v;
-  };
-
-  float ra[NA], rb[NB];
-  auto load = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) ra[i] = wv ? a.wt[(size_t)(kt * BK + ka + RA * i) * a.cout + c0 + ta] : 0.f;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) rb[i] = gather(kt * BK + kb + RB * i);
-  };
-
-  f32x16 acc[WN], part[WN];
-#pragma unroll
-  for (int j = 0; j < WN; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  const int nk = KS == 7 ? STEM_K_PADDED / BK : a.cin * KS * KS / BK;      // cin is a multiple of 32
-  if (KS == 7) __syncthreads();                                             // the table
-  load(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NA; ++i) As[ka + RA * i][ta] = ra[i];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) Bs[kb + RB * i][tb] = rb[i];
-    __syncthreads();
-    if (kt + 1 < nk) load(kt + 1);
-#pragma unroll
-    for (int j = 0; j < WN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) part[j][r] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-      const float av = As[kk * 2 + (lane >> 5)][wr * 32 + (lane & 31)];
-#pragma unroll
-      for (int j = 0; j < WN; ++j) {
-        const float bv = Bs[kk * 2 + (lane >> 5)][(wc * WN + j) * 32 + (lane & 31)];
-        part[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, part[j], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < WN; ++j) acc[j] += part[j];
-  }
-
-  // D: column (lane & 31) = output position, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = output channel
-#pragma unroll
-  for (int j = 0; j < WN; ++j) {
-    const int nc = n0 + (wc * WN + j) * 32 + (lane & 31);
-    if (nc >= N) continue;
-    const int oimg = nc / HWo, opos = nc - oimg * HWo;
-    const size_t obase = (size_t)oimg * a.cout * HWo + opos;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = c0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (co >= a.cout) continue;
-      const size_t o = obase + (size_t)co * HWo;
-      float v = fmaf(acc[j][r], a.scale[co], a.shift[co]);
-      if (a.res) v += a.res[o];
-      a.out[o] = a.relu ? fmaxf(v, 0.f) : v;
-    }
-  }
-}
-
-template <int KS, int WN>
-int launch_conv_tile(const ConvArgs& a, hipStream_t st) {
-  const int N = a.B * a.ho * a.wo;
-  const dim3 grid((unsigned)div_up(N, 64 * WN), (unsigned)div_up(a.cout, 64));
-  if (KS != 7 && !a.in2 && !a.mul && !a.up) {
-    conv_kernel<KS, WN, (KS != 7)><<<grid, TB, 0, st>>>(a);
-  } else {
-    conv_kernel<KS, WN, false><<<grid, TB, 0, st>>>(a);
-  }
-  INSTAG_CHECK_LAUNCH();
-  return INSTAG_OK;
-}
-
-// the largest tile that still gives every CU two workgroups (the arithmetic does not depend on the choice)
-template <int KS>
-int launch_conv(const ConvArgs& a, hipStream_t st) {
-  const int N = a.B * a.ho * a.wo;
-  if (div_up(N, 128) * div_up(a.cout, 64) >= MIN_BLOCKS) return launch_conv_tile<KS, 2>(a, st);
-  return launch_conv_tile<KS, 1>(a, st);
-}
-
-// ---- 3 x 3 max-pool, stride 2, pad 1 -----------------------------------------------------------------------------------
-__global__ void __launch_bounds__(TB) maxpool_kernel(const float* in, float* out, int planes, int hi, int wi, int ho,
-                                                     int wo) {
-  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  if (i >= (size_t)planes * ho * wo) return;
-  const int x = (int)(i % wo), y = (int)((i / wo) % ho);
-  const size_t p = i / ((size_t)wo * ho);
-  const float* src = in + p * hi * wi;
-  float m = -INFINITY;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int yy = 2 * y + dy, xx = 2 * x + dx;
-      if (yy >= 0 && yy < hi && xx >= 0 && xx < wi) m = fmaxf(m, src[(size_t)yy * wi + xx]);
-    }
-  out[i] = m;
-}
 
 // ---- global average pool: one wave per (frame, channel) ------------------------------------------------------------------
 __global__ void __launch_bounds__(TB) pool_kernel(const float* in, float* out, int planes, int n) {
