@@ -441,6 +441,21 @@ def check(code: int, what: str = ""):
         raise RuntimeError(f"{what}: {msg}" if what else msg)
 
 
+def check_arg(code: int, what: str):
+    """``check`` for the entry points whose callers tell a refused argument from a failure: ValueError for
+    INSTAG_E_ARG (1), RuntimeError for every other non-zero code."""
+    if code != 0:
+        msg = lib().instag_last_error().decode("utf-8", "replace")
+        raise (ValueError if code == 1 else RuntimeError)(f"{what}: {msg}")
+
+
+def workspace_bytes(nbytes: int) -> int:
+    """The result of a ``*_workspace_bytes`` entry point: 0 says the shape was refused -> ValueError with its text."""
+    if nbytes == 0:
+        raise ValueError(lib().instag_last_error().decode("utf-8", "replace"))
+    return int(nbytes)
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())

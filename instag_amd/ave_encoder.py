@@ -23,6 +23,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import convnet
+from .convnet import BN_EPS
+
 # (cin, cout, kernel, (stride_h, stride_w), padding, residual): scene/motion_net.py:106-123
 LAYERS = (
     (1, 32, 3, (1, 1), 1, False), (32, 32, 3, (1, 1), 1, True), (32, 32, 3, (1, 1), 1, True),
@@ -32,108 +35,48 @@ LAYERS = (
     (256, 512, 3, (1, 1), 0, False), (512, 512, 1, (1, 1), 0, False),
 )
 N_MELS, WINDOW, DIM_OUT = 80, 16, 512
-BN_EPS = 1e-5
 FPS, MEL_PER_SECOND = 25., 80.                       # utils/audio_utils.py:125,135
 MACS_PER_WINDOW = sum(ci * co * k * k * ho * wo for (ci, co, k, _, _, _), (ho, wo) in zip(
     LAYERS, ((80, 16),) * 3 + ((27, 16),) * 3 + ((9, 6),) * 3 + ((3, 3),) * 2 + ((1, 1),) * 2))
 
-_FIELDS = (("weight", "conv_block.0.weight"), ("bias", "conv_block.0.bias"), ("gamma", "conv_block.1.weight"),
-           ("beta", "conv_block.1.bias"), ("mean", "conv_block.1.running_mean"), ("var", "conv_block.1.running_var"))
+# convnet's table: block i is ``{i}.conv_block.0`` (convolution, with a bias) and ``{i}.conv_block.1`` (BatchNorm)
+_TABLE = tuple((f"{i}.conv_block.0", f"{i}.conv_block.1", True, ci, co, k, stride)
+               for i, (ci, co, k, stride, _, _) in enumerate(LAYERS))
 
 
 # ---- weights ----------------------------------------------------------------------------------------------------------
-class AudioEncoderWeights:
+class AudioEncoderWeights(convnet.ConvWeights):
     """The frozen parameters: per layer the convolution's weight and bias and BatchNorm's gamma, beta, running mean and
-    running variance.  Kept in fp32 on the CPU; the device copy (convolutions in the kernels' layout, BatchNorm folded)
-    is made once per device (``device_pack``)."""
+    running variance (convnet.ConvWeights).  On the device the first layer stays as stored, [32][9]."""
 
-    def __init__(self, layers):
-        if len(layers) != len(LAYERS):
-            raise ValueError(f"AudioEncoder weights: expected {len(LAYERS)} layers, got {len(layers)}")
-        self.layers = []
-        for i, (lay, (ci, co, k, _, _, _)) in enumerate(zip(layers, LAYERS)):
-            lay = {f: lay[f].detach().float().contiguous().cpu() for f, _ in _FIELDS}
-            for f, _ in _FIELDS:
-                want = (co, ci, k, k) if f == "weight" else (co,)
-                if tuple(lay[f].shape) != want:
-                    raise ValueError(f"AudioEncoder weights: layer {i} {f} has shape {tuple(lay[f].shape)}, "
-                                     f"expected {want}")
-            self.layers.append(lay)
-        self._packs = {}
+    TABLE, LABEL, STRUCT, COUT_MAJOR = _TABLE, "AudioEncoder weights", "AveEncoderWeights", (0,)
+
+    @staticmethod
+    def _layer_name(l):
+        return f"layer {l}"
 
     @classmethod
     def from_state_dict(cls, sd) -> "AudioEncoderWeights":
         """``sd``: the keys of audio_visual_encoder.pth as shipped, ``{i}.conv_block.{0,1}.*``, or the
         ``audio_encoder.``-prefixed form dataset_readers.py:118 builds (``AudioEncoder().state_dict()``)."""
         prefix = "audio_encoder." if any(k.startswith("audio_encoder.") for k in sd) else ""
-        layers = []
-        for i in range(len(LAYERS)):
-            lay = {}
-            for f, name in _FIELDS:
-                key = f"{prefix}{i}.{name}"
-                if key not in sd:
-                    raise KeyError(f"AudioEncoder weights: layer {i} misses {key!r}")
-                lay[f] = sd[key]
-            layers.append(lay)
-        return cls(layers)
-
-    @classmethod
-    def load(cls, path) -> "AudioEncoderWeights":
-        return cls.from_state_dict(torch.load(path, map_location="cpu"))
+        return cls._read({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}, lambda l, key: KeyError(
+            f"AudioEncoder weights: layer {l} misses {prefix + key!r}"))
 
     @classmethod
     def random(cls, seed: int = 0) -> "AudioEncoderWeights":
-        """Seeded stand-ins with the scale of trained ones (tests, benches): He-scaled convolutions, biases of about
-        0.1 and non-trivial BatchNorm statistics -- gamma and the variance in [0.5, 1.5], beta and the running mean of
-        about 0.2 -- so that the fold is exercised and about half of every layer's units are active."""
+        """Seeded stand-ins with the scale of trained ones (tests, benches; convnet.draw_layer), so that the fold is
+        exercised and about half of every layer's units are active."""
         g = torch.Generator().manual_seed(seed)
-        layers = []
-        for ci, co, k, _, _, _ in LAYERS:
-            layers.append(dict(
-                weight=torch.randn(co, ci, k, k, generator=g) * (2.0 / (ci * k * k)) ** 0.5,
-                bias=torch.randn(co, generator=g) * 0.1,
-                gamma=torch.rand(co, generator=g) + 0.5,
-                beta=torch.randn(co, generator=g) * 0.2,
-                mean=torch.randn(co, generator=g) * 0.2,
-                var=torch.rand(co, generator=g) + 0.5))
-        return cls(layers)
+        return cls([convnet.draw_layer(g, row) for row in _TABLE])
 
     def state_dict(self, prefix: str = ""):
         """The keys of the shipped file (``prefix="audio_encoder."``: those of the reference module)."""
-        return {f"{prefix}{i}.{name}": lay[f].clone() for i, lay in enumerate(self.layers) for f, name in _FIELDS}
+        return {f"{prefix}{key}": lay[f].clone() for lay, row in zip(self.layers, _TABLE) for f, key in convnet.keys(row)}
 
     def to(self, device=None, dtype=None):
         """The list of per-layer dicts as tensors of ``device`` / ``dtype`` for the torch statement."""
-        return [{f: t.to(device=device, dtype=dtype) for f, t in lay.items()} for lay in self.layers]
-
-    def folded(self, dtype=torch.float64):
-        """Per layer (bias-free convolution weight, scale, shift) with BatchNorm (eval) and the convolution bias
-        folded in fp64: scale = gamma / sqrt(var + eps), shift = (b_conv - mean) * scale + beta."""
-        out = []
-        for lay in self.layers:
-            d = {f: t.double() for f, t in lay.items()}
-            scale = d["gamma"] / torch.sqrt(d["var"] + BN_EPS)
-            shift = (d["bias"] - d["mean"]) * scale + d["beta"]
-            out.append((d["weight"].to(dtype), scale.to(dtype), shift.to(dtype)))
-        return out
-
-    def device_pack(self, device):
-        """struct instag_ave_encoder_weights for ``device`` (and the tensors it points into)."""
-        from . import _lib
-        device = torch.device(device)
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        pack = self._packs.get(key)
-        if pack is not None:
-            return pack
-        keep, s = [], _lib.AveEncoderWeights()
-        for l, (w, scale, shift) in enumerate(self.folded(torch.float32)):
-            co = w.shape[0]
-            wk = w.reshape(co, -1) if l == 0 else w.reshape(co, -1).t()          # [32][9] / [K = (cin, ky, kx)][cout]
-            ts = [t.contiguous().to(device) for t in (wk, scale, shift)]
-            keep += ts
-            s.w[l], s.scale[l], s.shift[l] = [t.data_ptr() for t in ts]
-        pack = self._packs[key] = (s, keep)
-        return pack
+        return list(super().to(device, dtype).values())
 
 
 # ---- plain-torch statement -------------------------------------------------------------------------------------------
@@ -190,10 +133,9 @@ class AudioEncoder:
             self._struct, self._keep = weights.device_pack(self.device)
 
     def _workspace(self, batch):
+        from . import _lib
         if self._ws is None or self._ws[0] < batch:
-            nbytes = self._L.instag_ave_encoder_workspace_bytes(batch)
-            if nbytes == 0:
-                raise ValueError(self._L.instag_last_error().decode("utf-8", "replace"))
+            nbytes = _lib.workspace_bytes(self._L.instag_ave_encoder_workspace_bytes(batch))
             self._ws = (batch, torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes)
         return self._ws[1], self._ws[2]
 

@@ -34,6 +34,9 @@ void set_error(const std::string& msg);
 
 #define INSTAG_CHECK_LAUNCH() INSTAG_CHECK_HIP(hipGetLastError())
 
+// a step that returns a code of its own (and has set the error text): leave with it unless it is INSTAG_OK
+#define INSTAG_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
+
 // ---- per-kernel event timing (bench.py roofline leg) -----------------------------------------
 enum ProfKernel {
   K_PREPROCESS = 0, K_DUPLICATE = 1, K_SORT = 2, K_RANGES = 3, K_BLEND_FWD = 4, K_BLEND_BWD = 5,
@@ -68,6 +71,12 @@ static inline int set_max_dynamic_lds(const void* kernel, int bytes) {
 }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// offsets of the pieces of a workspace, in floats: every piece starts at a multiple of 64
+struct Arena {
+  size_t off = 0;
+  size_t take(size_t n) { const size_t o = off; off += align_up(n, 64); return o; }
+};
 
 // ---- rasterizer buffer layouts (device memory, opaque to the caller) ----------------------------
 constexpr int TILE_X = 16;

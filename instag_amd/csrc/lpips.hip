@@ -473,15 +473,14 @@ int make_plan(int H, int W, int pmin, int pmax, int nstack, Plan* out, const cha
     pl.m[2] = std::max(pl.m[2], (size_t)d.n * d.q2 * d.q2);
   }
   INSTAG_REQUIRE(pl.n_max <= 65534, std::string(who) + ": too many patches");
-  size_t o = 0;
-  auto take = [&](size_t floats) { const size_t at = o; o += align_up(floats, 64); return at; };
-  for (int t = 0; t < NTAP; ++t) pl.act[t] = take(2 * pl.a[t]);
-  for (int t = 0; t < 2; ++t) pl.pool[t] = take(2 * pl.pl[t]);
-  for (int t = 0; t < 2; ++t) pl.idx[t] = take((pl.pl[t] + 3) / 4);
-  for (int t = 0; t < NTAP; ++t) pl.grad[t] = take(pl.a[t]);
-  for (int t = 0; t < 2; ++t) pl.pgrad[t] = take(pl.pl[t]);
-  pl.tapval = take((size_t)NTAP * pl.n_max);
-  pl.total = o;
+  Arena ws;
+  for (int t = 0; t < NTAP; ++t) pl.act[t] = ws.take(2 * pl.a[t]);
+  for (int t = 0; t < 2; ++t) pl.pool[t] = ws.take(2 * pl.pl[t]);
+  for (int t = 0; t < 2; ++t) pl.idx[t] = ws.take((pl.pl[t] + 3) / 4);
+  for (int t = 0; t < NTAP; ++t) pl.grad[t] = ws.take(pl.a[t]);
+  for (int t = 0; t < 2; ++t) pl.pgrad[t] = ws.take(pl.pl[t]);
+  pl.tapval = ws.take((size_t)NTAP * pl.n_max);
+  pl.total = ws.off;
   INSTAG_REQUIRE(2 * pl.a[0] <= 0x7fffffffull && 2 * pl.a[1] <= 0x7fffffffull, std::string(who) + ": problem too large");
   *out = pl;
   return INSTAG_OK;

@@ -2,7 +2,7 @@
 // fp32, forward only, from uint8 frames to labels and the colour map of parsing/<i>.png (include/instag_hip.h, "Face
 // parsing").
 //
-// BatchNorm arrives folded into a per-channel (scale, shift) pair (instag_amd/parsing.py: device_pack), so a
+// BatchNorm arrives folded into a per-channel (scale, shift) pair (instag_amd/convnet.py: device_pack), so a
 // convolution block is act(scale * conv(x) + shift [+ residual]).
 //   convolutions  conv_mfma.hpp (shared with teeth.hip): implicit GEMM on the f32-input MFMA (v_mfma_f32_32x32x2_f32):
 //                 D[cout][m] with m = (frame, oy, ox) tiled jointly -- at 1/32 resolution a frame has a few hundred
@@ -93,20 +93,7 @@ __global__ void __launch_bounds__(TB) label_kernel(const float* logits, int B, i
   const int x = (int)(i % ow), y = (int)((i / ow) % oh);
   const int b = (int)(i / ((size_t)ow * oh));
   const int py = min((int)(((int64_t)y * H) / oh), H - 1), px = min((int)(((int64_t)x * W) / ow), W - 1);
-  const float fy = (H > 1 ? (float)(h8 - 1) / (float)(H - 1) : 0.f) * (float)py;
-  const float fx = (W > 1 ? (float)(w8 - 1) / (float)(W - 1) : 0.f) * (float)px;
-  const int y0 = min((int)fy, h8 - 1), x0 = min((int)fx, w8 - 1);
-  const int y1 = min(y0 + 1, h8 - 1), x1 = min(x0 + 1, w8 - 1);
-  const float ly = fminf(fmaxf(fy - (float)y0, 0.f), 1.f), lx = fminf(fmaxf(fx - (float)x0, 0.f), 1.f);
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  const float* src = logits + (size_t)b * NCLS * h8 * w8;
-  float best = 0.f;
-  int arg = 0;
-  for (int c = 0; c < NCLS; ++c) {
-    const float* p = src + (size_t)c * h8 * w8;
-    const float v = hy * (hx * p[y0 * w8 + x0] + lx * p[y0 * w8 + x1]) + ly * (hx * p[y1 * w8 + x0] + lx * p[y1 * w8 + x1]);
-    if (c == 0 || v > best) { best = v; arg = c; }             // the first maximum
-  }
+  const int arg = bilinear_argmax<true>(logits + (size_t)b * NCLS * h8 * w8, NCLS, h8, w8, H, W, py, px);
   if (labels) labels[i] = (uint8_t)arg;
   if (colours) colour_of(arg, colours + i * 3);
 }
@@ -146,39 +133,33 @@ Layout layout(int B, int H, int W) {
   Layout l;
   const size_t b = (size_t)B;
   const size_t p2 = (size_t)(H / 2) * (W / 2), p4 = p2 / 4, p8 = p4 / 4, p16 = p8 / 4, p32 = p16 / 4;
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += align_up(n, 64); return o; };
-  l.stem = take(b * 64 * p2);
-  const size_t after_stem = off;
-  off = l.stem;
-  l.arm32 = take(b * 128 * p32);
-  l.arm16 = take(b * 128 * p16);
-  l.cp16 = take(b * 128 * p16);
-  l.cp8 = take(b * 128 * p8);
-  l.fuse = take(b * 256 * p8);
-  l.mid = take(b * 256 * p8);
-  l.logits = take(b * NCLS * p8);
-  off = std::max(off, after_stem);                             // (they fit: 19.5 p4 + ... < 256 p4)
-  for (int i = 0; i < 3; ++i) l.tmp[i] = take(b * 64 * p4);
-  l.feat8 = take(b * 128 * p8);
-  l.feat16 = take(b * 256 * p16);
-  l.feat32 = take(b * 512 * p32);
-  l.pool32 = take(b * 512);
-  l.avg = take(b * 128);
-  l.parm32 = take(b * 128);
-  l.att32 = take(b * 128);
-  l.parm16 = take(b * 128);
-  l.att16 = take(b * 128);
-  l.pffm = take(b * 256);
-  l.hid = take(b * 64);
-  l.attffm = take(b * 256);
-  l.total = off;
+  Arena a;
+  l.stem = a.take(b * 64 * p2);
+  const size_t after_stem = a.off;
+  a.off = l.stem;
+  l.arm32 = a.take(b * 128 * p32);
+  l.arm16 = a.take(b * 128 * p16);
+  l.cp16 = a.take(b * 128 * p16);
+  l.cp8 = a.take(b * 128 * p8);
+  l.fuse = a.take(b * 256 * p8);
+  l.mid = a.take(b * 256 * p8);
+  l.logits = a.take(b * NCLS * p8);
+  a.off = std::max(a.off, after_stem);                             // (they fit: 19.5 p4 + ... < 256 p4)
+  for (int i = 0; i < 3; ++i) l.tmp[i] = a.take(b * 64 * p4);
+  l.feat8 = a.take(b * 128 * p8);
+  l.feat16 = a.take(b * 256 * p16);
+  l.feat32 = a.take(b * 512 * p32);
+  l.pool32 = a.take(b * 512);
+  l.avg = a.take(b * 128);
+  l.parm32 = a.take(b * 128);
+  l.att32 = a.take(b * 128);
+  l.parm16 = a.take(b * 128);
+  l.att16 = a.take(b * 128);
+  l.pffm = a.take(b * 256);
+  l.hid = a.take(b * 64);
+  l.attffm = a.take(b * 256);
+  l.total = a.off;
   return l;
-}
-
-bool shape_ok(int B, int H, int W) {
-  return B >= 1 && H >= 64 && W >= 64 && H % 32 == 0 && W % 32 == 0 && H <= 4096 && W <= 4096 &&
-         (size_t)B * 64 * (H / 2) * (W / 2) < ((size_t)1 << 31);
 }
 
 }  // namespace
@@ -189,8 +170,8 @@ using namespace instag;
 extern "C" {
 
 size_t instag_parsing_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-  if (!shape_ok(B, H, W)) {
-    set_error("parsing_workspace_bytes: B >= 1, H and W multiples of 32 in [64, 4096], B * 16 * H * W < 2^31");
+  if (!frames_ok(B, H, W)) {
+    set_error(std::string("parsing_workspace_bytes") + FRAMES_OK);
     return 0;
   }
   return layout(B, H, W).total * sizeof(float);
@@ -211,10 +192,10 @@ int instag_parsing_forward(const instag_parsing_weights* w, const uint8_t* frame
                            void* workspace, size_t workspace_bytes, instag_stream_t stream) {
   INSTAG_REQUIRE(w && frames && workspace, "parsing_forward: NULL tensor");
   INSTAG_REQUIRE(logits8 || labels || colours, "parsing_forward: no output asked for");
-  for (int l = 0; l < NLAYER; ++l)
-    INSTAG_REQUIRE(w->w[l] && w->scale[l] && w->shift[l], "parsing_forward: NULL weight of layer " + std::to_string(l));
-  INSTAG_REQUIRE(shape_ok(B, H, W),
-                 "parsing_forward: B >= 1, H and W multiples of 32 in [64, 4096], B * 16 * H * W < 2^31");
+  const ConvNet conv{w->w, w->scale, w->shift, B, (hipStream_t)stream};
+  const int null_layer = conv.null_layer(NLAYER);
+  INSTAG_REQUIRE(null_layer < 0, "parsing_forward: NULL weight of layer " + std::to_string(null_layer));
+  INSTAG_REQUIRE(frames_ok(B, H, W), std::string("parsing_forward") + FRAMES_OK);
   INSTAG_REQUIRE(!colours || (out_h >= 1 && out_w >= 1 && out_h <= 8192 && out_w <= 8192),
                  "parsing_forward: out_h and out_w in [1, 8192]");
   const Layout L = layout(B, H, W);
@@ -222,33 +203,19 @@ int instag_parsing_forward(const instag_parsing_weights* w, const uint8_t* frame
     set_error("parsing_forward: workspace too small");
     return INSTAG_E_SPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = conv.st;
   float* base = (float*)workspace;
   auto at = [&](size_t off) { return base + off; };
   const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8, h16 = H / 16, w16 = W / 16,
             h32 = H / 32, w32 = W / 32;
 
-  auto conv = [&](int layer, int ks, const float* in, int cin, int hi, int wi, int stride, int cout, float* out,
-                  const float* res, int relu, ConvArgs extra) -> int {
-    ConvArgs c = extra;
-    c.in = in; c.wt = w->w[layer]; c.scale = w->scale[layer]; c.shift = w->shift[layer]; c.res = res; c.out = out;
-    c.B = B; c.cin = cin; c.cout = cout; c.hi = hi; c.wi = wi; c.stride = stride; c.relu = relu;
-    if (!c.in2) c.c_split = cin;
-    c.ho = (hi + 2 * (ks / 2) - ks) / stride + 1;
-    c.wo = (wi + 2 * (ks / 2) - ks) / stride + 1;
-    return ks == 1 ? launch_conv<1>(c, st) : ks == 3 ? launch_conv<3>(c, st) : launch_conv_tile<7, 2>(c, st);
-  };
-  const ConvArgs plain{};
-#define PARSING_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
   // the stem and the max-pool
   {
     ConvArgs e{};
     e.frames = frames;
-    PARSING_TRY(conv(L_STEM, 7, nullptr, 3, H, W, 2, 64, at(L.stem), nullptr, 1, e));
-    const size_t n = (size_t)B * 64 * h4 * w4;
-    maxpool_kernel<<<(unsigned)div_up(n, (size_t)TB), TB, 0, st>>>(at(L.stem), at(L.tmp[0]), B * 64, h2, w2, h4, w4);
-    INSTAG_CHECK_LAUNCH();
+    INSTAG_TRY(conv(L_STEM, 7, nullptr, 3, H, W, 2, 64, at(L.stem), nullptr, 1, e));
+    INSTAG_TRY(conv.maxpool(at(L.stem), at(L.tmp[0]), 64, h2, w2));
   }
 
   // the eight residual blocks: relu(shortcut + bn2(conv2(relu(bn1(conv1 x)))))
@@ -268,19 +235,19 @@ int instag_parsing_forward(const instag_parsing_weights* w, const uint8_t* frame
       const int stride = down ? 2 : 1;
       const int ho = hx / stride, wo = wx / stride;
       float* t1 = pick(x, nullptr, nullptr);
-      PARSING_TRY(conv(layer, 3, x, ch, hx, wx, stride, cout, t1, nullptr, 1, plain));
+      INSTAG_TRY(conv(layer, 3, x, ch, hx, wx, stride, cout, t1, nullptr, 1));
       const float* res = x;
       float* out;
       if (down) {
         float* t2 = pick(x, t1, nullptr);
-        PARSING_TRY(conv(layer + 2, 1, x, ch, hx, wx, 2, cout, t2, nullptr, 0, plain));
+        INSTAG_TRY(conv(layer + 2, 1, x, ch, hx, wx, 2, cout, t2, nullptr, 0));
         res = t2;
         out = pick(t1, t2, nullptr);                           // x itself is not read again
       } else {
         out = pick(x, t1, nullptr);
       }
       if (blk == 1 && stage_out[stage]) out = stage_out[stage];
-      PARSING_TRY(conv(layer + 1, 3, t1, cout, ho, wo, 1, cout, out, res, 1, plain));
+      INSTAG_TRY(conv(layer + 1, 3, t1, cout, ho, wo, 1, cout, out, res, 1));
       layer += down ? 3 : 2;
       x = out; ch = cout; hx = ho; wx = wo;
     }
@@ -299,42 +266,41 @@ int instag_parsing_forward(const instag_parsing_weights* w, const uint8_t* frame
   };
 
   // context path
-  PARSING_TRY(pool(feat32, at(L.pool32), B * 512, h32 * w32));
-  PARSING_TRY(fc(L_AVG, at(L.pool32), at(L.avg), 512, 128, ACT_RELU));
-  PARSING_TRY(conv(L_ARM32, 3, feat32, 512, h32, w32, 1, 128, at(L.arm32), nullptr, 1, plain));
-  PARSING_TRY(pool(at(L.arm32), at(L.parm32), B * 128, h32 * w32));
-  PARSING_TRY(fc(L_ATT32, at(L.parm32), at(L.att32), 128, 128, ACT_SIGMOID));
+  INSTAG_TRY(pool(feat32, at(L.pool32), B * 512, h32 * w32));
+  INSTAG_TRY(fc(L_AVG, at(L.pool32), at(L.avg), 512, 128, ACT_RELU));
+  INSTAG_TRY(conv(L_ARM32, 3, feat32, 512, h32, w32, 1, 128, at(L.arm32), nullptr, 1));
+  INSTAG_TRY(pool(at(L.arm32), at(L.parm32), B * 128, h32 * w32));
+  INSTAG_TRY(fc(L_ATT32, at(L.parm32), at(L.att32), 128, 128, ACT_SIGMOID));
   {
     ConvArgs e{};
     e.up = 1; e.mul = at(L.att32); e.add_bc = at(L.avg);
-    PARSING_TRY(conv(L_HEAD32, 3, at(L.arm32), 128, h16, w16, 1, 128, at(L.cp16), nullptr, 1, e));
+    INSTAG_TRY(conv(L_HEAD32, 3, at(L.arm32), 128, h16, w16, 1, 128, at(L.cp16), nullptr, 1, e));
   }
-  PARSING_TRY(conv(L_ARM16, 3, feat16, 256, h16, w16, 1, 128, at(L.arm16), nullptr, 1, plain));
-  PARSING_TRY(pool(at(L.arm16), at(L.parm16), B * 128, h16 * w16));
-  PARSING_TRY(fc(L_ATT16, at(L.parm16), at(L.att16), 128, 128, ACT_SIGMOID));
+  INSTAG_TRY(conv(L_ARM16, 3, feat16, 256, h16, w16, 1, 128, at(L.arm16), nullptr, 1));
+  INSTAG_TRY(pool(at(L.arm16), at(L.parm16), B * 128, h16 * w16));
+  INSTAG_TRY(fc(L_ATT16, at(L.parm16), at(L.att16), 128, 128, ACT_SIGMOID));
   {
     ConvArgs e{};
     e.up = 1; e.mul = at(L.att16); e.add_sp = at(L.cp16);
-    PARSING_TRY(conv(L_HEAD16, 3, at(L.arm16), 128, h8, w8, 1, 128, at(L.cp8), nullptr, 1, e));
+    INSTAG_TRY(conv(L_HEAD16, 3, at(L.arm16), 128, h8, w8, 1, 128, at(L.cp8), nullptr, 1, e));
   }
 
   // feature fusion and the output head
   {
     ConvArgs e{};
     e.in2 = at(L.cp8); e.c_split = 128;
-    PARSING_TRY(conv(L_FFM, 1, feat8, 256, h8, w8, 1, 256, at(L.fuse), nullptr, 1, e));
+    INSTAG_TRY(conv(L_FFM, 1, feat8, 256, h8, w8, 1, 256, at(L.fuse), nullptr, 1, e));
   }
-  PARSING_TRY(pool(at(L.fuse), at(L.pffm), B * 256, h8 * w8));
-  PARSING_TRY(fc(L_FFM1, at(L.pffm), at(L.hid), 256, 64, ACT_RELU));
-  PARSING_TRY(fc(L_FFM2, at(L.hid), at(L.attffm), 64, 256, ACT_SIGMOID));
+  INSTAG_TRY(pool(at(L.fuse), at(L.pffm), B * 256, h8 * w8));
+  INSTAG_TRY(fc(L_FFM1, at(L.pffm), at(L.hid), 256, 64, ACT_RELU));
+  INSTAG_TRY(fc(L_FFM2, at(L.hid), at(L.attffm), 64, 256, ACT_SIGMOID));
   {
     ConvArgs e{};
     e.mul = at(L.attffm); e.self_add = 1;
-    PARSING_TRY(conv(L_OUT_MID, 3, at(L.fuse), 256, h8, w8, 1, 256, at(L.mid), nullptr, 1, e));
+    INSTAG_TRY(conv(L_OUT_MID, 3, at(L.fuse), 256, h8, w8, 1, 256, at(L.mid), nullptr, 1, e));
   }
   float* logits = logits8 ? logits8 : at(L.logits);
-  PARSING_TRY(conv(L_OUT, 1, at(L.mid), 256, h8, w8, 1, NCLS, logits, nullptr, 0, plain));
-#undef PARSING_TRY
+  INSTAG_TRY(conv(L_OUT, 1, at(L.mid), 256, h8, w8, 1, NCLS, logits, nullptr, 0));
 
   if (labels || colours) return launch_labels(logits, B, H, W, out_h, out_w, labels, colours, st);
   return INSTAG_OK;

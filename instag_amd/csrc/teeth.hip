@@ -3,7 +3,7 @@
 // FPNHead in eval mode, fp32, forward only, from uint8 frames to the labels and the teeth mask of teeth_mask/<i>.npy
 // (include/instag_hip.h, "Teeth segmentation").
 //
-// BatchNorm arrives folded into a per-channel (scale, shift) pair and a bias as (1, bias) (instag_amd/teeth.py:
+// BatchNorm arrives folded into a per-channel (scale, shift) pair and a bias as (1, bias) (instag_amd/convnet.py:
 // device_pack), so every one of the 71 convolutions is act(scale * conv(x) + shift [+ residual]).
 //   convolutions  conv_mfma.hpp, the kernel parsing.hip runs: implicit GEMM on the f32-input MFMA, D[cout][m] with
 //                 m = (frame, oy, ox) tiled jointly, K tiles of 32 added in order, the epilogue on the accumulators.
@@ -64,20 +64,7 @@ __global__ void __launch_bounds__(TB) teeth_label_kernel(const float* logits, in
   if (i >= (size_t)B * H * W) return;
   const int x = (int)(i % W), y = (int)((i / W) % H);
   const int b = (int)(i / ((size_t)W * H));
-  const float fy = fmaxf(((float)y + 0.5f) * ((float)h4 / (float)H) - 0.5f, 0.f);
-  const float fx = fmaxf(((float)x + 0.5f) * ((float)w4 / (float)W) - 0.5f, 0.f);
-  const int y0 = min((int)fy, h4 - 1), x0 = min((int)fx, w4 - 1);
-  const int y1 = min(y0 + 1, h4 - 1), x1 = min(x0 + 1, w4 - 1);
-  const float ly = fy - (float)y0, lx = fx - (float)x0;
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  const float* src = logits + (size_t)b * C * h4 * w4;
-  float best = 0.f;
-  int arg = 0;
-  for (int c = 0; c < C; ++c) {
-    const float* p = src + (size_t)c * h4 * w4;
-    const float v = hy * (hx * p[y0 * w4 + x0] + lx * p[y0 * w4 + x1]) + ly * (hx * p[y1 * w4 + x0] + lx * p[y1 * w4 + x1]);
-    if (c == 0 || v > best) { best = v; arg = c; }             // the first maximum
-  }
+  const int arg = bilinear_argmax<false>(logits + (size_t)b * C * h4 * w4, C, h4, w4, H, W, y, x);
   if (labels) labels[i] = (uint8_t)arg;
   if (mask) mask[i] = arg == TEETH ? 1 : 0;
 }
@@ -105,23 +92,17 @@ struct Layout {
 Layout layout(int B, int H, int W) {
   Layout l;
   const size_t bp4 = (size_t)B * (H / 4) * (W / 4);
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += align_up(n, 64); return o; };
-  l.stem_a = take(128 * bp4);
-  l.stem_b = take(128 * bp4);
-  l.stem_c = take(256 * bp4);
-  l.pool = take(64 * bp4);
-  l.big[0] = take(256 * bp4);
-  l.big[1] = take(256 * bp4);
-  for (int s = 0; s < 4; ++s) l.feat[s] = take((256 >> s) * bp4);
-  l.logits = take(MAX_CLS * bp4);
-  l.total = off;
+  Arena a;
+  l.stem_a = a.take(128 * bp4);
+  l.stem_b = a.take(128 * bp4);
+  l.stem_c = a.take(256 * bp4);
+  l.pool = a.take(64 * bp4);
+  l.big[0] = a.take(256 * bp4);
+  l.big[1] = a.take(256 * bp4);
+  for (int s = 0; s < 4; ++s) l.feat[s] = a.take((256 >> s) * bp4);
+  l.logits = a.take(MAX_CLS * bp4);
+  l.total = a.off;
   return l;
-}
-
-bool shape_ok(int B, int H, int W) {
-  return B >= 1 && H >= 64 && W >= 64 && H % 32 == 0 && W % 32 == 0 && H <= 4096 && W <= 4096 &&
-         (size_t)B * 16 * H * W < ((size_t)1 << 31);            // no map has 2^31 elements: 256 channels at stride 4
 }
 
 }  // namespace
@@ -132,8 +113,8 @@ using namespace instag;
 extern "C" {
 
 size_t instag_teeth_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-  if (!shape_ok(B, H, W)) {
-    set_error("teeth_workspace_bytes: B >= 1, H and W multiples of 32 in [64, 4096], B * 16 * H * W < 2^31");
+  if (!frames_ok(B, H, W)) {
+    set_error(std::string("teeth_workspace_bytes") + FRAMES_OK);
     return 0;
   }
   return layout(B, H, W).total * sizeof(float);
@@ -153,50 +134,38 @@ int instag_teeth_forward(const instag_teeth_weights* w, const uint8_t* frames, i
                          instag_stream_t stream) {
   INSTAG_REQUIRE(w && frames && workspace, "teeth_forward: NULL tensor");
   INSTAG_REQUIRE(logits4 || labels || mask, "teeth_forward: no output asked for");
-  for (int l = 0; l < NLAYER; ++l)
-    INSTAG_REQUIRE(w->w[l] && w->scale[l] && w->shift[l], "teeth_forward: NULL weight of layer " + std::to_string(l));
-  INSTAG_REQUIRE(shape_ok(B, H, W), "teeth_forward: B >= 1, H and W multiples of 32 in [64, 4096], B * 16 * H * W < 2^31");
+  const ConvNet conv{w->w, w->scale, w->shift, B, (hipStream_t)stream};
+  const int null_layer = conv.null_layer(NLAYER);
+  INSTAG_REQUIRE(null_layer < 0, "teeth_forward: NULL weight of layer " + std::to_string(null_layer));
+  INSTAG_REQUIRE(frames_ok(B, H, W), std::string("teeth_forward") + FRAMES_OK);
   INSTAG_REQUIRE(C >= MIN_CLS && C <= MAX_CLS, "teeth_forward: C in [8, 32]");
   const Layout L = layout(B, H, W);
   if (workspace_bytes < L.total * sizeof(float)) {
     set_error("teeth_forward: workspace too small");
     return INSTAG_E_SPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = conv.st;
   float* base = (float*)workspace;
   auto at = [&](size_t off) { return base + off; };
   const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4;
   const size_t bp4 = (size_t)B * h4 * w4;
 
-  auto conv = [&](int layer, int ks, const float* in, int cin, int hi, int wi, int stride, int cout, float* out,
-                  const float* res, int relu, ConvArgs extra) -> int {
-    ConvArgs c = extra;
-    c.in = in; c.wt = w->w[layer]; c.scale = w->scale[layer]; c.shift = w->shift[layer]; c.res = res; c.out = out;
-    c.B = B; c.cin = cin; c.c_split = cin; c.cout = cout; c.hi = hi; c.wi = wi; c.stride = stride; c.relu = relu;
-    c.ho = (hi + 2 * (ks / 2) - ks) / stride + 1;
-    c.wo = (wi + 2 * (ks / 2) - ks) / stride + 1;
-    return ks == 1 ? launch_conv<1>(c, st) : launch_conv<3>(c, st);
-  };
   auto up2 = [&](const float* in, const float* add, float* out, int ch, int h, int wd) -> int {
     const size_t n = (size_t)B * ch * h * wd * 4;
     upsample2_kernel<<<(unsigned)div_up(n, (size_t)TB), TB, 0, st>>>(in, add, out, B * ch, h, wd);
     INSTAG_CHECK_LAUNCH();
     return INSTAG_OK;
   };
-  const ConvArgs plain{};
-#define TEETH_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
   // the deep stem and the max-pool
   {
     ConvArgs e{};
     e.frames = frames;
     for (int c = 0; c < 3; ++c) { e.mean[c] = MEAN[c]; e.stdev[c] = STDEV[c]; }
-    TEETH_TRY(conv(L_STEM, 3, nullptr, 3, H, W, 2, 32, at(L.stem_a), nullptr, 1, e));
-    TEETH_TRY(conv(L_STEM + 1, 3, at(L.stem_a), 32, h2, w2, 1, 32, at(L.stem_b), nullptr, 1, plain));
-    TEETH_TRY(conv(L_STEM + 2, 3, at(L.stem_b), 32, h2, w2, 1, 64, at(L.stem_c), nullptr, 1, plain));
-    const size_t n = 64 * bp4;
-    maxpool_kernel<<<(unsigned)div_up(n, (size_t)TB), TB, 0, st>>>(at(L.stem_c), at(L.pool), B * 64, h2, w2, h4, w4);
-    INSTAG_CHECK_LAUNCH();
+    INSTAG_TRY(conv(L_STEM, 3, nullptr, 3, H, W, 2, 32, at(L.stem_a), nullptr, 1, e));
+    INSTAG_TRY(conv(L_STEM + 1, 3, at(L.stem_a), 32, h2, w2, 1, 32, at(L.stem_b), nullptr, 1));
+    INSTAG_TRY(conv(L_STEM + 2, 3, at(L.stem_b), 32, h2, w2, 1, 64, at(L.stem_c), nullptr, 1));
+    INSTAG_TRY(conv.maxpool(at(L.stem_c), at(L.pool), 64, h2, w2));
   }
 
   // the sixteen bottlenecks: relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + identity), the stride on conv2
@@ -214,16 +183,16 @@ int instag_teeth_forward(const instag_teeth_weights* w, const uint8_t* frames, i
     for (int blk = 0; blk < BLOCKS[stage]; ++blk) {
       const int stride = blk == 0 && stage > 0 ? 2 : 1;
       const int ho = hx / stride, wo = wx / stride;
-      TEETH_TRY(conv(layer, 1, x, ch, hx, wx, 1, planes, mid1, nullptr, 1, plain));
-      TEETH_TRY(conv(layer + 1, 3, mid1, planes, hx, wx, stride, planes, mid2, nullptr, 1, plain));
+      INSTAG_TRY(conv(layer, 1, x, ch, hx, wx, 1, planes, mid1, nullptr, 1));
+      INSTAG_TRY(conv(layer + 1, 3, mid1, planes, hx, wx, stride, planes, mid2, nullptr, 1));
       const float* res = x;
       if (blk == 0) {
         float* down = pick(x, nullptr);
-        TEETH_TRY(conv(layer + 3, 1, x, ch, hx, wx, stride, cout, down, nullptr, 0, plain));
+        INSTAG_TRY(conv(layer + 3, 1, x, ch, hx, wx, stride, cout, down, nullptr, 0));
         res = down;
       }
       float* out = blk == BLOCKS[stage] - 1 ? at(L.feat[stage]) : pick(x, res);
-      TEETH_TRY(conv(layer + 2, 1, mid2, planes, ho, wo, 1, cout, out, res, 1, plain));
+      INSTAG_TRY(conv(layer + 2, 1, mid2, planes, ho, wo, 1, cout, out, res, 1));
       layer += blk == 0 ? 4 : 3;
       x = out; ch = cout; hx = ho; wx = wo;
     }
@@ -235,33 +204,32 @@ int instag_teeth_forward(const instag_teeth_weights* w, const uint8_t* frames, i
   for (int i = 3; i >= 0; --i) {
     ConvArgs e{};
     e.res_up = i < 3;
-    TEETH_TRY(conv(L_LATERAL + i, 1, at(L.feat[i]), 256 << i, h4 >> i, w4 >> i, 1, 256, lat[i], i < 3 ? lat[i + 1] : nullptr,
+    INSTAG_TRY(conv(L_LATERAL + i, 1, at(L.feat[i]), 256 << i, h4 >> i, w4 >> i, 1, 256, lat[i], i < 3 ? lat[i + 1] : nullptr,
                    0, e));
   }
   for (int i = 0; i < 4; ++i)
-    TEETH_TRY(conv(L_FPN + i, 3, lat[i], 256, h4 >> i, w4 >> i, 1, 256, fpn[i], nullptr, 0, plain));
+    INSTAG_TRY(conv(L_FPN + i, 3, lat[i], 256, h4 >> i, w4 >> i, 1, 256, fpn[i], nullptr, 0));
 
   // the head: level i runs max(1, i) times (conv + BN + ReLU [+ x2 upsample]); the levels are summed in order at stride 4
   float* sum = at(L.stem_b);
   float *t0 = at(L.pool), *t1 = at(L.pool) + 32 * bp4;
-  TEETH_TRY(conv(L_HEAD, 3, fpn[0], 256, h4, w4, 1, 128, sum, nullptr, 1, plain));
+  INSTAG_TRY(conv(L_HEAD, 3, fpn[0], 256, h4, w4, 1, 128, sum, nullptr, 1));
   int hl = L_HEAD + 1;
   for (int i = 1; i < 4; ++i) {
     const float* in = fpn[i];
     int cin = 256, h = h4 >> i, wd = w4 >> i;
     for (int k = 0; k < i; ++k) {
-      TEETH_TRY(conv(hl++, 3, in, cin, h, wd, 1, 128, t0, nullptr, 1, plain));
+      INSTAG_TRY(conv(hl++, 3, in, cin, h, wd, 1, 128, t0, nullptr, 1));
       if (k == i - 1) {
-        TEETH_TRY(up2(t0, sum, sum, 128, h, wd));
+        INSTAG_TRY(up2(t0, sum, sum, 128, h, wd));
       } else {
-        TEETH_TRY(up2(t0, nullptr, t1, 128, h, wd));
+        INSTAG_TRY(up2(t0, nullptr, t1, 128, h, wd));
       }
       in = t1; cin = 128; h *= 2; wd *= 2;
     }
   }
   float* logits = logits4 ? logits4 : at(L.logits);
-  TEETH_TRY(conv(L_SEG, 1, sum, 128, h4, w4, 1, C, logits, nullptr, 0, plain));
-#undef TEETH_TRY
+  INSTAG_TRY(conv(L_SEG, 1, sum, 128, h4, w4, 1, C, logits, nullptr, 0));
 
   if (labels || mask) return launch_labels(logits, B, H, W, C, labels, mask, st);
   return INSTAG_OK;

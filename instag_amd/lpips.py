@@ -199,9 +199,7 @@ class _Plan:
         from . import _lib
         self.L = _lib.lib()
         self.args = (int(H), int(W), int(p_min), int(p_max), int(n_stack))
-        nbytes = self.L.instag_lpips_workspace_bytes(*self.args)
-        if nbytes == 0:
-            raise ValueError(self.L.instag_last_error().decode("utf-8", "replace"))
+        nbytes = _lib.workspace_bytes(self.L.instag_lpips_workspace_bytes(*self.args))
         self.device = torch.device(device)
         self.n_max = self.L.instag_lpips_max_patches(*self.args)
         self.struct, self._keep = w.device_pack(self.device)

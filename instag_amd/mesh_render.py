@@ -37,6 +37,7 @@ import torch
 import torch.nn.functional as Fn
 
 from . import _lib
+from ._lib import check_arg
 from .track import Face3DMM, euler2rot_torch, landmarks_torch, project_torch
 
 SIGMA = 1e-4
@@ -269,15 +270,6 @@ def render_torch(rott_geo, texture, light, tris, vert_tris, focal, H, W, sigma=S
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------
-def _raise(code, what):
-    if code == 0:
-        return
-    msg = _lib.lib().instag_last_error().decode("utf-8", "replace")
-    if code == 1:                                                        # INSTAG_E_ARG
-        raise ValueError(f"{what}: {msg}")
-    raise RuntimeError(f"{what}: {msg}")
-
-
 def _settings(r):
     a = _lib.MeshSettings()
     a.H, a.W, a.K = r.H, r.W, K_FACES
@@ -302,9 +294,9 @@ class _VertexStage(torch.autograd.Function):
             raise ValueError(f"mesh_render: rott_geo [B,{r.V},3], texture [B,{r.V},3], light [B,27]")
         colours = torch.empty_like(texture)
         with torch.cuda.device(r.device):
-            _raise(_lib.lib().instag_mesh_vertex_forward(_lib.ptr(rott_geo), _lib.ptr(texture), _lib.ptr(light), _lib.ptr(r.tris),
-                                                         _lib.ptr(r.vert_tris), B, V, r.T, r.M, _lib.ptr(colours),
-                                                         _lib.current_stream()), "mesh_vertex_forward")
+            check_arg(_lib.lib().instag_mesh_vertex_forward(_lib.ptr(rott_geo), _lib.ptr(texture), _lib.ptr(light), _lib.ptr(r.tris),
+                                                           _lib.ptr(r.vert_tris), B, V, r.T, r.M, _lib.ptr(colours),
+                                                           _lib.current_stream()), "mesh_vertex_forward")
         ctx.r = r
         ctx.save_for_backward(rott_geo, texture, light)
         return colours
@@ -319,10 +311,10 @@ class _VertexStage(torch.autograd.Function):
         lib = _lib.lib()
         ws = torch.empty(int(lib.instag_mesh_vertex_backward_workspace_bytes(B, V)), dtype=torch.uint8, device=r.device)
         with torch.cuda.device(r.device):
-            _raise(lib.instag_mesh_vertex_backward(_lib.ptr(rott_geo), _lib.ptr(texture), _lib.ptr(light), _lib.ptr(r.tris),
-                                                   _lib.ptr(r.vert_tris), _lib.ptr(d_colours), B, V, r.T, r.M, _lib.ptr(d_geo),
-                                                   _lib.ptr(d_tex), _lib.ptr(d_light), _lib.ptr(ws), ws.numel(),
-                                                   _lib.current_stream()), "mesh_vertex_backward")
+            check_arg(lib.instag_mesh_vertex_backward(_lib.ptr(rott_geo), _lib.ptr(texture), _lib.ptr(light), _lib.ptr(r.tris),
+                                                     _lib.ptr(r.vert_tris), _lib.ptr(d_colours), B, V, r.T, r.M, _lib.ptr(d_geo),
+                                                     _lib.ptr(d_tex), _lib.ptr(d_light), _lib.ptr(ws), ws.numel(),
+                                                     _lib.current_stream()), "mesh_vertex_backward")
         return None, d_geo, d_tex, d_light
 
 
@@ -339,9 +331,9 @@ class _Blend(torch.autograd.Function):
         out = torch.empty(B, r.H, r.W, 4, dtype=torch.float32, device=r.device)
         s = _settings(r)
         with torch.cuda.device(r.device):
-            _raise(_lib.lib().instag_mesh_blend_forward(C.byref(s), _lib.ptr(screen), _lib.ptr(colours), _lib.ptr(r.tris),
-                                                        _lib.ptr(ids), B, r.V, r.T, _lib.ptr(out), _lib.current_stream()),
-                   "mesh_blend_forward")
+            check_arg(_lib.lib().instag_mesh_blend_forward(C.byref(s), _lib.ptr(screen), _lib.ptr(colours), _lib.ptr(r.tris),
+                                                          _lib.ptr(ids), B, r.V, r.T, _lib.ptr(out), _lib.current_stream()),
+                     "mesh_blend_forward")
         ctx.r = r
         ctx.save_for_backward(screen, colours, ids)
         return out
@@ -354,10 +346,10 @@ class _Blend(torch.autograd.Function):
         d_screen, d_colours = torch.empty_like(screen), torch.empty_like(colours)      # (the entry point clears them)
         s = _settings(r)
         with torch.cuda.device(r.device):
-            _raise(_lib.lib().instag_mesh_blend_backward(C.byref(s), _lib.ptr(screen), _lib.ptr(colours), _lib.ptr(r.tris),
-                                                         _lib.ptr(ids), _lib.ptr(d_out), screen.shape[0], r.V, r.T,
-                                                         _lib.ptr(d_screen), _lib.ptr(d_colours), _lib.current_stream()),
-                   "mesh_blend_backward")
+            check_arg(_lib.lib().instag_mesh_blend_backward(C.byref(s), _lib.ptr(screen), _lib.ptr(colours), _lib.ptr(r.tris),
+                                                           _lib.ptr(ids), _lib.ptr(d_out), screen.shape[0], r.V, r.T,
+                                                           _lib.ptr(d_screen), _lib.ptr(d_colours), _lib.current_stream()),
+                     "mesh_blend_backward")
         return None, d_screen, d_colours, None
 
 
@@ -401,8 +393,8 @@ class MeshRenderer:
         ids = torch.empty(B, self.H, self.W, K_FACES, dtype=torch.int32, device=self.device)
         s = _settings(self)
         with torch.cuda.device(self.device):
-            _raise(_lib.lib().instag_mesh_select(C.byref(s), _lib.ptr(screen), _lib.ptr(self.tris), B, self.V, self.T,
-                                                 _lib.ptr(keys), _lib.ptr(ids), _lib.current_stream()), "mesh_select")
+            check_arg(_lib.lib().instag_mesh_select(C.byref(s), _lib.ptr(screen), _lib.ptr(self.tris), B, self.V, self.T,
+                                                   _lib.ptr(keys), _lib.ptr(ids), _lib.current_stream()), "mesh_select")
         return ids
 
     def blend(self, screen, colours, ids):

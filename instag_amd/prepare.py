@@ -225,15 +225,6 @@ def frames_torch(ori, parsing, bc):
 
 
 # ---- the kernels --------------------------------------------------------------------------------------------------------
-def _raise(code, what):
-    if code == 0:
-        return
-    msg = _lib.lib().instag_last_error().decode("utf-8", "replace")
-    if code == 1:                                                        # INSTAG_E_ARG
-        raise ValueError(f"{what}: {msg}")
-    raise RuntimeError(f"{what}: {msg}")
-
-
 def _dev_u8(x, device):
     t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
     return t.to(device=device, dtype=torch.uint8).contiguous()
@@ -265,7 +256,7 @@ def background(ori, parsing, device=None):
     with torch.cuda.device(device):
         rc = lib.instag_prep_background(_lib.ptr(ori), _lib.ptr(parsing), S, H, W, _lib.ptr(bc), _lib.ptr(max_d2),
                                         _lib.ptr(arg), _lib.ptr(ws), nbytes, _lib.current_stream())
-    _raise(rc, "background")
+    _lib.check_arg(rc, "background")
     return bc, max_d2, arg
 
 
@@ -312,7 +303,7 @@ def frames_into(ori, parsing, bc, gt, torso, batch: int = 256):
             rc = lib.instag_prep_frames(_lib.ptr(o), _lib.ptr(p), _lib.ptr(bc), _lib.ptr(table), e - s, H, W,
                                         _lib.ptr(gt[s:e]), _lib.ptr(torso[s:e]), _lib.ptr(cols),
                                         _lib.current_stream())
-            _raise(rc, "frames")
+            _lib.check_arg(rc, "frames")
 
 
 # ---- a directory --------------------------------------------------------------------------------------------------------

@@ -31,15 +31,14 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .parsing import first_argmax
+from . import convnet
+from .convnet import BN_EPS, first_argmax  # noqa: F401
 
-BN_EPS = 1e-5
 SIZE = 512                                           # the size InsTaG's frames have
 MEAN = (143.55267075, 132.96705975, 126.94924335)    # fpn-fp.py: img_norm_cfg, RGB, on the 0..255 scale
 STD = (60.2625333, 60.32740275, 59.30988645)
 TEETH = 7                                            # create_teeth_mask.py:30
 MIN_CLASSES, MAX_CLASSES = 8, 32
-MIN_SIDE, SIDE_MULTIPLE = 64, 32
 STAGE_BLOCKS = (3, 4, 6, 3)
 WORKSPACE_BUDGET = 1 << 30                           # bytes the default max_batch may ask for at 512 x 512
 SEG = "decode_head.conv_seg"
@@ -75,7 +74,6 @@ def _layers():
 # (convolution, its BatchNorm or None, has a bias, cin, cout, kernel, stride) in the order of struct instag_teeth_weights
 LAYERS = _layers()
 INDEX = {name: i for i, (name, *_) in enumerate(LAYERS)}
-_BN = (("gamma", "weight"), ("beta", "bias"), ("mean", "running_mean"), ("var", "running_var"))
 
 
 def macs_per_frame(H: int = SIZE, W: int = SIZE, classes: int = MIN_CLASSES) -> int:
@@ -102,156 +100,47 @@ def macs_per_frame(H: int = SIZE, W: int = SIZE, classes: int = MIN_CLASSES) -> 
     return total
 
 
-def _fields(bn, bias):
-    return ("weight",) + (("bias",) if bias else ()) + (tuple(f for f, _ in _BN) if bn else ())
-
-
 # ---- weights ----------------------------------------------------------------------------------------------------------
-class FPNWeights:
+class FPNWeights(convnet.ConvWeights):
     """The frozen parameters of the fpn-fp segmentor: per layer of ``LAYERS`` the convolution's weight, its bias where
     it has one (the neck and ``conv_seg``: a ConvModule has a bias exactly when it has no norm) and, where it has one,
-    BatchNorm's gamma, beta, running mean and running variance.  ``classes`` is the number of rows of ``conv_seg``.
-    Kept in fp32 on the CPU; the device copy (convolutions in the kernels' layout, BatchNorm folded) is made once per
-    device (``device_pack``)."""
+    BatchNorm's gamma, beta, running mean and running variance (convnet.ConvWeights; ``from_state_dict`` takes the keys
+    of fpn-fp-512.pth's state dict or the mmcv checkpoint itself).  ``classes`` is the number of rows of ``conv_seg``.
+    On the device the first stem convolution's K = 27 is padded with zero rows to 32."""
 
-    def __init__(self, layers):
-        if len(layers) != len(LAYERS):
-            raise ValueError(f"FPN weights: expected {len(LAYERS)} layers, got {len(layers)}")
+    TABLE, LABEL, STRUCT, STEM_K = LAYERS, "FPN weights", "TeethWeights", 32
+
+    def _prepare(self, layers):
         seg = layers[INDEX[SEG]]["weight"]
         if seg.dim() != 4 or not MIN_CLASSES <= int(seg.shape[0]) <= MAX_CLASSES:
             raise ValueError(f"FPN weights: {SEG}.weight has shape {tuple(seg.shape)}, expected (C, 128, 1, 1) with "
                              f"{MIN_CLASSES} <= C <= {MAX_CLASSES}")
         self.classes = int(seg.shape[0])
-        self.layers = []
-        for lay, (name, bn, bias, cin, cout, k, _) in zip(layers, LAYERS):
-            cout = self.classes if cout is None else cout
-            fields = _fields(bn, bias)
-            lay = {f: lay[f].detach().float().contiguous().cpu() for f in fields}
-            for f in fields:
-                want = (cout, cin, k, k) if f == "weight" else (cout,)
-                if tuple(lay[f].shape) != want:
-                    raise ValueError(f"FPN weights: {name} {f} has shape {tuple(lay[f].shape)}, expected {want}")
-            self.layers.append(lay)
-        self._packs = {}
-
-    @classmethod
-    def from_state_dict(cls, sd) -> "FPNWeights":
-        """``sd``: the keys of fpn-fp-512.pth's state dict (the reference modules'), or the mmcv checkpoint
-        ``{"meta": ..., "state_dict": ...}`` itself.  ``num_batches_tracked`` is accepted and not read; a missing key
-        raises a ValueError naming it."""
-        if "state_dict" in sd and not torch.is_tensor(sd["state_dict"]):
-            sd = sd["state_dict"]
-
-        def get(key):
-            if key not in sd:
-                raise ValueError(f"FPN weights: the state dict misses {key!r}")
-            return sd[key]
-
-        layers = []
-        for name, bn, bias, *_ in LAYERS:
-            lay = {"weight": get(f"{name}.weight")}
-            if bias:
-                lay["bias"] = get(f"{name}.bias")
-            if bn:
-                lay.update({f: get(f"{bn}.{key}") for f, key in _BN})
-            layers.append(lay)
-        return cls(layers)
-
-    @classmethod
-    def load(cls, path) -> "FPNWeights":
-        return cls.from_state_dict(torch.load(path, map_location="cpu"))
 
     @classmethod
     def random(cls, seed: int = 0, classes: int = MIN_CLASSES) -> "FPNWeights":
-        """Seeded stand-ins with the scale of trained ones (tests, benches): He-scaled convolutions and non-trivial
-        BatchNorm statistics -- gamma and the variance in [0.5, 1.5], beta and the running mean of about 0.2 -- so that
-        the fold is exercised and about half of every stage's units are active.  ``conv3`` of every bottleneck is
-        scaled by a further 1/2 so that the trunk's magnitude stays of order one through the sixteen blocks; the neck's
-        convolutions, which no norm follows, by 0.7, their biases 0.1 randn; every class row of ``conv_seg`` sums to
-        zero over its inputs -- they are all positive, and an uncentred row turns their common mean into a per-class
-        offset that lets two or three classes win everywhere."""
+        """Seeded stand-ins with the scale of trained ones (tests, benches; convnet.draw_layer), so that the fold is
+        exercised and about half of every stage's units are active.  ``conv3`` of every bottleneck is scaled by a
+        further 1/2 so that the trunk's magnitude stays of order one through the sixteen blocks; the neck's
+        convolutions, which no norm follows, by 0.7; every class row of ``conv_seg`` sums to zero over its inputs --
+        they are all positive, and an uncentred row turns their common mean into a per-class offset that lets two or
+        three classes win everywhere."""
         g = torch.Generator().manual_seed(seed)
         layers = {}
         lat, fpn = INDEX["neck.lateral_convs.0.conv"], INDEX["neck.fpn_convs.0.conv"]
         # drawn in the order the modules run: each level's lateral convolution, then its output convolution
         order = list(range(lat)) + [j + i for i in range(4) for j in (lat, fpn)] + list(range(fpn + 4, len(LAYERS)))
         for l in order:
-            name, bn, bias, cin, cout, k, _ = LAYERS[l]
-            cout = classes if cout is None else cout
+            name = LAYERS[l][0]
             gain = 0.5 if name.endswith(".conv3") else 0.7 if name.startswith("neck.") else 1.0
-            lay = dict(weight=torch.randn(cout, cin, k, k, generator=g) * (gain * (2.0 / (cin * k * k)) ** 0.5))
-            if name == SEG:
-                lay["weight"] -= lay["weight"].mean(dim=1, keepdim=True)
-            if bn:
-                lay.update(gamma=torch.rand(cout, generator=g) + 0.5, beta=torch.randn(cout, generator=g) * 0.2,
-                           mean=torch.randn(cout, generator=g) * 0.2, var=torch.rand(cout, generator=g) + 0.5)
-            if bias:
-                lay["bias"] = torch.randn(cout, generator=g) * 0.1
-            layers[l] = lay
+            layers[l] = convnet.draw_layer(g, LAYERS[l], gain=gain, centre=name == SEG, classes=classes)
         return cls([layers[l] for l in range(len(LAYERS))])
-
-    def state_dict(self):
-        """The keys of the checkpoint's state dict (the reference modules'), ``num_batches_tracked`` included."""
-        out = {}
-        for lay, (name, bn, bias, *_) in zip(self.layers, LAYERS):
-            out[f"{name}.weight"] = lay["weight"].clone()
-            if bias:
-                out[f"{name}.bias"] = lay["bias"].clone()
-            if bn:
-                out.update({f"{bn}.{key}": lay[f].clone() for f, key in _BN})
-                out[f"{bn}.num_batches_tracked"] = torch.zeros((), dtype=torch.int64)
-        return out
-
-    def to(self, device=None, dtype=None):
-        """name -> dict of tensors of ``device`` / ``dtype`` for the torch statement."""
-        return {name: {f: t.to(device=device, dtype=dtype) for f, t in lay.items()}
-                for lay, (name, *_) in zip(self.layers, LAYERS)}
-
-    def folded(self, dtype=torch.float64):
-        """Per layer (convolution weight, scale, shift) with BatchNorm (eval) folded in fp64: scale = gamma /
-        sqrt(var + eps), shift = beta - mean * scale; (1, bias) for a layer without BatchNorm."""
-        out = []
-        for lay in self.layers:
-            d = {f: t.double() for f, t in lay.items()}
-            if "gamma" in d:
-                scale = d["gamma"] / torch.sqrt(d["var"] + BN_EPS)
-                shift = d["beta"] - d["mean"] * scale
-            else:
-                scale, shift = torch.ones(d["weight"].shape[0], dtype=torch.float64), d["bias"]
-            out.append((d["weight"].to(dtype), scale.to(dtype), shift.to(dtype)))
-        return out
-
-    def device_pack(self, device):
-        """struct instag_teeth_weights for ``device`` (and the tensors it points into): every convolution as
-        [K = (cin, ky, kx)][cout], the first stem convolution's K = 27 padded with zero rows to 32."""
-        from . import _lib
-        device = torch.device(device)
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        pack = self._packs.get(key)
-        if pack is not None:
-            return pack
-        keep, s = [], _lib.TeethWeights()
-        for l, (w, scale, shift) in enumerate(self.folded(torch.float32)):
-            wk = w.reshape(w.shape[0], -1).t()
-            if l == 0:
-                wk = torch.cat([wk, torch.zeros(32 - wk.shape[0], wk.shape[1])], dim=0)
-            ts = [t.contiguous().to(device) for t in (wk, scale, shift)]
-            keep += ts
-            s.w[l], s.scale[l], s.shift[l] = [t.data_ptr() for t in ts]
-        pack = self._packs[key] = (s, keep)
-        return pack
 
 
 # ---- plain-torch statement -------------------------------------------------------------------------------------------
 def normalise(frames_u8, dtype=torch.float32):
     """u8 [B,H,W,3] -> [B,3,H,W] of ``dtype``: mmcv's ``Normalize``, (u8 - MEAN) / STD per channel, in ``dtype``."""
-    x = torch.as_tensor(frames_u8)
-    if x.dim() != 4 or x.shape[-1] != 3 or x.dtype != torch.uint8:
-        raise ValueError(f"teeth: frames uint8 [B,H,W,3], got {x.dtype} {tuple(x.shape)}")
-    x = x.permute(0, 3, 1, 2).to(dtype)
-    mean = torch.tensor(MEAN, dtype=dtype, device=x.device).view(1, 3, 1, 1)
-    std = torch.tensor(STD, dtype=dtype, device=x.device).view(1, 3, 1, 1)
-    return (x - mean) / std
+    return convnet.normalise("teeth", frames_u8, MEAN, STD, False, dtype)
 
 
 def fpn_torch(weights: FPNWeights, x, taps=None):
@@ -315,110 +204,51 @@ def labels_torch(logits4, H: int, W: int):
     return first_argmax(upsample_torch(logits4, H, W))
 
 
-def _check_frames(frames_u8):
-    x = torch.as_tensor(frames_u8)
-    if x.dim() != 4 or x.shape[-1] != 3 or x.dtype != torch.uint8:
-        raise ValueError(f"teeth: frames uint8 [B,H,W,3], got {x.dtype} {tuple(x.shape)}")
-    H, W = int(x.shape[1]), int(x.shape[2])
-    if H < MIN_SIDE or W < MIN_SIDE or H % SIDE_MULTIPLE or W % SIDE_MULTIPLE:
-        raise ValueError(f"teeth: H and W multiples of {SIDE_MULTIPLE} and at least {MIN_SIDE}, got {H} x {W}")
-    return x, H, W
-
-
 @torch.no_grad()
 def teeth_torch(weights: FPNWeights, frames_u8, dtype=torch.float32):
     """The chain from u8 frames [B,H,W,3] to the teeth mask u8 [B,H,W] (1 = teeth) in plain torch, on the frames'
     device."""
-    x, H, W = _check_frames(frames_u8)
+    x, H, W = convnet.check_frames("teeth", frames_u8)
     labels = labels_torch(fpn_torch(weights, normalise(x, dtype)), H, W)
     return (labels == TEETH).to(torch.uint8)
 
 
 # ---- HIP operator -----------------------------------------------------------------------------------------------------
-class TeethSegmenter:
+class TeethSegmenter(convnet.FrameOperator):
     """``mask(frames u8 [B,H,W,3]) -> u8 [B,H,W]`` (1 = teeth), ``labels -> u8 [B,H,W]`` and ``logits ->
-    [B,C,H/4,W/4]`` on ``device``, on torch's current stream; inference only.  On the GPU the frames go through
-    csrc/teeth.hip in chunks of at most ``max_batch`` with one workspace that is grown when a call needs more and kept
-    (the workspace is the operator's: use one operator per stream); on the CPU all three are the torch statement.
+    [B,C,H/4,W/4]`` on ``device`` through csrc/teeth.hip, in chunks of at most ``max_batch`` (convnet.FrameOperator).
     ``max_batch=None``: the largest batch, at most 8, whose workspace at 512 x 512 (100 MiB per frame: the stride-4 maps
     of 256 channels are 16 MiB each) stays within 1 GiB."""
 
+    NAME = "teeth"
+    net_torch, normalise_torch, labels_torch = staticmethod(fpn_torch), staticmethod(normalise), staticmethod(labels_torch)
+
     def __init__(self, weights: FPNWeights, device="cuda", max_batch=None):
-        if max_batch is not None and max_batch < 1:
-            raise ValueError("TeethSegmenter: max_batch >= 1")
-        self.weights = weights
-        self.device = torch.device(device)
-        self._ws = None
-        if self.device.type == "cuda":
-            from . import _lib
-            self._L = _lib.lib()
-            self._struct, self._keep = weights.device_pack(self.device)
-            if max_batch is None:
-                per_frame = int(self._L.instag_teeth_workspace_bytes(1, SIZE, SIZE))
-                max_batch = max(1, min(8, WORKSPACE_BUDGET // per_frame))
+        super().__init__(weights, device, max_batch)
+        if max_batch is None and self.device.type == "cuda":
+            per_frame = int(self._L.instag_teeth_workspace_bytes(1, SIZE, SIZE))
+            max_batch = max(1, min(8, WORKSPACE_BUDGET // per_frame))
         self.max_batch = int(8 if max_batch is None else max_batch)
 
-    def _workspace(self, batch, H, W):
-        nbytes = int(self._L.instag_teeth_workspace_bytes(batch, H, W))
-        if nbytes == 0:
-            raise ValueError(self._L.instag_last_error().decode("utf-8", "replace"))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws, int(self._ws.numel())
+    def _workspace_bytes(self, batch, H, W):
+        return self._L.instag_teeth_workspace_bytes(batch, H, W)
 
     def _run(self, frames_u8, want):
         from . import _lib
-        x, H, W = _check_frames(frames_u8)
+        x, H, W = convnet.check_frames(self.NAME, frames_u8)
         x = x.to(self.device).contiguous()
         B, Cn = int(x.shape[0]), self.weights.classes
-        dev = self.device
-        logits = torch.empty(B, Cn, H // 4, W // 4, dtype=torch.float32, device=dev) if "logits" in want else None
-        labels = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if "labels" in want else None
-        mask = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if "mask" in want else None
-        if B == 0:
-            return logits, labels, mask
-        ws, nbytes = self._workspace(min(B, self.max_batch), H, W)
-        with torch.cuda.device(dev):
-            for i in range(0, B, self.max_batch):
-                m = min(self.max_batch, B - i)
-                rc = self._L.instag_teeth_forward(
-                    C.byref(self._struct), _lib.ptr(x[i:i + m]), m, H, W, Cn,
-                    _lib.ptr(None if logits is None else logits[i:i + m]),
-                    _lib.ptr(None if labels is None else labels[i:i + m]),
-                    _lib.ptr(None if mask is None else mask[i:i + m]), _lib.ptr(ws), nbytes, _lib.current_stream())
-                _raise(rc, "teeth_forward")
-        return logits, labels, mask
-
-    @torch.no_grad()
-    def logits(self, frames_u8):
-        if self.device.type != "cuda":
-            x, _, _ = _check_frames(frames_u8)
-            return fpn_torch(self.weights, normalise(x.to(self.device)))
-        return self._run(frames_u8, ("logits",))[0]
-
-    @torch.no_grad()
-    def labels(self, frames_u8):
-        if self.device.type != "cuda":
-            x, H, W = _check_frames(frames_u8)
-            return labels_torch(fpn_torch(self.weights, normalise(x.to(self.device))), H, W)
-        return self._run(frames_u8, ("labels",))[1]
+        outs = self._empty(want, logits=(B, Cn, H // 4, W // 4), labels=(B, H, W), mask=(B, H, W))
+        self._chunks(x, H, W, lambda c, m, ws, nbytes: self._L.instag_teeth_forward(
+            C.byref(self._struct), _lib.ptr(x[c]), m, H, W, Cn, *(_lib.ptr(None if t is None else t[c]) for t in outs),
+            ws, nbytes, _lib.current_stream()), "teeth_forward")
+        return outs
 
     @torch.no_grad()
     def mask(self, frames_u8):
         if self.device.type != "cuda":
             return teeth_torch(self.weights, torch.as_tensor(frames_u8).to(self.device))
         return self._run(frames_u8, ("mask",))[2]
-
-
-def _raise(code, what):
-    if code == 0:
-        return
-    from . import _lib
-    msg = _lib.lib().instag_last_error().decode("utf-8", "replace")
-    if code == 1:                                                        # INSTAG_E_ARG
-        raise ValueError(f"{what}: {msg}")
-    raise RuntimeError(f"{what}: {msg}")
 
 
 def teeth_labels(logits4, H: int, W: int, want_mask: bool = False):
@@ -436,7 +266,7 @@ def teeth_labels(logits4, H: int, W: int, want_mask: bool = False):
     with torch.cuda.device(logits4.device):
         rc = _lib.lib().instag_teeth_labels(_lib.ptr(logits4), B, H, W, Cn, _lib.ptr(labels), _lib.ptr(mask),
                                             _lib.current_stream())
-    _raise(rc, "teeth_labels")
+    _lib.check_arg(rc, "teeth_labels")
     return (labels, mask) if want_mask else labels
 
 
@@ -445,27 +275,14 @@ def teeth_identity(path, weights: FPNWeights, device="cuda", write: bool = True,
     """ori_imgs/<i>.jpg of ``path`` (ascending numeric order) -> teeth masks u8 [N,H,W] (1 = teeth) on ``device``, what
     ``FrameStore.append(teeth=...)`` takes, H x W the frames' own size (create_teeth_mask.py does not resize).
     ``write``: also teeth_mask/<i>.npy as ``np.bool_ [H,W]``, the file ``dataset.decode_images`` reads."""
-    from PIL import Image
-    from .prepare import list_frames
-    ids = list_frames(path)
-    device = torch.device(device)
-    seg = TeethSegmenter(weights, device, max_batch=batch)
-    out, size = [], None
+    seg = TeethSegmenter(weights, torch.device(device), max_batch=batch)
+    out = []
     if write:
         os.makedirs(os.path.join(path, "teeth_mask"), exist_ok=True)
-    for s in range(0, len(ids), batch):
-        frames = []
-        for i in ids[s:s + batch]:
-            img = Image.open(os.path.join(path, "ori_imgs", f"{i}.jpg"))
-            if size is None:
-                size = img.size                                              # (width, height)
-            elif img.size != size:
-                raise ValueError(f"{path}: ori_imgs/{i}.jpg is {img.size}, the first frame {size}")
-            frames.append(np.array(img.convert("RGB")))
-        mask = seg.mask(torch.from_numpy(np.stack(frames)))
+    for ids, frames, _ in convnet.frame_batches(path, batch):
+        mask = seg.mask(frames)
         out.append(mask)
         if write:
-            host = mask.cpu().numpy()
-            for j, i in enumerate(ids[s:s + batch]):
-                np.save(os.path.join(path, "teeth_mask", f"{i}.npy"), host[j].astype(np.bool_))
+            for i, host in zip(ids, mask.cpu().numpy()):
+                np.save(os.path.join(path, "teeth_mask", f"{i}.npy"), host.astype(np.bool_))
     return torch.cat(out, dim=0)

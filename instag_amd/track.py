@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import check_arg
 
 N_LMS = 68
 N_SLOTS = 16
@@ -481,15 +482,6 @@ def track_torch(model, lms, h, w, focals=FOCALS, every=40, focal_iters=(2000, 25
 
 
 # ---- the kernels ---------------------------------------------------------------------------------------------------------
-def _raise(code, what):
-    if code == 0:
-        return
-    msg = _lib.lib().instag_last_error().decode("utf-8", "replace")
-    if code == 1:                                                        # INSTAG_E_ARG
-        raise ValueError(f"{what}: {msg}")
-    raise RuntimeError(f"{what}: {msg}")
-
-
 class LandmarkTracker:
     """The fit on a HIP device.  States are TrackState objects (fp32, on the device); every method works in place and
     returns the state, so segments chain: ``fit_pose(st, 25, 0.1); fit_pose(st, 15, 0.1)`` is bit-identical to
@@ -533,20 +525,20 @@ class LandmarkTracker:
         """The candidate points [F,M,3] of the state's id / exp."""
         a, keep = self._args(st)
         with torch.cuda.device(self.device):
-            _raise(_lib.lib().instag_track_geometry(C.byref(a), _lib.current_stream()), "track_geometry")
+            check_arg(_lib.lib().instag_track_geometry(C.byref(a), _lib.current_stream()), "track_geometry")
         return st._ws[0].view(st.F, self.model.M, 3).clone()
 
     def fit_pose(self, st, n: int, lr: float):
         a, keep = self._args(st)
         with torch.cuda.device(self.device):
-            _raise(_lib.lib().instag_track_fit_pose(C.byref(a), int(n), float(lr), _lib.current_stream()), "track_fit_pose")
+            check_arg(_lib.lib().instag_track_fit_pose(C.byref(a), int(n), float(lr), _lib.current_stream()), "track_fit_pose")
         return st
 
     def fit_joint(self, st, n: int, lr_pose: float, lr_idexp: float):
         a, keep = self._args(st)
         with torch.cuda.device(self.device):
-            _raise(_lib.lib().instag_track_fit_joint(C.byref(a), int(n), float(lr_pose), float(lr_idexp),
-                                                     _lib.current_stream()), "track_fit_joint")
+            check_arg(_lib.lib().instag_track_fit_joint(C.byref(a), int(n), float(lr_pose), float(lr_idexp),
+                                                       _lib.current_stream()), "track_fit_joint")
         return st
 
     def loss_and_grads(self, st):
@@ -555,7 +547,7 @@ class LandmarkTracker:
         grads = (torch.empty_like(st.id), torch.empty_like(st.exp), torch.empty_like(st.pose))
         a, keep = self._args(st, grads)
         with torch.cuda.device(self.device):
-            _raise(_lib.lib().instag_track_loss_grad(C.byref(a), _lib.current_stream()), "track_loss_grad")
+            check_arg(_lib.lib().instag_track_loss_grad(C.byref(a), _lib.current_stream()), "track_loss_grad")
         return st.loss.clone(), dict(id=grads[0], exp=grads[1], pose=grads[2])
 
     def search_focal(self, lms, h, w, focals=FOCALS, every=40, iters=(2000, 2500)):

@@ -1,117 +1,13 @@
-"""Face parsing (csrc/parsing.hip): 256 seeded 512 x 512 frames through FaceParser.parse, beside parse_torch (library
-convolutions + batch norm, the same chunks) on the same GPU and the fp32 statement on the CPU.
+"""Face parsing (csrc/parsing.hip): 256 seeded 512 x 512 frames through FaceParser.parse, beside parse_torch on the same
+GPU and the fp32 statement on the CPU (scripts/_bench_frames.py has the method).
 
     python scripts/bench_parsing.py [--json out.json] [--frames 256] [--batch 8]
-
-The GPU figures are the median of WINDOWS windows of one pass over all frames, timed with device events around the
-window; the two GPU paths are measured in alternating windows of one process.  The CPU statement is timed on CPU_FRAMES
-frames with the wall clock.  FLOPs are 2 x the multiply-adds of the convolutions (parsing.macs_per_frame); the peak is
-the 157.3 TFLOP/s of the fp32 MFMA.  Per kernel: the operator's launches from a device trace of one chunk."""
-import argparse, json, os, re, statistics, sys, time
-import torch
+"""
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _bench_frames
 from instag_amd import parsing as P
 
-WINDOWS = 5
-CPU_FRAMES = 2
-PEAK_TFLOPS = 157.3
-dev = torch.device("cuda")
-
-
-def seeded_frames(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    low = torch.rand(n, 3, 32, 32, generator=g)
-    img = torch.nn.functional.interpolate(low, (P.SIZE, P.SIZE), mode="bilinear", align_corners=False)
-    img = 0.7 * img + 0.3 * torch.rand(n, 3, P.SIZE, P.SIZE, generator=g)
-    return (img * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
-
-
-def window(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-def operator_kernels(fn):
-    """Device time of the operator's kernels in one call, summed by kernel name, in microseconds."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        out = {}
-        for e in prof.events():
-            if "instag" not in e.name:
-                continue
-            m = re.search(r"(\w+_kernel(<[^>]*>)?)", e.name)
-            name = m.group(1) if m else e.name[:60]
-            t = float(getattr(e, "device_time", 0) or getattr(e, "cuda_time", 0))
-            n, s = out.get(name, (0, 0.0))
-            out[name] = (n + 1, s + t)
-        return {k: {"launches": n, "us": round(s, 1)} for k, (n, s) in sorted(out.items(), key=lambda kv: -kv[1][1])}
-    except Exception as exc:                                      # noqa: BLE001 (diagnostic leg only)
-        return {"unavailable": repr(exc)}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--json")
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--batch", type=int, default=8)
-    a = ap.parse_args()
-    w = P.BiSeNetWeights.random(0)
-    host = seeded_frames(a.frames)
-    frames = host.to(dev)
-    parser = P.FaceParser(w, dev, max_batch=a.batch)
-
-    def hip():
-        return parser.parse(frames)
-
-    def lib():
-        return torch.cat([P.parse_torch(w, frames[i:i + a.batch]) for i in range(0, a.frames, a.batch)])
-
-    # faster and different is not faster: the paths agree on the timed inputs
-    got, want = hip(), lib()
-    differ = float((got != want).any(dim=-1).double().mean())
-    assert differ < 0.01, differ
-    l_hip, l_lib = parser.logits(frames[:a.batch]), P.bisenet_torch(w, P.normalise(frames[:a.batch]))
-    rel = float((l_hip - l_lib).abs().max() / l_lib.abs().max())
-    assert rel < 1e-4, rel
-    t0 = time.perf_counter()
-    cpu = P.parse_torch(w, host[:CPU_FRAMES])
-    cpu_s = (time.perf_counter() - t0) / CPU_FRAMES
-    cpu_differ = float((got[:CPU_FRAMES].cpu() != cpu).any(dim=-1).double().mean())
-
-    t = {"hip": [], "torch": []}
-    for _ in range(WINDOWS):
-        t["hip"].append(window(hip))
-        t["torch"].append(window(lib))
-    flop = 2.0 * P.macs_per_frame() * a.frames
-    res = dict(frames=a.frames, size=P.SIZE, batch=a.batch, gmac_per_frame=P.macs_per_frame() / 1e9,
-               logits_hip_vs_torch_rel=rel, pixels_differing_hip_vs_torch=differ, pixels_differing_hip_vs_cpu=cpu_differ,
-               cpu_fp32_frames_per_s=1.0 / cpu_s, cpu_threads=torch.get_num_threads())
-    print(f"cpu  : {1.0 / cpu_s:.2f} frames/s (fp32 statement, {torch.get_num_threads()} threads, {CPU_FRAMES} frames)")
-    for k in ("hip", "torch"):
-        ms = statistics.median(t[k])
-        res[f"{k}_ms"] = ms
-        res[f"{k}_min_ms"] = min(t[k])
-        res[f"{k}_frames_per_s"] = a.frames / (ms * 1e-3)
-        res[f"{k}_tflops"] = flop / (ms * 1e-3) / 1e12
-        res[f"{k}_fraction_of_fp32_mfma_peak"] = res[f"{k}_tflops"] / PEAK_TFLOPS
-        print(f"{k:5s}: {ms:.1f} ms for {a.frames} frames (min {min(t[k]):.1f}), {res[f'{k}_frames_per_s']:.1f} frames/s, "
-              f"{res[f'{k}_tflops']:.2f} TFLOP/s, {100 * res[f'{k}_fraction_of_fp32_mfma_peak']:.1f} % of the fp32 MFMA peak",
-              flush=True)
-    res["hip_kernels_one_chunk"] = operator_kernels(lambda: parser.parse(frames[:a.batch]))
-    for k, v in res["hip_kernels_one_chunk"].items():
-        print(f"  {k:62s} {v}")
-    print(json.dumps(res), flush=True)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
-
-
 if __name__ == "__main__":
-    main()
+    _bench_frames.main(P, P.BiSeNetWeights.random(0), P.FaceParser, lambda parser, frames: parser.parse(frames), P.parse_torch)

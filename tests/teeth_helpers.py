@@ -6,9 +6,8 @@ and variance in [0.5, 1.5], beta and running mean of about 0.2, ``conv_seg``'s r
 under the keys of fpn-fp-512.pth; the generator loads it into the reference's own modules, the tests into
 ``FPNWeights``.  Under it between a fifth and four fifths of every stage's units are active, at least five labels occur
 in a 64 x 96 frame and class 7 (teeth) takes between 0.2 % and 50 % of its pixels."""
-import torch
-
-from tests.parsing_helpers import liveness, seeded_frames, top_two_margin  # noqa: F401 (re-exported)
+from tests import segnet_helpers as S
+from tests.segnet_helpers import liveness, seeded_frames, top_two_margin  # noqa: F401 (re-exported)
 
 SEED = 15
 G15_H, G15_W = 64, 96
@@ -25,14 +24,6 @@ def weights(seed: int = SEED):
 
 
 def reference_fp64(weights_, frames_u8):
-    """The fp64 statement on the CPU: logits at 1/4 resolution, the full-size logits, the labels, e32 of the fp32
-    statement against it (relative to the largest fp64 logit), and that largest logit."""
+    """segnet_helpers.reference_fp64 of the segmenter: logits at 1/4 resolution."""
     from instag_amd import teeth as T
-    H, W = frames_u8.shape[1:3]
-    with torch.no_grad():
-        want4 = T.fpn_torch(weights_, T.normalise(frames_u8, torch.float64))
-        full = T.upsample_torch(want4, H, W)
-        got32 = T.fpn_torch(weights_, T.normalise(frames_u8, torch.float32))
-    scale = float(want4.abs().max())
-    e32 = float((got32.double() - want4).abs().max()) / scale
-    return want4, full, T.first_argmax(full), e32, scale
+    return S.reference_fp64(T, T.fpn_torch, weights_, frames_u8)

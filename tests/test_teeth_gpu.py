@@ -18,25 +18,18 @@ import pytest
 import torch
 
 from tests import teeth_helpers as H
+from tests import segnet_helpers as S
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 8.0
 MAX_LEFT_OUT = 0.01
 
 
 def _case(weights, frames):
-    want4, full, labels, e32, scale = H.reference_fp64(weights, frames)
-    assert 1e-8 < e32 < 2e-5, e32
-    risk = H.top_two_margin(full) < 2.0 * FACTOR * e32 * scale
-    return dict(weights=weights, frames=frames, want4=want4, labels=labels, e32=e32, scale=scale, risk=risk)
+    return S.case(H.reference_fp64, weights, frames)
 
 
-def _check_logits(name, got, c):
-    err = float((got.detach().double().cpu() - c["want4"]).abs().max()) / c["scale"]
-    print(f"{name}: operator {err:.3e} e32 {c['e32']:.3e} bar {FACTOR * c['e32']:.3e} scale {c['scale']:.3e}")
-    assert tuple(got.shape) == tuple(c["want4"].shape) and got.dtype == torch.float32 and got.is_cuda
-    assert err <= FACTOR * c["e32"], (name, err, c["e32"])
+_check_logits = S.check_logits
 
 
 def _check_labels(name, labels, mask, c):
@@ -76,7 +69,7 @@ def test_g15(g15, g15_weights):
     frames = torch.from_numpy(g15["frame"])[None]
     c = _case(g15_weights, frames)
     golden = torch.from_numpy(g15["logits4"])[None]
-    assert float((c["want4"] - golden).abs().max()) <= 1e-9 * c["scale"]
+    assert float((c["want"] - golden).abs().max()) <= 1e-9 * c["scale"]
     assert np.array_equal(c["labels"][0].numpy(), g15["labels"])
     seg = TeethSegmenter(g15_weights, "cuda")
     _check_logits("g15", seg.logits(frames), c)
