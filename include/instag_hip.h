@@ -11,6 +11,12 @@
  *
  * Each entry point cites the reference interface it replaces (paths relative to the
  * reference checkout).
+ *
+ * Python reads this file: instag_amd/_cabi.py derives the ctypes structs, prototypes and constants from
+ * its text, so a declaration written here is the binding.  It takes block comments, preprocessor lines
+ * with integer `#define INSTAG_*` constants, `typedef struct [tag] { ... } name;` of scalars, pointers
+ * and fixed arrays, and `ret name(params);` over the fixed-width scalars, `instag_stream_t`, pointers to
+ * them and single pointers to the structs declared above the use; anything else makes the import raise.
  */
 #ifndef INSTAG_HIP_H
 #define INSTAG_HIP_H
@@ -31,6 +37,7 @@ typedef void* instag_stream_t; /* hipStream_t */
 
 const char* instag_last_error(void);
 /* ABI version of this header; bumped on any signature change. */
+#define INSTAG_ABI_VERSION 10
 int instag_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -344,14 +351,14 @@ int instag_linear_weight_grad(const float* dz, const float* in, float* dw, void*
  * instag_linear_weight_grad_workspace_bytes rounded up to 256 B.  At most 16 jobs. */
 typedef struct {
   const float* dz; /* [N,O] */
-  const float* in; /* [N,K] */
+  const float* inp; /* [N,K] */
   float* dw;       /* [O,K] (written) */
   int32_t N, O, K;
 } instag_wgrad_job;
 int instag_linear_weight_grad_batched(const instag_wgrad_job* jobs, int32_t n_jobs, void* workspace,
                                       size_t workspace_bytes, instag_stream_t stream);
-/* The same with ONE job (index glue_job) whose input rows are not stored: row r of its `in` is
- * cat(in[r] (KX = K - KA - KE values), aud[r] * enc_a (KA), relu(eye_pre[r]) * enc_e (KE)) -- sigma_net's input as the glue
+/* The same with ONE job (index glue_job) whose input rows are not stored: row r of its `inp` is
+ * cat(inp[r] (KX = K - KA - KE values), aud[r] * enc_a (KA), relu(eye_pre[r]) * enc_e (KE)) -- sigma_net's input as the glue
  * forms it (scene/motion_net.py:291-306).  instag_mlp_forward_glue then takes h_in = NULL and does not write those rows
  * (30 MB at 100k Gaussians).  65 <= K <= 96. */
 int instag_linear_weight_grad_batched_glue(const instag_wgrad_job* jobs, int32_t n_jobs, int32_t glue_job,

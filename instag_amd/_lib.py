@@ -9,6 +9,8 @@ import ctypes as C
 import os
 import threading
 
+from . import _cabi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libinstag_hip.so")
 
@@ -16,82 +18,19 @@ _lib = None
 _lock = threading.Lock()
 
 vp = C.c_void_p
-u32 = C.c_uint32
 i32 = C.c_int32
-i64 = C.c_int64
 f32 = C.c_float
-sz = C.c_size_t
 
-
-class FaceLossCfg(C.Structure):
-    """struct instag_face_loss_cfg (include/instag_hip.h)."""
-    _fields_ = [("H", i32), ("W", i32), ("flags", i32), ("w_dssim", f32), ("w_alpha", f32),
-                ("w_attn_hair", f32), ("w_attn_lips", f32), ("w_extra", f32)]
-
-
-class LpipsWeights(C.Structure):
-    """struct instag_lpips_weights (include/instag_hip.h)."""
-    _fields_ = [("wf", vp * 5), ("bias", vp * 5), ("wb", vp * 5), ("lin", vp * 5)]
-
-
-class AveEncoderWeights(C.Structure):
-    """struct instag_ave_encoder_weights (include/instag_hip.h)."""
-    _fields_ = [("w", vp * 13), ("scale", vp * 13), ("shift", vp * 13)]
-
-
-class ParsingWeights(C.Structure):
-    """struct instag_parsing_weights (include/instag_hip.h)."""
-    _fields_ = [("w", vp * 32), ("scale", vp * 32), ("shift", vp * 32)]
-
-
-class TeethWeights(C.Structure):
-    """struct instag_teeth_weights (include/instag_hip.h)."""
-    _fields_ = [("w", vp * 71), ("scale", vp * 71), ("shift", vp * 71)]
-
-
-class FrameUnpackArgs(C.Structure):
-    """struct instag_frame_unpack_args (include/instag_hip.h)."""
-    _fields_ = [("store", vp), ("records", vp), ("normal", vp), ("depth", vp), ("audio", vp), ("dst", vp),
-                ("dst_bytes", i64),
-                ("off_image", i64), ("off_background", i64), ("off_face", i64), ("off_hair", i64), ("off_mouth", i64),
-                ("off_world_view", i64), ("off_full_proj", i64), ("off_camera_center", i64), ("off_au_exp", i64),
-                ("off_lips_rect", i64), ("off_auds", i64), ("off_normal", i64), ("off_depth", i64),
-                ("F", i32), ("H", i32), ("W", i32), ("idx", i32), ("audio_index", i32), ("T", i32), ("audio_row", i32),
-                ("reserved", i32)]
-
-
-class TrackArgs(C.Structure):
-    """struct instag_track_args (include/instag_hip.h)."""
-    _fields_ = [(n, vp) for n in ("basis", "basis_t", "mu", "lms", "id", "exp", "pose", "m_pose", "v_pose", "m_exp",
-                                  "v_exp", "m_id", "v_id", "state", "geo", "did", "frame_loss", "loss", "sel", "g_id",
-                                  "g_exp", "g_pose")] + \
-               [("group_start", C.POINTER(i32)), ("focal", C.POINTER(f32))] + \
-               [(n, i32) for n in ("G", "F", "id_dim", "exp_dim", "P", "n_landmarks")] + [("cx", f32), ("cy", f32)]
-
-
-class MeshSettings(C.Structure):
-    """struct instag_mesh_settings (include/instag_hip.h)."""
-    _fields_ = [(n, i32) for n in ("H", "W", "K", "reserved")] + \
-               [(n, C.c_double) for n in ("sigma", "gamma", "blur_radius", "znear", "zfar", "eps", "bg_r", "bg_g", "bg_b")]
-
-
-class WgradJob(C.Structure):
-    """struct instag_wgrad_job (include/instag_hip.h)."""
-    _fields_ = [("dz", vp), ("inp", vp), ("dw", vp), ("N", i32), ("O", i32), ("K", i32)]
-
-
-class RasterArgs(C.Structure):
-    """struct instag_raster_args (include/instag_hip.h)."""
-    _fields_ = [
-        ("N", i32), ("M", i32), ("sh_degree", i32), ("E", i32),
-        ("image_height", i32), ("image_width", i32),
-        ("tanfovx", f32), ("tanfovy", f32), ("scale_modifier", f32),
-        ("prefiltered", i32), ("debug", i32), ("single_stream", i32),
-        ("bg", vp), ("viewmatrix", vp), ("projmatrix", vp), ("campos", vp),
-        ("means3D", vp), ("shs", vp), ("colors_precomp", vp), ("opacities", vp),
-        ("scales", vp), ("rotations", vp), ("cov3Ds_precomp", vp), ("extra_attrs", vp),
-        ("shs_rest", vp), ("walk_hints", vp),
-    ]
+# The C ABI is stated once, in include/instag_hip.h: the struct classes, the prototypes and the constants are read from
+# its text here, and a declaration _cabi cannot read raises.  struct instag_raster_args is the class RasterArgs, and so
+# on: FaceLossCfg, LpipsWeights, AveEncoderWeights, ParsingWeights, TeethWeights, FrameUnpackArgs, TrackArgs,
+# MeshSettings, WgradJob.
+_STRUCTS, _PROTOTYPES, _CONSTANTS = _cabi.read()
+globals().update((cls.__name__, cls) for cls in _STRUCTS.values())
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
+ABI_VERSION = _CONSTANTS["INSTAG_ABI_VERSION"]     # a stale libinstag_hip.so must not be driven with these prototypes
+E_ARG = _CONSTANTS["INSTAG_E_ARG"]
+FACE_LOSS = {k[len("INSTAG_FACE_LOSS_"):]: v for k, v in _CONSTANTS.items() if k.startswith("INSTAG_FACE_LOSS_")}
 
 
 # ---- streams -------------------------------------------------------------------------------------------------------
@@ -242,171 +181,6 @@ def leaf_stream(stream):
         _LEAF_STREAMS.append(stream)
 
 
-_PROTOS = {
-    "instag_last_error": (C.c_char_p, []),
-    "instag_abi_version": (C.c_int, []),
-    "instag_grid_encode_forward": (C.c_int, [vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, C.c_int, u32, vp]),
-    "instag_grid_encode_backward": (C.c_int, [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32,
-                                              C.c_int, u32, vp]),
-    "instag_grid_total_variation_workspace_bytes": (sz, [u32, u32]),
-    "instag_grid_total_variation": (C.c_int, [vp, vp, vp, vp, f32, u32, u32, u32, u32, f32, u32, u32, C.c_int,
-                                              u32, vp, sz, vp]),
-    "instag_triplane_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, u32, f32, u32, u32, f32, u32, f32, u32, vp]),
-    "instag_triplane_backward_workspace_bytes": (sz, [u32, u32]),
-    "instag_triplane_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, u32, f32, vp,
-                                           u32, u32, f32, u32, f32, u32, vp, vp, vp]),
-    "instag_sh_encode_forward": (C.c_int, [vp, vp, u32, u32, u32, vp, vp]),
-    "instag_sh_encode_backward": (C.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
-    "instag_raster_geom_bytes": (sz, [i32]),
-    "instag_raster_image_bytes": (sz, [i32, i32]),
-    "instag_raster_binning_bytes": (sz, [i64, i32, i32]),
-    "instag_raster_backward_workspace_bytes": (sz, [i32, i64]),
-    "instag_raster_forward_stage1": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, C.POINTER(i64), vp]),
-    "instag_raster_forward_stage2": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, sz, vp, sz, i64,
-                                               vp, vp, vp, vp, vp, vp, vp, vp]),
-    "instag_raster_forward_capacity": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, sz, vp, sz, i64, vp, vp,
-                                                 vp, vp, vp, vp, vp, vp, vp, vp]),
-    "instag_raster_aux_backward": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, sz, vp, sz, i64, vp, vp, vp, vp, sz,
-                                             vp, vp, vp]),
-    "instag_raster_backward": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, sz, vp, sz, i64, vp,
-                                         vp, vp, vp, vp, vp, vp, sz,
-                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "instag_raster_debug_export": (C.c_int, [vp, sz, vp, sz, vp, sz, i32, i64, i32, i32,
-                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "instag_raster_debug_export_flags": (C.c_int, [vp, sz, i32, vp, vp]),
-    "instag_raster_debug_export_work_list": (C.c_int, [vp, sz, vp, sz, i64, i32, i32, vp, vp, i64, vp, vp]),
-    "instag_debug_depth_sort": (C.c_int, [C.POINTER(RasterArgs), vp, sz, vp, vp, vp]),
-    "instag_debug_depth_sort_blocks": (C.c_uint32, [i32]),
-    "instag_raster_sort_stalls": (C.c_int, [vp, i32, vp]),
-    "instag_raster_sort_stalls_clear": (C.c_int, [vp]),
-    "instag_debug_scan_stall_probe": (C.c_int, [vp]),
-    "instag_mlp_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "instag_mlp_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "instag_mlp_backward_add": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "instag_linear_weight_grad_batched": (C.c_int, [vp, i32, vp, sz, vp]),
-    "instag_linear_weight_grad_batched_glue": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, sz, vp]),
-    "instag_mlp_backward_glue_supported": (C.c_int, [i32] * 6),
-    "instag_mlp_backward_glue_num_partials": (C.c_int, [i32]),
-    "instag_mlp_backward_glue": (C.c_int, [vp] * 18 + [i32] * 3 + [vp]),
-    "instag_mlp_forward_glue": (C.c_int, [vp] * 13 + [i32] * 3 + [vp]),
-    "instag_extreme_values_workspace_bytes": (sz, [i32, i32]),
-    "instag_extreme_values": (C.c_int, [vp, i32, i32, vp, vp, vp, sz, vp]),
-    "instag_jaw_feature_workspace_bytes": (sz, [i32, i32]),
-    "instag_jaw_feature": (C.c_int, [vp, i32, i32, i32, f32, i32, vp, i32, vp, vp, sz, vp]),
-    "instag_mlp2_supported": (C.c_int, [i32] * 5),
-    "instag_mlp2_forward": (C.c_int, [vp] * 9 + [i32] * 6 + [vp]),
-    "instag_mlp2_backward": (C.c_int, [vp] * 12 + [i32] * 6 + [vp]),
-    "instag_linear_weight_grad_workspace_bytes": (sz, [i32, i32, i32]),
-    "instag_linear_weight_grad": (C.c_int, [vp, vp, vp, vp, sz, i32, i32, i32, vp]),
-    "instag_motion_glue_forward": (C.c_int, [vp] * 7 + [i32] * 4 + [vp]),
-    "instag_motion_glue_backward_num_partials": (C.c_int, [i32, i32, i32, i32]),
-    "instag_motion_glue_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
-    "instag_deform_activate_num_reg_partials": (C.c_int, [i32]),
-    "instag_deform_activate_forward": (C.c_int, [vp] * 11 + [f32, i32, vp]),
-    "instag_deform_activate_backward": (C.c_int, [vp] * 16 + [f32, i32, vp]),
-    "instag_abs_mean_num_partials": (C.c_int, [i32]),
-    "instag_abs_mean_forward": (C.c_int, [vp, i32, i32, i32, f32, vp, vp]),
-    "instag_abs_mean_backward": (C.c_int, [vp, vp, i32, i32, i32, f32, vp, vp]),
-    "instag_mouth_glue_forward": (C.c_int, [vp] * 5 + [i32] * 4 + [vp]),
-    "instag_mouth_glue_backward_num_partials": (C.c_int, [i32]),
-    "instag_mouth_glue_backward": (C.c_int, [vp] * 4 + [i32] * 4 + [vp]),
-    "instag_fuse_compose_forward": (C.c_int, [vp] * 8 + [i32, i32, vp]),
-    "instag_fuse_compose_backward": (C.c_int, [vp] * 10 + [i32, i32, vp]),
-    "instag_mouth_activate_forward": (C.c_int, [vp] * 6 + [f32] * 3 + [vp] * 4 + [i32, vp]),
-    "instag_mouth_activate_backward": (C.c_int, [vp] * 5 + [f32] * 3 + [vp] * 10 + [i32, vp]),
-    "instag_motion_l1_reg_num_partials": (C.c_int, [i32]),
-    "instag_motion_l1_reg_forward": (C.c_int, [vp, vp, vp, i32, vp]),
-    "instag_motion_l1_reg_backward": (C.c_int, [vp, vp, vp, vp, vp, i32, vp]),
-    "instag_knn3_mean_dist2": (C.c_int, [vp, vp, i32, vp]),
-    "instag_densify_stats": (C.c_int, [vp, vp, vp, vp, vp, i32, vp]),
-    "instag_densify_stats_add": (C.c_int, [vp] * 6 + [i32, vp]),
-    "instag_frame_code_saved_floats": (C.c_int64, [i32, i32, i32]),
-    "instag_frame_code_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
-    "instag_frame_code_backward_workspace_bytes": (sz, [i32, i32, i32]),
-    "instag_frame_code_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
-    "instag_frame_code_ave_saved_floats": (C.c_int64, [i32]),
-    "instag_frame_code_ave_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
-    "instag_frame_code_ave_backward_workspace_bytes": (sz, [i32]),
-    "instag_frame_code_ave_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
-    "instag_l1_ssim_num_partials": (C.c_int, [i32, i32, i32]),
-    "instag_l1_ssim_forward": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
-    "instag_l1_ssim_backward": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
-    "instag_face_loss_num_partials": (C.c_int64, [i32, i32]),
-    "instag_face_loss_forward": (C.c_int, [vp] * 11 + [i32] + [vp] * 4),
-    "instag_face_loss_backward": (C.c_int, [vp] * 16),
-    "instag_face_loss_forward_deferred": (C.c_int, [vp] * 11 + [i32] + [vp] * 3),
-    "instag_face_loss_backward_deferred": (C.c_int, [vp] * 11 + [i32] + [vp] * 7),
-    "instag_geometry_prior_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float,
-                                                vp, vp, vp, vp]),
-    "instag_geometry_prior_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float,
-                                                 vp, vp, vp, vp, vp, vp]),
-    "instag_adam_chunk_elems": (C.c_int, []),
-    "instag_adam_step": (C.c_int, [vp, i32, vp, vp, vp, i32, vp, vp]),
-    "instag_adam_grads_max": (C.c_int, []),
-    "instag_adam_step_grads": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp]),
-    "instag_adam_step_grads_ticketed": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
-    "instag_adam_ema_step": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, C.c_double, vp]),
-    "instag_pretrain_deform_max_others": (C.c_int, []),
-    "instag_pretrain_deform_num_partials": (C.c_int, [i32]),
-    "instag_pretrain_deform_forward": (C.c_int, [vp] * 7 + [i32] + [vp] * 5 + [i32, vp]),
-    "instag_pretrain_deform_backward": (C.c_int, [vp] * 6 + [i32] + [vp] * 11 + [i32, vp]),
-    "instag_pretrain_mouth_deform_num_partials": (C.c_int, [i32]),
-    "instag_pretrain_mouth_deform_forward": (C.c_int, [vp] * 8 + [f32] * 3 + [vp] * 5 + [i32, vp]),
-    "instag_pretrain_mouth_deform_backward": (C.c_int, [vp] * 7 + [f32] * 3 + [vp] * 12 + [i32, vp]),
-    "instag_window_mean_forward": (C.c_int, [vp, i32, i32, i32, i32, vp, f32, vp, i32, vp, vp]),
-    "instag_window_mean_backward": (C.c_int, [i32, i32, i32, i32, vp, f32, vp, vp, vp]),
-    "instag_lpips_workspace_bytes": (sz, [i32] * 5),
-    "instag_lpips_max_patches": (C.c_int, [i32] * 5),
-    "instag_lpips_forward": (C.c_int, [C.POINTER(LpipsWeights), vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, sz,
-                                       vp, vp, vp]),
-    "instag_lpips_backward": (C.c_int, [C.POINTER(LpipsWeights), vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz,
-                                        vp, vp]),
-    "instag_ave_encoder_max_batch": (C.c_int, []),
-    "instag_ave_encoder_workspace_bytes": (sz, [i32]),
-    "instag_ave_encoder_forward": (C.c_int, [C.POINTER(AveEncoderWeights), vp, i32, vp, i32, vp, vp, sz, vp]),
-    "instag_frame_metrics_num_partials": (C.c_int64, [i32, i32, i32]),
-    "instag_frame_metrics": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
-    "instag_meter_add": (C.c_int, [vp, i32, vp, vp]),
-    "instag_infer_compose": (C.c_int, [vp] * 6 + [i32, vp, vp, i32, i32, vp]),
-    "instag_frame_store_stride": (C.c_int64, [i32, i32]),
-    "instag_frame_record_dwords": (i32, []),
-    "instag_frame_ingest": (C.c_int, [vp] * 5 + [i32] * 3 + [vp, vp, vp]),
-    "instag_frame_unpack": (C.c_int, [C.POINTER(FrameUnpackArgs), vp]),
-    "instag_prep_background_workspace_bytes": (sz, [i32, i32, i32]),
-    "instag_prep_background": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "instag_prep_frames": (C.c_int, [vp] * 4 + [i32] * 3 + [vp] * 4),
-    "instag_parsing_workspace_bytes": (sz, [i32, i32, i32]),
-    "instag_parsing_forward": (C.c_int, [C.POINTER(ParsingWeights), vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "instag_parsing_labels": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
-    "instag_teeth_workspace_bytes": (sz, [i32, i32, i32]),
-    "instag_teeth_forward": (C.c_int, [C.POINTER(TeethWeights), vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "instag_teeth_labels": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
-    "instag_track_max_groups": (C.c_int, []),
-    "instag_track_geometry": (C.c_int, [C.POINTER(TrackArgs), vp]),
-    "instag_track_fit_pose": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, vp]),
-    "instag_track_fit_joint": (C.c_int, [C.POINTER(TrackArgs), i32, C.c_double, C.c_double, vp]),
-    "instag_track_loss_grad": (C.c_int, [C.POINTER(TrackArgs), vp]),
-    "instag_mesh_vertex_forward": (C.c_int, [vp] * 5 + [i32] * 4 + [vp, vp]),
-    "instag_mesh_vertex_backward_workspace_bytes": (sz, [i32, i32]),
-    "instag_mesh_vertex_backward": (C.c_int, [vp] * 6 + [i32] * 4 + [vp] * 4 + [sz, vp]),
-    "instag_mesh_select": (C.c_int, [C.POINTER(MeshSettings), vp, vp, i32, i32, i32, vp, vp, vp]),
-    "instag_mesh_blend_forward": (C.c_int, [C.POINTER(MeshSettings), vp, vp, vp, vp, i32, i32, i32, vp, vp]),
-    "instag_mesh_blend_backward": (C.c_int, [C.POINTER(MeshSettings), vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
-    "instag_prof_enable": (C.c_int, [C.c_int]),
-    "instag_prof_reset": (C.c_int, []),
-    "instag_prof_read": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),
-    "instag_prof_graph_begin": (C.c_int, [i32]),
-    "instag_prof_graph_pairs_used": (C.c_int, []),
-    "instag_prof_graph_collect": (C.c_int, []),
-    "instag_prof_graph_end": (C.c_int, []),
-}
-
-EXPORTED_SYMBOLS = tuple(_PROTOS)
-
-
-ABI_VERSION = 10    # instag_abi_version() in csrc/raster_api.hip: a stale libinstag_hip.so must not be driven with these prototypes
-
-
 def lib():
     """Load (once) and return the ctypes handle; raises if the HIP library is unavailable."""
     global _lib
@@ -423,7 +197,7 @@ def lib():
         # "no ROCm-capable device is detected" from the second one.
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in _PROTOTYPES.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
@@ -443,10 +217,10 @@ def check(code: int, what: str = ""):
 
 def check_arg(code: int, what: str):
     """``check`` for the entry points whose callers tell a refused argument from a failure: ValueError for
-    INSTAG_E_ARG (1), RuntimeError for every other non-zero code."""
+    INSTAG_E_ARG, RuntimeError for every other non-zero code."""
     if code != 0:
         msg = lib().instag_last_error().decode("utf-8", "replace")
-        raise (ValueError if code == 1 else RuntimeError)(f"{what}: {msg}")
+        raise (ValueError if code == E_ARG else RuntimeError)(f"{what}: {msg}")
 
 
 def workspace_bytes(nbytes: int) -> int:

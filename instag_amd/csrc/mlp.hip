@@ -1129,10 +1129,10 @@ static int weight_grad_batched_impl(const instag_wgrad_job* jobs, int32_t n_jobs
   int N0 = jobs[0].N, max_count = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const instag_wgrad_job& q = jobs[i];
-    INSTAG_REQUIRE(q.dz && q.in && q.dw, "linear_weight_grad_batched: NULL tensor");
+    INSTAG_REQUIRE(q.dz && q.inp && q.dw, "linear_weight_grad_batched: NULL tensor");
     INSTAG_REQUIRE(q.O >= 1 && q.O <= 64 && q.K >= 1 && q.K <= 96, "linear_weight_grad: need O <= 64 and K <= 96");
     INSTAG_REQUIRE(q.N == N0 && q.N >= 1, "linear_weight_grad_batched: all jobs must have the same N >= 1");
-    b.j[i] = WgJob{q.dz, q.in, (float*)((char*)workspace + off), q.dw, q.N, q.O, q.K, 0};
+    b.j[i] = WgJob{q.dz, q.inp, (float*)((char*)workspace + off), q.dw, q.N, q.O, q.K, 0};
     off += (instag_linear_weight_grad_workspace_bytes(q.N, q.O, q.K) + 255) / 256 * 256;
     max_count = std::max(max_count, q.O * q.K);
   }

@@ -11,6 +11,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from ._lib import FACE_LOSS
+
 _WINDOWS = {}
 
 
@@ -178,7 +180,8 @@ def l1_and_ssim(img1, img2):
 
 
 # ---- the face branch's whole loss block ---------------------------------------------------------------------------
-FLAG_HAIR_TO_BG, FLAG_ALPHA, FLAG_HAIR_ATTN, FLAG_LIPS, FLAG_MOUTH, FLAG_PLAIN = 1, 2, 4, 8, 16, 32
+FLAG_HAIR_TO_BG, FLAG_ALPHA, FLAG_HAIR_ATTN, FLAG_LIPS, FLAG_MOUTH, FLAG_PLAIN = (
+    FACE_LOSS[n] for n in ("HAIR_TO_BG", "ALPHA", "HAIR_ATTN", "LIPS", "MOUTH", "PLAIN"))   # INSTAG_FACE_LOSS_*
 
 
 def face_loss_torch(image, gt, face_mask, hair_mask, mouth_mask, bg, alpha=None, attn=None, lips_rect=None,

@@ -516,7 +516,7 @@ class LandmarkTracker:
         if grads is not None:
             a.g_id, a.g_exp, a.g_pose = (g.data_ptr() for g in grads)
         starts, focals = (_lib.i32 * (st.G + 1))(*st.start), (_lib.f32 * st.G)(*st.focals)
-        a.group_start, a.focal = starts, focals
+        a.group_start, a.focal = C.addressof(starts), C.addressof(focals)
         a.G, a.F, a.id_dim, a.exp_dim, a.P, a.n_landmarks = st.G, F, m.id_dim, m.exp_dim, m.P, N_LMS
         a.cx, a.cy = st.cx, st.cy
         return a, (starts, focals)

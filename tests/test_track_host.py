@@ -236,7 +236,7 @@ def test_track_argument_errors_do_not_need_a_gpu():
         for n in pointers:
             setattr(a, n, one)
         a._keep = ((_lib.i32 * len(starts))(*starts), (_lib.f32 * G)(*([1000.0] * G)))
-        a.group_start, a.focal = a._keep
+        a.group_start, a.focal = (ctypes.addressof(k) for k in a._keep)
         a.G, a.F, a.id_dim, a.exp_dim, a.P, a.n_landmarks = G, starts[-1], 100, 79, 20, 68
         a.cx = a.cy = 256.0
         for k, v in kw.items():
