@@ -292,23 +292,30 @@ int instag_debug_scan_stall_probe(instag_stream_t stream);
  * eye_att_net, align_net; instantiated at :234-238 and :600-604), i.e. for NL layers
  *     y = W_NL * relu(... relu(W_1 x))          W_l row-major [out_l, in_l] (torch.nn.Linear.weight)
  * x [N,K0], hidden width H, y [N,O]; NL in {2,3}; K0 <= 96, H <= 64, O <= 32.
- * forward optionally stores the post-ReLU hidden activations a1 [N,H] (and a2 [N,H] for NL==3) for
- * backward (pass NULL for inference).  backward consumes dy [N,O] and writes the pre-activation
- * gradients dz1 [N,H] (dz2 [N,H]) and, when dx != NULL, dx [N,K0]; the weight gradients are then
+ * forward optionally stores the post-ReLU hidden activations a1 [N,H] (and a2 [N,H] for NL==3) for the
+ * weight gradients and their ReLU sign words s1 (s2) for backward (pass NULL for inference; for NL==3
+ * s1 and s2 are given or NULL together).
+ * Sign words: one uint32_t per lane and 32-row tile and hidden layer, s[tile][lane] = [ceil(N/32)][64]
+ * (256 B per tile).  Bit 16 b + r of word (tile, lane) is set when feature
+ *     32 b + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)            b in {0,1}, r in 0..15
+ * of row 32 tile + (lane & 31) is > 0 after the ReLU (a NaN gives 0); bits of features >= H and of rows
+ * >= N are 0.  This is the register layout of the kernels' tiles: a lane builds and reads its own word.
+ * backward consumes dy [N,O] and the sign words (one bit of every activation is all it needs) and writes
+ * the pre-activation gradients dz1 [N,H] (dz2 [N,H]) and, when dx != NULL, dx [N,K0]; the weight gradients are then
  *     dW_1 = dz1^T x,  dW_2 = dz2^T a1 (NL==3) or dy^T a1 (NL==2),  dW_3 = dy^T a2
  * each computed with instag_linear_weight_grad (dz [N,O], in [N,K] -> dw [O,K]; O <= 64, K <= 96;
  * workspace of instag_linear_weight_grad_workspace_bytes; deterministic).
  * ------------------------------------------------------------------------------------------ */
 int instag_mlp_forward(const float* x, const float* w1, const float* w2, const float* w3, float* y,
-                       float* a1, float* a2, int32_t N, int32_t K0, int32_t H, int32_t O, int32_t NL,
-                       instag_stream_t stream);
-int instag_mlp_backward(const float* dy, const float* a1, const float* a2, const float* w1,
+                       float* a1, float* a2, uint32_t* s1, uint32_t* s2, int32_t N, int32_t K0, int32_t H,
+                       int32_t O, int32_t NL, instag_stream_t stream);
+int instag_mlp_backward(const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1,
                         const float* w2, const float* w3, float* dz1, float* dz2, float* dx, int32_t N,
                         int32_t K0, int32_t H, int32_t O, int32_t NL, instag_stream_t stream);
 /* as instag_mlp_backward with dx = dX + dx_add ([N,K0], may be dx itself or NULL): when the MLP's input feeds other
  * consumers too (scene/motion_net.py:281-306: enc_x goes to both attention MLPs and into sigma_net's input), their
  * gradient is summed inside this kernel instead of by an elementwise launch in between */
-int instag_mlp_backward_add(const float* dy, const float* a1, const float* a2, const float* w1,
+int instag_mlp_backward_add(const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1,
                             const float* w2, const float* w3, float* dz1, float* dz2, float* dx,
                             const float* dx_add, int32_t N, int32_t K0, int32_t H, int32_t O, int32_t NL,
                             instag_stream_t stream);
@@ -319,27 +326,31 @@ int instag_mlp_backward_add(const float* dy, const float* a1, const float* a2, c
  * d_amb [N,3] may be NULL. */
 int instag_mlp_backward_glue_supported(int32_t K0, int32_t H, int32_t O, int32_t KX, int32_t KA, int32_t KE);
 int instag_mlp_backward_glue_num_partials(int32_t N);
-int instag_mlp_backward_glue(const float* dy, const float* a1, const float* a2, const float* w1, const float* w2,
+int instag_mlp_backward_glue(const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1, const float* w2,
                              const float* w3, float* dz1, float* dz2, const float* aud, const float* eye_pre,
                              const float* enc_a, const float* enc_e, const float* amb, const float* d_amb,
                              float* d_enc_x, float* d_aud, float* d_eye_pre, float* col_partials, int32_t N,
                              int32_t H, int32_t O, instag_stream_t stream);
 /* ... and its forward with the glue operator's forward (instag_motion_glue_forward) in front of the first layer: the
  * input rows are formed in registers; h_in [N,74] (read by the first layer's weight gradient) and amb [N,3] are still
- * written once.  a1 / a2 may be NULL (no gradient wanted). */
+ * written once.  a1 / a2 and s1 / s2 may be NULL (no gradient wanted). */
 int instag_mlp_forward_glue(const float* enc_x, const float* aud, const float* eye_pre, const float* enc_a,
                             const float* enc_e, const float* w1, const float* w2, const float* w3, float* y, float* a1,
-                            float* a2, float* h_in, float* amb, int32_t N, int32_t H, int32_t O,
-                            instag_stream_t stream);
+                            float* a2, uint32_t* s1, uint32_t* s2, float* h_in, float* amb, int32_t N, int32_t H,
+                            int32_t O, instag_stream_t stream);
 /* Two 2-layer MLPs over the SAME input x in one launch: (MLP_a(x), MLP_b(x)) -- the universal field's aud_ch_att_net and
  * eye_att_net both read the tri-plane features (scene/motion_net.py:281-290).  backward: dx = W_a1^T dz1a + W_b1^T dz1b
  * (+ dx_add, which may alias dx).  instag_mlp2_supported: 1 when the shape pair has a kernel (36 -> 32 -> 32 with
- * 36 -> 16 -> 6, in groups of eight features); otherwise launch the heads one by one. */
+ * 36 -> 16 -> 6, in groups of eight features); otherwise launch the heads one by one.
+ * Both hidden layers fit one 32-feature block, so the forward packs the two heads' sign bits into ONE word per lane and
+ * tile, s1 [ceil(N/32)][64]: head A in bits 0..15, head B in bits 16..31 (bit r / 16 + r <-> feature
+ * (r & 3) + 8 (r >> 2) + 4 (lane >> 5)).  backward reads head A's bits from the low half of s1a and head B's from the
+ * high half of s1b: pass the forward's buffer for both. */
 int instag_mlp2_supported(int32_t K0, int32_t HA, int32_t OA, int32_t HB, int32_t OB);
 int instag_mlp2_forward(const float* x, const float* wa1, const float* wa2, const float* wb1, const float* wb2,
-                        float* ya, float* yb, float* a1a, float* a1b, int32_t N, int32_t K0, int32_t HA, int32_t OA,
-                        int32_t HB, int32_t OB, instag_stream_t stream);
-int instag_mlp2_backward(const float* dya, const float* dyb, const float* a1a, const float* a1b, const float* wa1,
+                        float* ya, float* yb, float* a1a, float* a1b, uint32_t* s1, int32_t N, int32_t K0, int32_t HA,
+                        int32_t OA, int32_t HB, int32_t OB, instag_stream_t stream);
+int instag_mlp2_backward(const float* dya, const float* dyb, const uint32_t* s1a, const uint32_t* s1b, const float* wa1,
                          const float* wa2, const float* wb1, const float* wb2, float* dz1a, float* dz1b, float* dx,
                          const float* dx_add, int32_t N, int32_t K0, int32_t HA, int32_t OA, int32_t HB, int32_t OB,
                          instag_stream_t stream);

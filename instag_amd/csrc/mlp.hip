@@ -155,10 +155,19 @@ __device__ __forceinline__ void stage_weights(float* __restrict__ lds, const flo
 // Z^T = W X^T for one layer: in[KB] (layout L) -> acc[OB] (layout L).  KQ = number of 8-feature groups of the
 // input that hold data (compile time: a run-time test per k-step would split the chain into basic blocks and
 // make the compiler shuttle the accumulators between AGPRs and VGPRs around every MFMA).
-template <int KQ, int KB, int OB>
+// SIGN: `in` is a hidden layer's post-ReLU output and its sign word (see "ReLU sign words" below) is gathered here, behind
+// the MFMAs of the k-step that consumes the same register, where the operations issue while the matrix pipe is busy.
+// (Built in one piece after the ReLU -- compare into a lane mask, select, or: 32 x 4 issue slots per layer in front of the
+// next MFMA -- the word cost the sigma_net forward +2.2 us at 100k rows; here +0.7.)  The bit: a post-ReLU value is +0, -0
+// or positive (fmaxf returns the other operand for a NaN), so read as an integer and clamped to [0,1] it is `act > 0`;
+// v_med3_i32 is written out because the compiler turns the same clamp in C++ back into compare + select.
+// SHIFT: bit position of register 0 of block 0.
+template <int KQ, int KB, int OB, bool SIGN = false, int SHIFT = 0>
 __device__ __forceinline__ void layer_forward(const float* __restrict__ Wl, const f32x16 (&in)[KB], f32x16 (&acc)[OB],
-                                              int l31, int h) {
+                                              int l31, int h, uint32_t* sign = nullptr) {
+  static_assert(!SIGN || 16 * KB + SHIFT <= 32, "layer_forward: one sign word per lane");
   constexpr int KS = KB * 32 + 1;
+  uint32_t w = 0;
 #pragma unroll
   for (int t = 0; t < OB; ++t)
 #pragma unroll
@@ -174,9 +183,15 @@ __device__ __forceinline__ void layer_forward(const float* __restrict__ Wl, cons
           const float a = Wl[(32 * t + l31) * KS + k];
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, in[b][r], acc[t], 0, 0, 0);
         }
+        if (SIGN) {
+          uint32_t bit;
+          asm("v_med3_i32 %0, %1, 0, 1" : "=v"(bit) : "v"(in[b][r]));
+          w |= bit << (16 * b + r + SHIFT);
+        }
       }
     }
   }
+  if (SIGN) *sign |= w;
 }
 
 // dIn^T = W^T dZ^T for one layer: dz[OB] -> din[KB]; OQ = number of 8-feature groups of dz that hold data
@@ -212,12 +227,26 @@ __device__ __forceinline__ void relu_blocks(f32x16 (&v)[NB]) {
     for (int i = 0; i < 16; ++i) v[b][i] = fmaxf(v[b][i], 0.f);
 }
 
-template <int NB>
-__device__ __forceinline__ void mask_blocks(f32x16 (&g)[NB], const f32x16 (&act)[NB]) {
+// ---- ReLU sign words ---------------------------------------------------------------------------------------------
+// The backward-data chain needs one bit of every hidden activation (act > 0), the weight gradients need the values.  The
+// forward therefore also writes, per hidden layer, one 32-bit word per lane and 32-row tile, S[tile][lane] (256 B per
+// tile, coalesced): bit 16 b + r <-> register r of block b of that lane, i.e. feature 32 b + feat(r, lane >> 5) of row
+// 32 tile + (lane & 31).  The predicate is taken on the post-ReLU value (NaN -> 0); padding features and rows hold zeros
+// in the registers, so their bits are 0 (the forward gathers the word in layer_forward).  The backward kernels read these
+// words (2 registers per tile of a 3-layer MLP) instead of the activations (64), which leaves room to prefetch the next
+// tile in every variant.
+// SHIFT: mlp2 packs head A into the low and head B into the high half of one word.
+template <int NB, int SHIFT = 0>
+__device__ __forceinline__ void mask_blocks(f32x16 (&g)[NB], uint32_t word) {
+  static_assert(16 * NB + SHIFT <= 32, "mask_blocks: one word per lane");
 #pragma unroll
   for (int b = 0; b < NB; ++b)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) g[b][i] = act[b][i] > 0.f ? g[b][i] : 0.f;
+    for (int i = 0; i < 16; ++i) {
+      // bit -> all ones / all zeros (v_bfe_i32), then an AND: the same +0.0 a select would give, no lane mask
+      const int keep = (int)(word << (31 - (16 * b + i + SHIFT))) >> 31;
+      g[b][i] = __int_as_float(__float_as_int(g[b][i]) & keep);
+    }
 }
 
 struct MlpDims { int N, K0, H, O; };
@@ -233,11 +262,14 @@ struct GlueFwd {
 };
 
 // KQ0 / HQ / OQ: input, hidden and output widths in groups of 8 features (rounded up)
-template <int KQ0, int HQ, int OQ, int NL, bool GLUE = false>
+// KEEP: the sign words are stored.  (A compile-time switch: behind a run-time `if (S1)` the compiler moves the whole
+// gathering of the word into that branch, i.e. out of the MFMA loop it is meant to hide in.)
+template <int KQ0, int HQ, int OQ, int NL, bool GLUE = false, bool KEEP = true>
 __global__ void __launch_bounds__(MLP_BLOCK)
 mlp_forward_kernel(MlpDims d, const float* __restrict__ X, const float* __restrict__ W1,
                    const float* __restrict__ W2, const float* __restrict__ W3, float* __restrict__ Y,
-                   float* __restrict__ A1, float* __restrict__ A2, GlueFwd gf = GlueFwd{}) {
+                   float* __restrict__ A1, float* __restrict__ A2, uint32_t* __restrict__ S1,
+                   uint32_t* __restrict__ S2, GlueFwd gf = GlueFwd{}) {
   extern __shared__ __align__(16) float s_w[];
   constexpr int KB0 = (KQ0 + 3) / 4, HB = (HQ + 3) / 4;
   constexpr int KP0 = KB0 * 32, HP = HB * 32;
@@ -353,14 +385,19 @@ mlp_forward_kernel(MlpDims d, const float* __restrict__ X, const float* __restri
     f32x16 out[1];
     if (NL == 3) {
       f32x16 h2[HB];
-      layer_forward<HQ, HB, HB>(w2, h1, h2, l31, h);
+      uint32_t sw1 = 0, sw2 = 0;
+      layer_forward<HQ, HB, HB, KEEP>(w2, h1, h2, l31, h, &sw1);
+      if constexpr (KEEP) S1[(size_t)tile * 64 + lane] = sw1;
       relu_blocks<HB>(h2);
       if (A2) {
         store_blocks<HB, 8 * HQ>(A2, row, valid, d.H, h, h2);
       }
-      layer_forward<HQ, HB, 1>(w3, h2, out, l31, h);
+      layer_forward<HQ, HB, 1, KEEP>(w3, h2, out, l31, h, &sw2);
+      if constexpr (KEEP) S2[(size_t)tile * 64 + lane] = sw2;
     } else {
-      layer_forward<HQ, HB, 1>(w2, h1, out, l31, h);
+      uint32_t sw1 = 0;
+      layer_forward<HQ, HB, 1, KEEP>(w2, h1, out, l31, h, &sw1);
+      if constexpr (KEEP) S1[(size_t)tile * 64 + lane] = sw1;
     }
     store_block(Y, row, valid, d.O, 0, h, out[0]);
   }
@@ -378,8 +415,8 @@ struct GlueBwd {
 
 template <int KQ0, int HQ, int OQ, int NL, bool GLUE = false>
 __global__ void __launch_bounds__(MLP_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
-mlp_backward_kernel(MlpDims d, const float* __restrict__ dY, const float* __restrict__ A1,
-                    const float* __restrict__ A2, const float* __restrict__ W1, const float* __restrict__ W2,
+mlp_backward_kernel(MlpDims d, const float* __restrict__ dY, const uint32_t* __restrict__ S1,
+                    const uint32_t* __restrict__ S2, const float* __restrict__ W1, const float* __restrict__ W2,
                     const float* __restrict__ W3, float* __restrict__ dZ1, float* __restrict__ dZ2,
                     float* dX, const float* dXadd /* [N,K0] added to the input gradient, may alias dX, or null */,
                     GlueBwd gl = GlueBwd{}) {
@@ -407,44 +444,37 @@ mlp_backward_kernel(MlpDims d, const float* __restrict__ dY, const float* __rest
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
   const int ntiles = (d.N + 31) / 32;
   const int tstride = gridDim.x * 4;
-  // next tile's dY and activations fetched before this tile's products and stores are issued (see mlp_forward_kernel)
-  f32x16 ndy, nact2[NL == 3 ? HB : 1], nact1[HB];
+  // next tile's dY and sign words (18 registers) fetched before this tile's products and stores are issued (see
+  // mlp_forward_kernel)
+  f32x16 ndy;
+  uint32_t ns1 = 0, ns2 = 0;
   auto fetch = [&](int tile) {
     const size_t row = (size_t)tile * 32 + l31;
     const bool valid = row < (size_t)d.N;
     load_block(dY, row, valid, d.O, 0, h, ndy);
-    if constexpr (NL == 3) {
-      load_blocks<HB, 8 * HQ>(A2, row, valid, d.H, h, nact2);
-    }
-    load_blocks<HB, 8 * HQ>(A1, row, valid, d.H, h, nact1);
+    if constexpr (NL == 3) ns2 = S2[(size_t)tile * 64 + lane];
+    ns1 = S1[(size_t)tile * 64 + lane];
   };
-  // (the GLUE variant's epilogue needs the registers: with the prefetch it spills)
-  constexpr bool PREFETCH = !GLUE;
   int tile = blockIdx.x * 4 + wave;
-  if (PREFETCH && tile < ntiles) fetch(tile);
+  if (tile < ntiles) fetch(tile);
   for (; tile < ntiles; tile += tstride) {
     const size_t row = (size_t)tile * 32 + l31;
     const bool valid = row < (size_t)d.N;
-    if (!PREFETCH) fetch(tile);
-    f32x16 dy[1], act2[NL == 3 ? HB : 1], act1[HB];
+    f32x16 dy[1];
     dy[0] = ndy;
-#pragma unroll
-    for (int b = 0; b < HB; ++b) {
-      act1[b] = nact1[b];
-      if constexpr (NL == 3) act2[b] = nact2[b];
-    }
-    if (PREFETCH && tile + tstride < ntiles) fetch(tile + tstride);
+    const uint32_t s1 = ns1, s2 = ns2;
+    if (tile + tstride < ntiles) fetch(tile + tstride);
     f32x16 g1[HB];
     if constexpr (NL == 3) {
       f32x16 g2[HB];
       layer_backward<OQ, 1, HB>(w3, dy, g2, l31, h);
-      mask_blocks<HB>(g2, act2);
+      mask_blocks<HB>(g2, s2);
       store_blocks<HB, 8 * HQ>(dZ2, row, valid, d.H, h, g2);
       layer_backward<HQ, HB, HB>(w2, g2, g1, l31, h);
     } else {
       layer_backward<OQ, 1, HB>(w2, dy, g1, l31, h);
     }
-    mask_blocks<HB>(g1, act1);
+    mask_blocks<HB>(g1, s1);
     store_blocks<HB, 8 * HQ>(dZ1, row, valid, d.H, h, g1);
     if (GLUE) {
       f32x16 gx[KB0];
@@ -542,14 +572,16 @@ size_t mlp2_lds_bytes() {
   return sizeof(float) * (HPA * (KP0 + 1) + 32 * (HPA + 1) + HPB * (KP0 + 1) + 32 * (HPB + 1));
 }
 
-template <int KQ0, int HQA, int OQA, int HQB, int OQB>
+template <int KQ0, int HQA, int OQA, int HQB, int OQB, bool KEEP /* see mlp_forward_kernel */>
 __global__ void __launch_bounds__(MLP_BLOCK)
 mlp2_forward_kernel(Mlp2Dims d, const float* __restrict__ X, const float* __restrict__ WA1,
                     const float* __restrict__ WA2, const float* __restrict__ WB1, const float* __restrict__ WB2,
-                    float* __restrict__ YA, float* __restrict__ YB, float* __restrict__ A1A, float* __restrict__ A1B) {
+                    float* __restrict__ YA, float* __restrict__ YB, float* __restrict__ A1A, float* __restrict__ A1B,
+                    uint32_t* __restrict__ S1) {
   extern __shared__ __align__(16) float s_w[];
   constexpr int KB0 = (KQ0 + 3) / 4, HBA = (HQA + 3) / 4, HBB = (HQB + 3) / 4;
   constexpr int KP0 = KB0 * 32, HPA = HBA * 32, HPB = HBB * 32;
+  static_assert(HBA == 1 && HBB == 1, "mlp2: the two heads' sign bits share one word per lane");
   float* wa1 = s_w;
   float* wa2 = wa1 + HPA * (KP0 + 1);
   float* wb1 = wa2 + 32 * (HPA + 1);
@@ -567,12 +599,13 @@ mlp2_forward_kernel(Mlp2Dims d, const float* __restrict__ X, const float* __rest
     f32x16 in0[KB0];
 #pragma unroll
     for (int b = 0; b < KB0; ++b) load_block(X, row, valid, d.K0, b, h, in0[b]);
+    uint32_t sw = 0;                       // head A's sign bits in the low half, head B's in the high half
     {
       f32x16 h1[HBA], out[1];
       layer_forward<KQ0, KB0, HBA>(wa1, in0, h1, l31, h);
       relu_blocks<HBA>(h1);
       if (A1A) store_blocks<HBA, 8 * HQA>(A1A, row, valid, d.HA, h, h1);      // (null: forward only, nothing kept)
-      layer_forward<HQA, HBA, 1>(wa2, h1, out, l31, h);
+      layer_forward<HQA, HBA, 1, KEEP>(wa2, h1, out, l31, h, &sw);
       store_block(YA, row, valid, d.OA, 0, h, out[0]);
     }
     {
@@ -580,22 +613,24 @@ mlp2_forward_kernel(Mlp2Dims d, const float* __restrict__ X, const float* __rest
       layer_forward<KQ0, KB0, HBB>(wb1, in0, h1, l31, h);
       relu_blocks<HBB>(h1);
       if (A1B) store_blocks<HBB, 8 * HQB>(A1B, row, valid, d.HB, h, h1);
-      layer_forward<HQB, HBB, 1>(wb2, h1, out, l31, h);
+      layer_forward<HQB, HBB, 1, KEEP, 16>(wb2, h1, out, l31, h, &sw);
       store_block(YB, row, valid, d.OB, 0, h, out[0]);
     }
+    if constexpr (KEEP) S1[(size_t)tile * 64 + lane] = sw;
   }
 }
 
 template <int KQ0, int HQA, int OQA, int HQB, int OQB>
 __global__ void __launch_bounds__(MLP_BLOCK)
 mlp2_backward_kernel(Mlp2Dims d, const float* __restrict__ dYA, const float* __restrict__ dYB,
-                     const float* __restrict__ A1A, const float* __restrict__ A1B, const float* __restrict__ WA1,
+                     const uint32_t* S1A, const uint32_t* S1B /* usually one buffer */, const float* __restrict__ WA1,
                      const float* __restrict__ WA2, const float* __restrict__ WB1, const float* __restrict__ WB2,
                      float* __restrict__ dZ1A, float* __restrict__ dZ1B, float* dX,
                      const float* dXadd /* [N,K0] added to the input gradient, may alias dX, or null */) {
   extern __shared__ __align__(16) float s_w[];
   constexpr int KB0 = (KQ0 + 3) / 4, HBA = (HQA + 3) / 4, HBB = (HQB + 3) / 4;
   constexpr int KP0 = KB0 * 32, HPA = HBA * 32, HPB = HBB * 32;
+  static_assert(HBA == 1 && HBB == 1, "mlp2: the two heads' sign bits share one word per lane");
   float* wa1 = s_w;
   float* wa2 = wa1 + HPA * (KP0 + 1);
   float* wb1 = wa2 + 32 * (HPA + 1);
@@ -606,29 +641,45 @@ mlp2_backward_kernel(Mlp2Dims d, const float* __restrict__ dYA, const float* __r
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
   const int ntiles = (d.N + 31) / 32;
-  for (int tile = blockIdx.x * 4 + wave; tile < ntiles; tile += gridDim.x * 4) {
+  const int tstride = gridDim.x * 4;
+  // next tile's dY of both heads and sign words (34 registers) fetched before this tile's products and stores are issued
+  // (see mlp_forward_kernel)
+  f32x16 ndya, ndyb;
+  uint32_t nsa = 0, nsb = 0;
+  auto fetch = [&](int tile) {
     const size_t row = (size_t)tile * 32 + l31;
     const bool valid = row < (size_t)d.N;
+    load_block(dYA, row, valid, d.OA, 0, h, ndya);
+    load_block(dYB, row, valid, d.OB, 0, h, ndyb);
+    nsa = S1A[(size_t)tile * 64 + lane];
+    nsb = S1B[(size_t)tile * 64 + lane];
+  };
+  int tile = blockIdx.x * 4 + wave;
+  if (tile < ntiles) fetch(tile);
+  for (; tile < ntiles; tile += tstride) {
+    const size_t row = (size_t)tile * 32 + l31;
+    const bool valid = row < (size_t)d.N;
+    f32x16 dya[1], dyb[1];
+    dya[0] = ndya;
+    dyb[0] = ndyb;
+    const uint32_t sa = nsa, sb = nsb;
+    if (tile + tstride < ntiles) fetch(tile + tstride);
     f32x16 gx[KB0];
 #pragma unroll
     for (int b = 0; b < KB0; ++b)
 #pragma unroll
       for (int i = 0; i < 16; ++i) gx[b][i] = 0.f;
     {
-      f32x16 dy[1], g1[HBA], act[HBA];
-      load_block(dYA, row, valid, d.OA, 0, h, dy[0]);
-      layer_backward<OQA, 1, HBA>(wa2, dy, g1, l31, h);
-      load_blocks<HBA, 8 * HQA>(A1A, row, valid, d.HA, h, act);
-      mask_blocks<HBA>(g1, act);
+      f32x16 g1[HBA];
+      layer_backward<OQA, 1, HBA>(wa2, dya, g1, l31, h);
+      mask_blocks<HBA>(g1, sa);
       store_blocks<HBA, 8 * HQA>(dZ1A, row, valid, d.HA, h, g1);
       if (dX) layer_backward<HQA, HBA, KB0>(wa1, g1, gx, l31, h);
     }
     {
-      f32x16 dy[1], g1[HBB], act[HBB], gb[KB0];
-      load_block(dYB, row, valid, d.OB, 0, h, dy[0]);
-      layer_backward<OQB, 1, HBB>(wb2, dy, g1, l31, h);
-      load_blocks<HBB, 8 * HQB>(A1B, row, valid, d.HB, h, act);
-      mask_blocks<HBB>(g1, act);
+      f32x16 g1[HBB], gb[KB0];
+      layer_backward<OQB, 1, HBB>(wb2, dyb, g1, l31, h);
+      mask_blocks<HBB, 16>(g1, sb);
       store_blocks<HBB, 8 * HQB>(dZ1B, row, valid, d.HB, h, g1);
       if (dX) {
         layer_backward<HQB, HBB, KB0>(wb1, g1, gb, l31, h);
@@ -878,23 +929,24 @@ size_t mlp_lds_bytes() {
 
 template <int KQ0, int HQ, int OQ, int NL>
 int run_fwd(const MlpDims& d, const float* x, const float* w1, const float* w2, const float* w3, float* y, float* a1,
-            float* a2, hipStream_t s) {
+            float* a2, uint32_t* s1, uint32_t* s2, hipStream_t s) {
   const int ntiles = (d.N + 31) / 32;
   const int blocks = mlp_blocks(ntiles);
   ProfScope p(K_MLP_FWD, s);
-  mlp_forward_kernel<KQ0, HQ, OQ, NL><<<blocks, MLP_BLOCK, mlp_lds_bytes<(KQ0 + 3) / 4, (HQ + 3) / 4, NL>(), s>>>(
-      d, x, w1, w2, w3, y, a1, a2);
+  const size_t lds = mlp_lds_bytes<(KQ0 + 3) / 4, (HQ + 3) / 4, NL>();
+  if (s1) mlp_forward_kernel<KQ0, HQ, OQ, NL, false, true><<<blocks, MLP_BLOCK, lds, s>>>(d, x, w1, w2, w3, y, a1, a2, s1, s2);
+  else mlp_forward_kernel<KQ0, HQ, OQ, NL, false, false><<<blocks, MLP_BLOCK, lds, s>>>(d, x, w1, w2, w3, y, a1, a2, s1, s2);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
 template <int KQ0, int HQ, int OQ, int NL>
-int run_bwd(const MlpDims& d, const float* dy, const float* a1, const float* a2, const float* w1, const float* w2,
+int run_bwd(const MlpDims& d, const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1, const float* w2,
             const float* w3, float* dz1, float* dz2, float* dx, const float* dx_add, hipStream_t s) {
   const int ntiles = (d.N + 31) / 32;
   const int blocks = mlp_blocks(ntiles);
   ProfScope p(K_MLP_BWD, s);
   mlp_backward_kernel<KQ0, HQ, OQ, NL><<<blocks, MLP_BLOCK, mlp_lds_bytes<(KQ0 + 3) / 4, (HQ + 3) / 4, NL>(), s>>>(
-      d, dy, a1, a2, w1, w2, w3, dz1, dz2, dx, dx_add);
+      d, dy, s1, s2, w1, w2, w3, dz1, dz2, dx, dx_add);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
@@ -958,35 +1010,37 @@ using namespace instag;
 extern "C" {
 
 int instag_mlp_forward(const float* x, const float* w1, const float* w2, const float* w3, float* y, float* a1,
-                       float* a2, int32_t N, int32_t K0, int32_t H, int32_t O, int32_t NL, instag_stream_t stream) {
+                       float* a2, uint32_t* s1, uint32_t* s2, int32_t N, int32_t K0, int32_t H, int32_t O, int32_t NL,
+                       instag_stream_t stream) {
   if (int e = check_dims(N, K0, H, O, NL)) return e;
   INSTAG_REQUIRE(x && w1 && w2 && y && (NL == 2 || w3), "mlp_forward: NULL tensor");
+  INSTAG_REQUIRE(NL == 2 || (s1 == nullptr) == (s2 == nullptr), "mlp_forward: s1 and s2 go together");
   if (N == 0) return INSTAG_OK;
   const MlpDims d{N, K0, H, O};
   hipStream_t s = (hipStream_t)stream;
-  MLP_DISPATCH(run_fwd, d, x, w1, w2, w3, y, a1, a2, s);
+  MLP_DISPATCH(run_fwd, d, x, w1, w2, w3, y, a1, a2, s1, s2, s);
   set_error("mlp_forward: unsupported shape");
   return INSTAG_E_ARG;
 }
 
-int instag_mlp_backward_add(const float* dy, const float* a1, const float* a2, const float* w1, const float* w2,
+int instag_mlp_backward_add(const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1, const float* w2,
                             const float* w3, float* dz1, float* dz2, float* dx, const float* dx_add, int32_t N,
                             int32_t K0, int32_t H, int32_t O, int32_t NL, instag_stream_t stream) {
   if (int e = check_dims(N, K0, H, O, NL)) return e;
-  INSTAG_REQUIRE(dy && a1 && w1 && w2 && dz1 && (NL == 2 || (w3 && a2 && dz2)), "mlp_backward: NULL tensor");
+  INSTAG_REQUIRE(dy && s1 && w1 && w2 && dz1 && (NL == 2 || (w3 && s2 && dz2)), "mlp_backward: NULL tensor");
   INSTAG_REQUIRE(dx_add == nullptr || dx != nullptr, "mlp_backward: dx_add needs dx");
   if (N == 0) return INSTAG_OK;
   const MlpDims d{N, K0, H, O};
   hipStream_t s = (hipStream_t)stream;
-  MLP_DISPATCH(run_bwd, d, dy, a1, a2, w1, w2, w3, dz1, dz2, dx, dx_add, s);
+  MLP_DISPATCH(run_bwd, d, dy, s1, s2, w1, w2, w3, dz1, dz2, dx, dx_add, s);
   set_error("mlp_backward: unsupported shape");
   return INSTAG_E_ARG;
 }
 
-int instag_mlp_backward(const float* dy, const float* a1, const float* a2, const float* w1, const float* w2,
+int instag_mlp_backward(const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1, const float* w2,
                         const float* w3, float* dz1, float* dz2, float* dx, int32_t N, int32_t K0, int32_t H,
                         int32_t O, int32_t NL, instag_stream_t stream) {
-  return instag_mlp_backward_add(dy, a1, a2, w1, w2, w3, dz1, dz2, dx, nullptr, N, K0, H, O, NL, stream);
+  return instag_mlp_backward_add(dy, s1, s2, w1, w2, w3, dz1, dz2, dx, nullptr, N, K0, H, O, NL, stream);
 }
 
 /* sigma_net's backward with the glue operator's backward as its epilogue (universal field: K0 = 36 + 32 + 6, H = 64 or 32,
@@ -1001,14 +1055,14 @@ int instag_mlp_backward_glue_supported(int32_t K0, int32_t H, int32_t O, int32_t
 
 int instag_mlp_backward_glue_num_partials(int32_t N) { return mlp_blocks((N + 31) / 32); }
 
-int instag_mlp_backward_glue(const float* dy, const float* a1, const float* a2, const float* w1, const float* w2,
+int instag_mlp_backward_glue(const float* dy, const uint32_t* s1, const uint32_t* s2, const float* w1, const float* w2,
                              const float* w3, float* dz1, float* dz2, const float* aud, const float* eye_pre,
                              const float* enc_a, const float* enc_e, const float* amb, const float* d_amb,
                              float* d_enc_x, float* d_aud, float* d_eye_pre, float* col_partials, int32_t N,
                              int32_t H, int32_t O, instag_stream_t stream) {
   const int K0 = GLUE_KX + GLUE_KA + GLUE_KE;
   INSTAG_REQUIRE(instag_mlp_backward_glue_supported(K0, H, O, GLUE_KX, GLUE_KA, GLUE_KE), "mlp_backward_glue: unsupported shape");
-  INSTAG_REQUIRE(dy && a1 && a2 && w1 && w2 && w3 && dz1 && dz2 && aud && eye_pre && enc_a && enc_e && amb && d_enc_x &&
+  INSTAG_REQUIRE(dy && s1 && s2 && w1 && w2 && w3 && dz1 && dz2 && aud && eye_pre && enc_a && enc_e && amb && d_enc_x &&
                      d_aud && d_eye_pre && col_partials, "mlp_backward_glue: NULL tensor");
   if (N <= 0) return INSTAG_OK;
   const MlpDims d{N, K0, H, O};
@@ -1018,24 +1072,25 @@ int instag_mlp_backward_glue(const float* dy, const float* a1, const float* a2, 
   ProfScope p(K_MLP_BWD, s);
   if ((H + 7) / 8 == 8)
     mlp_backward_kernel<10, 8, 2, 3, true><<<blocks, MLP_BLOCK, mlp_lds_bytes<3, 2, 3>(), s>>>(
-        d, dy, a1, a2, w1, w2, w3, dz1, dz2, nullptr, nullptr, gl);
+        d, dy, s1, s2, w1, w2, w3, dz1, dz2, nullptr, nullptr, gl);
   else
     mlp_backward_kernel<10, 4, 2, 3, true><<<blocks, MLP_BLOCK, mlp_lds_bytes<3, 1, 3>(), s>>>(
-        d, dy, a1, a2, w1, w2, w3, dz1, dz2, nullptr, nullptr, gl);
+        d, dy, s1, s2, w1, w2, w3, dz1, dz2, nullptr, nullptr, gl);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
 
 /* sigma_net's forward with the glue operator's forward in front of its first layer (same shapes as
  * instag_mlp_backward_glue): reads enc_x [N,36], aud [N,32], eye_pre [N,6], enc_a [32], enc_e [6]; writes y [N,O], the
- * saved activations a1, a2 [N,H], the assembled input h_in [N,74] and amb [N,3]. */
+ * saved activations a1, a2 [N,H] with their sign words s1, s2, the assembled input h_in [N,74] and amb [N,3]. */
 int instag_mlp_forward_glue(const float* enc_x, const float* aud, const float* eye_pre, const float* enc_a,
                             const float* enc_e, const float* w1, const float* w2, const float* w3, float* y, float* a1,
-                            float* a2, float* h_in, float* amb, int32_t N, int32_t H, int32_t O,
-                            instag_stream_t stream) {
+                            float* a2, uint32_t* s1, uint32_t* s2, float* h_in, float* amb, int32_t N, int32_t H,
+                            int32_t O, instag_stream_t stream) {
   const int K0 = GLUE_KX + GLUE_KA + GLUE_KE;
   INSTAG_REQUIRE(instag_mlp_backward_glue_supported(K0, H, O, GLUE_KX, GLUE_KA, GLUE_KE), "mlp_forward_glue: unsupported shape");
   INSTAG_REQUIRE(enc_x && aud && eye_pre && enc_a && enc_e && w1 && w2 && w3 && y && amb, "mlp_forward_glue: NULL tensor");
+  INSTAG_REQUIRE((s1 == nullptr) == (s2 == nullptr), "mlp_forward_glue: s1 and s2 go together");
   INSTAG_REQUIRE((a1 == nullptr) == (a2 == nullptr) && (h_in == nullptr || a1 != nullptr),
                  "mlp_forward_glue: a1 and a2 go together (NULL: forward only); h_in (may be NULL: the caller's weight "
                  "gradient assembles the rows itself, instag_linear_weight_grad_batched_glue) needs them");
@@ -1045,12 +1100,11 @@ int instag_mlp_forward_glue(const float* enc_x, const float* aud, const float* e
   hipStream_t s = (hipStream_t)stream;
   const int blocks = mlp_blocks((N + 31) / 32);
   ProfScope p(K_MLP_FWD, s);
-  if ((H + 7) / 8 == 8)
-    mlp_forward_kernel<10, 8, 2, 3, true><<<blocks, MLP_BLOCK, mlp_lds_bytes<3, 2, 3>(), s>>>(
-        d, nullptr, w1, w2, w3, y, a1, a2, gf);
-  else
-    mlp_forward_kernel<10, 4, 2, 3, true><<<blocks, MLP_BLOCK, mlp_lds_bytes<3, 1, 3>(), s>>>(
-        d, nullptr, w1, w2, w3, y, a1, a2, gf);
+  const bool wide = (H + 7) / 8 == 8;
+  const size_t lds = wide ? mlp_lds_bytes<3, 2, 3>() : mlp_lds_bytes<3, 1, 3>();
+  auto kernel = wide ? (s1 ? mlp_forward_kernel<10, 8, 2, 3, true, true> : mlp_forward_kernel<10, 8, 2, 3, true, false>)
+                     : (s1 ? mlp_forward_kernel<10, 4, 2, 3, true, true> : mlp_forward_kernel<10, 4, 2, 3, true, false>);
+  kernel<<<blocks, MLP_BLOCK, lds, s>>>(d, nullptr, w1, w2, w3, y, a1, a2, s1, s2, gf);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
@@ -1064,8 +1118,8 @@ int instag_mlp2_supported(int32_t K0, int32_t HA, int32_t OA, int32_t HB, int32_
 }
 
 int instag_mlp2_forward(const float* x, const float* wa1, const float* wa2, const float* wb1, const float* wb2,
-                        float* ya, float* yb, float* a1a, float* a1b, int32_t N, int32_t K0, int32_t HA, int32_t OA,
-                        int32_t HB, int32_t OB, instag_stream_t stream) {
+                        float* ya, float* yb, float* a1a, float* a1b, uint32_t* s1, int32_t N, int32_t K0, int32_t HA,
+                        int32_t OA, int32_t HB, int32_t OB, instag_stream_t stream) {
   INSTAG_REQUIRE(instag_mlp2_supported(K0, HA, OA, HB, OB), "mlp2_forward: unsupported shape pair");
   INSTAG_REQUIRE(x && wa1 && wa2 && wb1 && wb2 && ya && yb, "mlp2_forward: NULL tensor");
   INSTAG_REQUIRE((a1a == nullptr) == (a1b == nullptr), "mlp2_forward: a1a and a1b go together (both NULL: forward only)");
@@ -1073,25 +1127,25 @@ int instag_mlp2_forward(const float* x, const float* wa1, const float* wa2, cons
   const Mlp2Dims d{N, K0, HA, OA, HB, OB};
   hipStream_t s = (hipStream_t)stream;
   ProfScope p(K_MLP_FWD, s);
-  mlp2_forward_kernel<5, 4, 4, 2, 1><<<mlp_blocks((N + 31) / 32), MLP_BLOCK, mlp2_lds_bytes<5, 4, 2>(), s>>>(
-      d, x, wa1, wa2, wb1, wb2, ya, yb, a1a, a1b);
+  auto kernel = s1 ? mlp2_forward_kernel<5, 4, 4, 2, 1, true> : mlp2_forward_kernel<5, 4, 4, 2, 1, false>;
+  kernel<<<mlp_blocks((N + 31) / 32), MLP_BLOCK, mlp2_lds_bytes<5, 4, 2>(), s>>>(d, x, wa1, wa2, wb1, wb2, ya, yb, a1a, a1b, s1);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
 
-int instag_mlp2_backward(const float* dya, const float* dyb, const float* a1a, const float* a1b, const float* wa1,
+int instag_mlp2_backward(const float* dya, const float* dyb, const uint32_t* s1a, const uint32_t* s1b, const float* wa1,
                          const float* wa2, const float* wb1, const float* wb2, float* dz1a, float* dz1b, float* dx,
                          const float* dx_add, int32_t N, int32_t K0, int32_t HA, int32_t OA, int32_t HB, int32_t OB,
                          instag_stream_t stream) {
   INSTAG_REQUIRE(instag_mlp2_supported(K0, HA, OA, HB, OB), "mlp2_backward: unsupported shape pair");
-  INSTAG_REQUIRE(dya && dyb && a1a && a1b && wa1 && wa2 && wb1 && wb2 && dz1a && dz1b, "mlp2_backward: NULL tensor");
+  INSTAG_REQUIRE(dya && dyb && s1a && s1b && wa1 && wa2 && wb1 && wb2 && dz1a && dz1b, "mlp2_backward: NULL tensor");
   INSTAG_REQUIRE(dx_add == nullptr || dx != nullptr, "mlp2_backward: dx_add needs dx");
   if (N <= 0) return INSTAG_OK;
   const Mlp2Dims d{N, K0, HA, OA, HB, OB};
   hipStream_t s = (hipStream_t)stream;
   ProfScope p(K_MLP_BWD, s);
   mlp2_backward_kernel<5, 4, 4, 2, 1><<<mlp_blocks((N + 31) / 32), MLP_BLOCK, mlp2_lds_bytes<5, 4, 2>(), s>>>(
-      d, dya, dyb, a1a, a1b, wa1, wa2, wb1, wb2, dz1a, dz1b, dx, dx_add);
+      d, dya, dyb, s1a, s1b, wa1, wa2, wb1, wb2, dz1a, dz1b, dx, dx_add);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }

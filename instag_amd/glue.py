@@ -99,12 +99,14 @@ class _GlueSigma(torch.autograd.Function):
         y = torch.empty(N, O, dtype=torch.float32, device=dev)
         a1 = torch.empty(N, H, dtype=torch.float32, device=dev) if keep else None
         a2 = torch.empty(N, H, dtype=torch.float32, device=dev) if keep else None
+        s1 = _mlp.sign_words(N, dev) if keep else None
+        s2 = _mlp.sign_words(N, dev) if keep else None
         check(L.instag_mlp_forward_glue(ptr(enc_x), ptr(aud), ptr(eye_pre), ptr(enc_a), ptr(enc_e), ptr(w1c), ptr(w2c),
-                                        ptr(w3c), ptr(y), ptr(a1), ptr(a2), ptr(h_in), ptr(amb), N, H, O, stream),
-              "mlp_forward_glue")
+                                        ptr(w3c), ptr(y), ptr(a1), ptr(a2), ptr(s1), ptr(s2), ptr(h_in), ptr(amb), N, H,
+                                        O, stream), "mlp_forward_glue")
         _mlp.STATS["fwd_flops"] += 2 * N * (K0 * H + H * H + H * O)
         ctx.save_for_backward(aud, eye_pre, enc_a, enc_e, amb, h_in if h_in is not None or not keep else enc_x, w1c,
-                              w2c, w3c, a1, a2)
+                              w2c, w3c, a1, a2, s1, s2)
         ctx.virtual = keep and h_in is None
         ctx.weights = (w1, w2, w3)
         ctx.dims = (N, KX, KA, KE, H, O)
@@ -118,7 +120,7 @@ class _GlueSigma(torch.autograd.Function):
         if d_amb is not None:
             from . import diff_gauss
             diff_gauss.join_pending_aux()        # (see _MotionGlue.backward)
-        aud, eye_pre, enc_a, enc_e, amb, h_in, w1, w2, w3, a1, a2 = ctx.saved_tensors
+        aud, eye_pre, enc_a, enc_e, amb, h_in, w1, w2, w3, a1, a2, s1, s2 = ctx.saved_tensors
         N, KX, KA, KE, H, O = ctx.dims
         dev = aud.device
         dy = torch.zeros(N, O, dtype=torch.float32, device=dev) if dy is None else _c(dy)
@@ -129,7 +131,7 @@ class _GlueSigma(torch.autograd.Function):
         d_aud = torch.empty(N, KA, dtype=torch.float32, device=dev)
         d_eye = torch.empty(N, KE, dtype=torch.float32, device=dev)
         parts = torch.empty(L.instag_mlp_backward_glue_num_partials(N), KA + KE, dtype=torch.float32, device=dev)
-        check(L.instag_mlp_backward_glue(ptr(dy), ptr(a1), ptr(a2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2),
+        check(L.instag_mlp_backward_glue(ptr(dy), ptr(s1), ptr(s2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2),
                                          ptr(aud), ptr(eye_pre), ptr(enc_a), ptr(enc_e), ptr(amb), ptr(d_amb),
                                          ptr(d_enc_x), ptr(d_aud), ptr(d_eye), ptr(parts), N, H, O,
                                          _lib.current_stream()), "mlp_backward_glue")

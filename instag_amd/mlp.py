@@ -20,6 +20,12 @@ def supported(dim_in, dim_hidden, dim_out, num_layers) -> bool:
     return num_layers in (2, 3) and 1 <= dim_in <= 96 and 1 <= dim_hidden <= 64 and 1 <= dim_out <= 32
 
 
+def sign_words(N, dev):
+    """One ReLU sign word per lane and 32-row tile of a hidden layer, [ceil(N/32), 64] (include/instag_hip.h): what the
+    backward kernels read in place of the activations."""
+    return torch.empty((N + 31) // 32, 64, dtype=torch.int32, device=dev)
+
+
 def _weight_grad(L, dz, inp, dw, ws):
     N, (O, K) = dz.shape[0], dw.shape
     check(L.instag_linear_weight_grad(ptr(dz), ptr(inp), ptr(dw), ptr(ws), ws.numel(), N, O, K,
@@ -41,9 +47,11 @@ class _FusedMLP(torch.autograd.Function):
         need = any(ctx.needs_input_grad)
         a1 = torch.empty(N, H, dtype=torch.float32, device=x.device) if need else None
         a2 = torch.empty(N, H, dtype=torch.float32, device=x.device) if (need and NL == 3) else None
-        check(L.instag_mlp_forward(ptr(x), ptr(w1c), ptr(w2c), ptr(w3c), ptr(y), ptr(a1), ptr(a2), N, K0, H, O, NL,
-                                   _lib.current_stream()), "mlp_forward")
-        ctx.save_for_backward(x, w1c, w2c, w3c, a1, a2)
+        s1 = sign_words(N, x.device) if need else None
+        s2 = sign_words(N, x.device) if (need and NL == 3) else None
+        check(L.instag_mlp_forward(ptr(x), ptr(w1c), ptr(w2c), ptr(w3c), ptr(y), ptr(a1), ptr(a2), ptr(s1), ptr(s2),
+                                   N, K0, H, O, NL, _lib.current_stream()), "mlp_forward")
+        ctx.save_for_backward(x, w1c, w2c, w3c, a1, a2, s1, s2)
         ctx.weights = (w1, w2, w3)          # the caller's tensors (leaf parameters in the deferred-gradient mode)
         ctx.dims = (N, K0, H, O, NL)
         STATS["fwd_flops"] += 2 * N * (K0 * H + (H * H if NL == 3 else 0) + H * O)
@@ -52,7 +60,7 @@ class _FusedMLP(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
-        x, w1, w2, w3, a1, a2 = ctx.saved_tensors
+        x, w1, w2, w3, a1, a2, s1, s2 = ctx.saved_tensors
         N, K0, H, O, NL = ctx.dims
         dy = dy.contiguous().float()
         stream = _lib.current_stream()
@@ -60,7 +68,7 @@ class _FusedMLP(torch.autograd.Function):
         dz1 = torch.empty(N, H, dtype=torch.float32, device=dev)
         dz2 = torch.empty(N, H, dtype=torch.float32, device=dev) if NL == 3 else None
         dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        check(L.instag_mlp_backward(ptr(dy), ptr(a1), ptr(a2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2), ptr(dx),
+        check(L.instag_mlp_backward(ptr(dy), ptr(s1), ptr(s2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2), ptr(dx),
                                     N, K0, H, O, NL, stream), "mlp_backward")
         STATS["bwd_flops"] += 2 * N * (H * O + (H * H if NL == 3 else 0) + (K0 * H if dx is not None else 0))
         # weight gradients: only the optimizer reads them.  Inside a ``deferred_grads`` block (instag_amd/deferred.py)
@@ -125,11 +133,12 @@ class _SharedInputMLPs(torch.autograd.Function):
             keep = any(ctx.needs_input_grad)          # forward only (inference, the jaw feature): nothing is kept
             a1a = torch.empty(N, HA, dtype=torch.float32, device=x.device) if keep else None
             a1b = torch.empty(N, HB, dtype=torch.float32, device=x.device) if keep else None
+            s1 = sign_words(N, x.device) if keep else None          # both heads' bits: A low half, B high half
             check(L.instag_mlp2_forward(ptr(x), ptr(ws[0]), ptr(ws[1]), ptr(ws[2]), ptr(ws[3]), ptr(ya), ptr(yb),
-                                        ptr(a1a), ptr(a1b), N, K0, HA, OA, HB, OB, _lib.current_stream()),
+                                        ptr(a1a), ptr(a1b), ptr(s1), N, K0, HA, OA, HB, OB, _lib.current_stream()),
                   "mlp2_forward")
             STATS["fwd_flops"] += 2 * N * (K0 * HA + HA * OA + K0 * HB + HB * OB)
-            ctx.save_for_backward(x, ws[0], ws[1], a1a, ws[2], ws[3], a1b)
+            ctx.save_for_backward(x, ws[0], ws[1], a1a, s1, ws[2], ws[3], a1b, s1)
             ctx.weights = (wa1, wa2, wb1, wb2)
             ctx.dims = (N, K0, [(HA, OA), (HB, OB)])
             ctx.fused = True
@@ -140,11 +149,12 @@ class _SharedInputMLPs(torch.autograd.Function):
             H, O = w1c.shape[0], w2c.shape[0]
             y = torch.empty(N, O, dtype=torch.float32, device=x.device)
             a1 = torch.empty(N, H, dtype=torch.float32, device=x.device)
-            check(L.instag_mlp_forward(ptr(x), ptr(w1c), ptr(w2c), None, ptr(y), ptr(a1), None, N, K0, H, O, 2,
-                                       _lib.current_stream()), "mlp_forward")
+            s1 = sign_words(N, x.device)
+            check(L.instag_mlp_forward(ptr(x), ptr(w1c), ptr(w2c), None, ptr(y), ptr(a1), None, ptr(s1), None, N, K0, H,
+                                       O, 2, _lib.current_stream()), "mlp_forward")
             STATS["fwd_flops"] += 2 * N * (K0 * H + H * O)
             outs.append(y)
-            saved += [w1c, w2c, a1]
+            saved += [w1c, w2c, a1, s1]
             dims.append((H, O))
         ctx.save_for_backward(*saved)
         ctx.weights = (wa1, wa2, wb1, wb2)
@@ -165,12 +175,12 @@ class _SharedInputMLPs(torch.autograd.Function):
         jobs = []
         fused = ctx.fused and dya is not None and dyb is not None
         if fused:
-            wa1, wa2, a1a, wb1, wb2, a1b = ctx.saved_tensors[1:7]
+            wa1, wa2, a1a, s1, wb1, wb2, a1b = ctx.saved_tensors[1:8]
             (HA, OA), (HB, OB) = dims
             dya, dyb = dya.contiguous().float(), dyb.contiguous().float()
             dz1a = torch.empty(N, HA, dtype=torch.float32, device=dev)
             dz1b = torch.empty(N, HB, dtype=torch.float32, device=dev)
-            check(L.instag_mlp2_backward(ptr(dya), ptr(dyb), ptr(a1a), ptr(a1b), ptr(wa1), ptr(wa2), ptr(wb1),
+            check(L.instag_mlp2_backward(ptr(dya), ptr(dyb), ptr(s1), ptr(s1), ptr(wa1), ptr(wa2), ptr(wb1),
                                          ptr(wb2), ptr(dz1a), ptr(dz1b), ptr(dx), ptr(add) if want_dx else None,
                                          N, K0, HA, OA, HB, OB, stream), "mlp2_backward")
             STATS["bwd_flops"] += 2 * N * (HA * OA + HB * OB + (K0 * (HA + HB) if want_dx else 0))
@@ -179,11 +189,13 @@ class _SharedInputMLPs(torch.autograd.Function):
         for k, dy in enumerate(() if fused else (dya, dyb)):
             if dy is None:
                 continue
-            w1, w2, a1 = ctx.saved_tensors[1 + 3 * k:4 + 3 * k]
+            w1, w2, a1, s1 = ctx.saved_tensors[1 + 4 * k:5 + 4 * k]
+            if ctx.fused and k == 1:
+                s1 = s1 >> 16                 # the fused forward packed head B's bits into the high half
             H, O = dims[k]
             dy = dy.contiguous().float()
             dz1 = torch.empty(N, H, dtype=torch.float32, device=dev)
-            check(L.instag_mlp_backward_add(ptr(dy), ptr(a1), None, ptr(w1), ptr(w2), None, ptr(dz1), None, ptr(dx),
+            check(L.instag_mlp_backward_add(ptr(dy), ptr(s1), None, ptr(w1), ptr(w2), None, ptr(dz1), None, ptr(dx),
                                             ptr(add) if want_dx else None, N, K0, H, O, 2, stream), "mlp_backward")
             STATS["bwd_flops"] += 2 * N * (H * O + (K0 * H if want_dx else 0))
             if want_dx:

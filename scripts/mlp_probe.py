@@ -17,9 +17,12 @@ def t_fwd(N, store, iters=60):
     y = torch.empty(N, O, device=dev)
     a1 = torch.empty(N, H, device=dev) if store else None
     a2 = torch.empty(N, H, device=dev) if store else None
+    s1 = torch.empty((N + 31) // 32, 64, dtype=torch.int32, device=dev) if store else None
+    s2 = torch.empty((N + 31) // 32, 64, dtype=torch.int32, device=dev) if store else None
     s = _lib.current_stream()
     def run():
-        check(L.instag_mlp_forward(ptr(x), ptr(w1), ptr(w2), ptr(w3), ptr(y), ptr(a1), ptr(a2), N, K0, H, O, NL, s), "f")
+        check(L.instag_mlp_forward(ptr(x), ptr(w1), ptr(w2), ptr(w3), ptr(y), ptr(a1), ptr(a2), ptr(s1), ptr(s2), N, K0, H,
+                                   O, NL, s), "f")
     for _ in range(10):
         run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -34,11 +37,12 @@ def t_fwd(N, store, iters=60):
 
 def t_bwd(N, iters=60):
     dy = torch.randn(N, O, device=dev)
-    a1, a2 = torch.randn(N, H, device=dev), torch.randn(N, H, device=dev)
+    # ReLU sign words (include/instag_hip.h): random bits stand in for a forward's
+    s1, s2 = (torch.randint(-2**31, 2**31, ((N + 31) // 32, 64), device=dev).to(torch.int32) for _ in range(2))
     dz1, dz2, dx = torch.empty(N, H, device=dev), torch.empty(N, H, device=dev), torch.empty(N, K0, device=dev)
     s = _lib.current_stream()
     def run():
-        check(L.instag_mlp_backward_add(ptr(dy), ptr(a1), ptr(a2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2),
+        check(L.instag_mlp_backward_add(ptr(dy), ptr(s1), ptr(s2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2),
                                         ptr(dx), None, N, K0, H, O, NL, s), "b")
     for _ in range(10):
         run()
