@@ -303,8 +303,10 @@ int instag_debug_scan_stall_probe(instag_stream_t stream);
  * backward consumes dy [N,O] and the sign words (one bit of every activation is all it needs) and writes
  * the pre-activation gradients dz1 [N,H] (dz2 [N,H]) and, when dx != NULL, dx [N,K0]; the weight gradients are then
  *     dW_1 = dz1^T x,  dW_2 = dz2^T a1 (NL==3) or dy^T a1 (NL==2),  dW_3 = dy^T a2
- * each computed with instag_linear_weight_grad (dz [N,O], in [N,K] -> dw [O,K]; O <= 64, K <= 96;
- * workspace of instag_linear_weight_grad_workspace_bytes; deterministic).
+ * each one job (dz [N,O], in [N,K] -> dw [O,K]; O <= 64, K <= 96; deterministic) of
+ * instag_linear_weight_grad_batched, which computes all of an MLP's, or of several MLPs', in one launch;
+ * instag_linear_weight_grad is that call with a single job (workspace of
+ * instag_linear_weight_grad_workspace_bytes).
  * ------------------------------------------------------------------------------------------ */
 int instag_mlp_forward(const float* x, const float* w1, const float* w2, const float* w3, float* y,
                        float* a1, float* a2, uint32_t* s1, uint32_t* s2, int32_t N, int32_t K0, int32_t H,
@@ -358,8 +360,9 @@ size_t instag_linear_weight_grad_workspace_bytes(int32_t N, int32_t O, int32_t K
 int instag_linear_weight_grad(const float* dz, const float* in, float* dw, void* workspace,
                               size_t workspace_bytes, int32_t N, int32_t O, int32_t K,
                               instag_stream_t stream);
-/* Several weight gradients in one launch (all with the same N): workspace = sum over jobs of
- * instag_linear_weight_grad_workspace_bytes rounded up to 256 B.  At most 16 jobs. */
+/* Several weight gradients in one launch (all with the same N).  Each job's partial sums start on a 256-byte boundary
+ * of the workspace: it holds instag_linear_weight_grad_workspace_bytes per job, rounded up to 256 B for every job but
+ * the last (rounding the last one up too is fine).  At most 16 jobs. */
 typedef struct {
   const float* dz; /* [N,O] */
   const float* inp; /* [N,K] */

@@ -828,14 +828,6 @@ __device__ __forceinline__ void weight_grad_body(const float* __restrict__ dZ, c
   }
 }
 
-template <int OB, int KB>
-__global__ void __launch_bounds__(MLP_BLOCK)
-weight_grad_kernel(const float* __restrict__ dZ, const float* __restrict__ In, int N, int O, int K,
-                   float* __restrict__ partial) {
-  __shared__ float s_acc[(OB * KB < 4 ? OB * KB : 1) * 1024];
-  weight_grad_body<OB, KB>(dZ, In, N, O, K, partial, s_acc, blockIdx.x, gridDim.x);
-}
-
 // Several weight-gradient GEMMs in ONE launch (blockIdx.y = job): a train step has nine of them (three MLPs of the
 // universal field, one of the personalised field), each too small to fill the chip on its own and none needed before
 // the optimizer runs.
@@ -865,6 +857,7 @@ weight_grad_batched_kernel(WgBatch b) {
   else weight_grad_body<2, 3>(job.dz, job.in, job.N, job.O, job.K, job.partial, s_acc, blockIdx.x, gridDim.x);
 }
 
+// dW[i] = sum_p partial[p][i] of job blockIdx.y: 64 elements x 4 partial-groups per workgroup, fixed summation order
 __global__ void __launch_bounds__(256)
 weight_grad_reduce_batched_kernel(WgBatch b, int nparts) {
   __shared__ float s_part[4][64];
@@ -883,24 +876,6 @@ weight_grad_reduce_batched_kernel(WgBatch b, int nparts) {
   s_part[g][e] = s;
   __syncthreads();
   if (g == 0 && i < count) job.dw[i] = ((s_part[0][e] + s_part[1][e]) + s_part[2][e]) + s_part[3][e];
-}
-
-// dW[i] = sum_p partial[p][i]: 64 elements x 4 partial-groups per workgroup, fixed summation order
-__global__ void __launch_bounds__(256)
-weight_grad_reduce_kernel(const float* __restrict__ partial, int nparts, int count, float* __restrict__ dW) {
-  __shared__ float s_part[4][64];
-  const int e = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + e;
-  float s = 0.f;
-  if (i < count) {
-    const int per = (nparts + 3) / 4;
-    const int p0 = g * per, p1 = min(nparts, p0 + per);
-#pragma unroll 8
-    for (int p = p0; p < p1; ++p) s += partial[(size_t)p * count + i];
-  }
-  s_part[g][e] = s;
-  __syncthreads();
-  if (g == 0 && i < count) dW[i] = ((s_part[0][e] + s_part[1][e]) + s_part[2][e]) + s_part[3][e];
 }
 
 // (256 workgroups per GEMM is the measured optimum, round 2: 128 -> +33 % per GEMM, 512 -> +5 %; round 3 in the step:
@@ -947,16 +922,6 @@ int run_bwd(const MlpDims& d, const float* dy, const uint32_t* s1, const uint32_
   ProfScope p(K_MLP_BWD, s);
   mlp_backward_kernel<KQ0, HQ, OQ, NL><<<blocks, MLP_BLOCK, mlp_lds_bytes<(KQ0 + 3) / 4, (HQ + 3) / 4, NL>(), s>>>(
       d, dy, s1, s2, w1, w2, w3, dz1, dz2, dx, dx_add);
-  INSTAG_CHECK_LAUNCH();
-  return INSTAG_OK;
-}
-template <int OB, int KB>
-int run_wg(const float* dz, const float* in, int N, int O, int K, float* partial, float* dw, hipStream_t s) {
-  const int blocks = wg_blocks(N);
-  ProfScope p(K_MLP_WGRAD, s);
-  weight_grad_kernel<OB, KB><<<blocks, MLP_BLOCK, 0, s>>>(dz, in, N, O, K, partial);
-  INSTAG_CHECK_LAUNCH();
-  weight_grad_reduce_kernel<<<(O * K + 63) / 64, 256, 0, s>>>(partial, blocks, O * K, dw);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
@@ -1154,32 +1119,12 @@ size_t instag_linear_weight_grad_workspace_bytes(int32_t N, int32_t O, int32_t K
   return (size_t)wg_blocks(N) * (size_t)O * (size_t)K * sizeof(float);
 }
 
-int instag_linear_weight_grad(const float* dz, const float* in, float* dw, void* workspace, size_t workspace_bytes,
-                              int32_t N, int32_t O, int32_t K, instag_stream_t stream) {
-  INSTAG_REQUIRE(dz && in && dw, "linear_weight_grad: NULL tensor");
-  INSTAG_REQUIRE(O >= 1 && O <= 64 && K >= 1 && K <= 96, "linear_weight_grad: need O <= 64 and K <= 96");
-  INSTAG_REQUIRE(N >= 1, "linear_weight_grad: N must be >= 1");
-  if (workspace == nullptr || workspace_bytes < instag_linear_weight_grad_workspace_bytes(N, O, K)) {
-    set_error("linear_weight_grad: workspace too small");
-    return INSTAG_E_SPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  const int ob = (O + 31) / 32, kb = (K + 31) / 32;
-  if (ob == 1 && kb == 1) return run_wg<1, 1>(dz, in, N, O, K, part, dw, s);
-  if (ob == 1 && kb == 2) return run_wg<1, 2>(dz, in, N, O, K, part, dw, s);
-  if (ob == 1 && kb == 3) return run_wg<1, 3>(dz, in, N, O, K, part, dw, s);
-  if (ob == 2 && kb == 1) return run_wg<2, 1>(dz, in, N, O, K, part, dw, s);
-  if (ob == 2 && kb == 2) return run_wg<2, 2>(dz, in, N, O, K, part, dw, s);
-  return run_wg<2, 3>(dz, in, N, O, K, part, dw, s);
-}
-
 static int weight_grad_batched_impl(const instag_wgrad_job* jobs, int32_t n_jobs, const WgVirt& virt, void* workspace,
                                    size_t workspace_bytes, instag_stream_t stream) {
   INSTAG_REQUIRE(jobs && n_jobs >= 1 && n_jobs <= WG_MAX_JOBS, "linear_weight_grad_batched: 1..16 jobs");
   WgBatch b;
   b.virt = virt;
-  size_t off = 0;
+  size_t off = 0, end = 0;                    // partials start on 256-byte boundaries; nothing is needed behind the last
   int N0 = jobs[0].N, max_count = 0;
   for (int i = 0; i < n_jobs; ++i) {
     const instag_wgrad_job& q = jobs[i];
@@ -1187,10 +1132,11 @@ static int weight_grad_batched_impl(const instag_wgrad_job* jobs, int32_t n_jobs
     INSTAG_REQUIRE(q.O >= 1 && q.O <= 64 && q.K >= 1 && q.K <= 96, "linear_weight_grad: need O <= 64 and K <= 96");
     INSTAG_REQUIRE(q.N == N0 && q.N >= 1, "linear_weight_grad_batched: all jobs must have the same N >= 1");
     b.j[i] = WgJob{q.dz, q.inp, (float*)((char*)workspace + off), q.dw, q.N, q.O, q.K, 0};
-    off += (instag_linear_weight_grad_workspace_bytes(q.N, q.O, q.K) + 255) / 256 * 256;
+    end = off + instag_linear_weight_grad_workspace_bytes(q.N, q.O, q.K);
+    off = (end + 255) / 256 * 256;
     max_count = std::max(max_count, q.O * q.K);
   }
-  if (workspace == nullptr || workspace_bytes < off) {
+  if (workspace == nullptr || workspace_bytes < end) {
     set_error("linear_weight_grad_batched: workspace too small");
     return INSTAG_E_SPACE;
   }
@@ -1208,6 +1154,20 @@ int instag_linear_weight_grad_batched(const instag_wgrad_job* jobs, int32_t n_jo
                                       size_t workspace_bytes, instag_stream_t stream) {
   return weight_grad_batched_impl(jobs, n_jobs, WgVirt{-1, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0}, workspace,
                                   workspace_bytes, stream);
+}
+
+// one job is a batch of one
+int instag_linear_weight_grad(const float* dz, const float* in, float* dw, void* workspace, size_t workspace_bytes,
+                              int32_t N, int32_t O, int32_t K, instag_stream_t stream) {
+  INSTAG_REQUIRE(dz && in && dw, "linear_weight_grad: NULL tensor");
+  INSTAG_REQUIRE(O >= 1 && O <= 64 && K >= 1 && K <= 96, "linear_weight_grad: need O <= 64 and K <= 96");
+  INSTAG_REQUIRE(N >= 1, "linear_weight_grad: N must be >= 1");
+  if (workspace == nullptr || workspace_bytes < instag_linear_weight_grad_workspace_bytes(N, O, K)) {
+    set_error("linear_weight_grad: workspace too small");
+    return INSTAG_E_SPACE;
+  }
+  const instag_wgrad_job job{dz, in, dw, N, O, K};
+  return instag_linear_weight_grad_batched(&job, 1, workspace, workspace_bytes, stream);
 }
 
 int instag_linear_weight_grad_batched_glue(const instag_wgrad_job* jobs, int32_t n_jobs, int32_t glue_job,

@@ -16,21 +16,20 @@ autograd as usual.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _keepalive, _lib
-from ._lib import check, ptr
 
 _STATE = {"active": False, "jobs": [], "streams": {}, "forked": set(), "extra": []}
-MAX_JOBS = 16
 
 
 def flush_async(device):
     """Launch the weight gradients queued so far NOW, on a side stream behind the current stream's tail, and keep
     going: called by the trainer at a point of the backward pass where most jobs are queued and a long chain that
-    does not depend on them is about to start (the personalised field's backward).  The block's exit joins."""
+    does not depend on them is about to start (the personalised field's backward).  The block's exit joins.
+    (Flushing earlier, right behind the backward of every per-Gaussian MLP, lost on the C3 step: starting sigma_net's
+    three GEMMs beside the glue backward doubles that kernel, 33 -> 75 us on the critical path, and the graph executor
+    then queues the personalised field's backward behind the next flush: 1.088 ms/step against 1.072.)"""
     if not _STATE["active"] or not _STATE["jobs"]:
         return
     device = torch.device(device)
@@ -68,50 +67,12 @@ def defer_weight_grad(dz, inp, weight, virt=None):
     _STATE["jobs"].append((dz, inp, weight, virt))
 
 
-def _chunks(group):
-    """Launches of at most MAX_JOBS jobs, at most one of them with virtual input rows."""
-    out, cur = [], []
-    for job in group:
-        if len(cur) == MAX_JOBS or (job[3] is not None and any(j[3] is not None for j in cur)):
-            out.append(cur)
-            cur = []
-        cur.append(job)
-    if cur:
-        out.append(cur)
-    return out
-
-
 def _flush(jobs):
-    L = _lib.lib()
-    by_n = {}
-    for job in jobs:
-        by_n.setdefault((job[0].device, job[0].shape[0]), []).append(job)
-    for (dev, N), group in by_n.items():
-        for chunk in _chunks(group):
-            arr = (_lib.WgradJob * len(chunk))()
-            dws, total, glue = [], 0, None
-            for i, (dz, inp, w, virt) in enumerate(chunk):
-                O, K = dz.shape[1], inp.shape[1]
-                if virt is not None:
-                    glue = (i, virt)
-                    K += virt[0].shape[1] + virt[1].shape[1]
-                dw = torch.empty(O, K, dtype=torch.float32, device=dev)
-                dws.append(dw)
-                arr[i] = _lib.WgradJob(dz.data_ptr(), inp.data_ptr(), dw.data_ptr(), N, O, K)
-                total += (L.instag_linear_weight_grad_workspace_bytes(N, O, K) + 255) // 256 * 256
-            ws = torch.empty(total, dtype=torch.uint8, device=dev)
-            if glue is None:
-                check(L.instag_linear_weight_grad_batched(arr, len(chunk), ptr(ws), total, _lib.current_stream()),
-                      "linear_weight_grad_batched")
-            else:
-                i, (aud, eye_pre, enc_a, enc_e) = glue
-                check(L.instag_linear_weight_grad_batched_glue(arr, len(chunk), i, ptr(aud), ptr(eye_pre), ptr(enc_a),
-                                                               ptr(enc_e), aud.shape[1], eye_pre.shape[1], ptr(ws),
-                                                               total, _lib.current_stream()),
-                      "linear_weight_grad_batched_glue")
-            for (dz, inp, w, _), dw in zip(chunk, dws):
-                dw = dw.reshape(w.shape).to(w.dtype)
-                w.grad = dw if w.grad is None else w.grad.add_(dw)
+    from . import mlp
+    dws = mlp.weight_grads([(dz, inp, virt) for dz, inp, _, virt in jobs])
+    for (_, _, w, _), dw in zip(jobs, dws):
+        dw = dw.reshape(w.shape).to(w.dtype)
+        w.grad = dw if w.grad is None else w.grad.add_(dw)
 
 
 _ONE = {}

@@ -105,9 +105,10 @@ class _GlueSigma(torch.autograd.Function):
                                         ptr(w3c), ptr(y), ptr(a1), ptr(a2), ptr(s1), ptr(s2), ptr(h_in), ptr(amb), N, H,
                                         O, stream), "mlp_forward_glue")
         _mlp.STATS["fwd_flops"] += 2 * N * (K0 * H + H * H + H * O)
-        ctx.save_for_backward(aud, eye_pre, enc_a, enc_e, amb, h_in if h_in is not None or not keep else enc_x, w1c,
-                              w2c, w3c, a1, a2, s1, s2)
         ctx.virtual = keep and h_in is None
+        # the first layer's weight gradient reads the stored rows, or assembles them around their enc_x columns
+        ctx.save_for_backward(aud, eye_pre, enc_a, enc_e, amb, enc_x if ctx.virtual else h_in, w1c, w2c, w3c, a1, a2,
+                              s1, s2)
         ctx.weights = (w1, w2, w3)
         ctx.dims = (N, KX, KA, KE, H, O)
         ctx.frame_stream = frame_stream
@@ -115,12 +116,12 @@ class _GlueSigma(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, d_amb):
-        from . import deferred, mlp as _mlp
+        from . import mlp as _mlp
         L = _lib.lib()
         if d_amb is not None:
             from . import diff_gauss
             diff_gauss.join_pending_aux()        # (see _MotionGlue.backward)
-        aud, eye_pre, enc_a, enc_e, amb, h_in, w1, w2, w3, a1, a2, s1, s2 = ctx.saved_tensors
+        aud, eye_pre, enc_a, enc_e, amb, x1, w1, w2, w3, a1, a2, s1, s2 = ctx.saved_tensors
         N, KX, KA, KE, H, O = ctx.dims
         dev = aud.device
         dy = torch.zeros(N, O, dtype=torch.float32, device=dev) if dy is None else _c(dy)
@@ -138,25 +139,9 @@ class _GlueSigma(torch.autograd.Function):
         _mlp.STATS["bwd_flops"] += 2 * N * (H * O + H * H + (KX + KA + KE) * H)
         d_vec = _column_sums(parts, ctx.frame_stream, dev)
         virt = (aud, eye_pre, enc_a, enc_e) if ctx.virtual else None
-        grads = [None, None, None]
-        queue = deferred.active() and all(w.is_leaf for w in ctx.weights)
-        if virt is not None and not queue and ctx.needs_input_grad[5]:
-            # (h_in holds enc_x here; outside a deferred block the single-job entry point wants the rows in memory)
-            h_in = torch.cat([h_in, aud * enc_a, torch.relu(eye_pre) * enc_e], dim=1)
-        jobs = [(dz1, h_in, 0), (dz2, a1, 1), (dy, a2, 2)]
-        if queue:
-            for dz, inp, idx in jobs:
-                if ctx.needs_input_grad[5 + idx]:
-                    deferred.defer_weight_grad(dz, inp, ctx.weights[idx], virt if idx == 0 else None)
-        else:
-            for dz, inp, idx in jobs:
-                if ctx.needs_input_grad[5 + idx]:
-                    dw = torch.empty(dz.shape[1], inp.shape[1], dtype=torch.float32, device=dev)
-                    ws = torch.empty(L.instag_linear_weight_grad_workspace_bytes(N, dz.shape[1], inp.shape[1]),
-                                     dtype=torch.uint8, device=dev)
-                    _mlp._weight_grad(L, dz, inp, dw, ws)
-                    grads[idx] = dw
-        return d_enc_x, d_aud, d_eye, d_vec[:KA], d_vec[KA:], grads[0], grads[1], grads[2], None
+        grads = _mlp.emit_weight_grads([(dz1, x1, virt), (dz2, a1, None), (dy, a2, None)], ctx.weights,
+                                       ctx.needs_input_grad[5:8])
+        return (d_enc_x, d_aud, d_eye, d_vec[:KA], d_vec[KA:], *grads, None)
 
 
 def _column_sums(parts, side, dev):

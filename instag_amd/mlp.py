@@ -2,18 +2,19 @@
 
 Boundary: the reference's ``MLP.forward`` (scene/motion_net.py:167-173) applied to the per-Gaussian
 feature matrix [N, dim_in].  C ABI: instag_mlp_forward / instag_mlp_backward /
-instag_linear_weight_grad (include/instag_hip.h).
+instag_linear_weight_grad_batched (include/instag_hip.h).
 """
 from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, deferred
 from ._lib import check, ptr
 
 
 # multiply-add work launched so far (2 flops per MAC), read by bench.py for the MFMA roofline of the MLP kernels
 STATS = {"fwd_flops": 0, "bwd_flops": 0}
+MAX_WGRAD_JOBS = 16           # per launch (include/instag_hip.h)
 
 
 def supported(dim_in, dim_hidden, dim_out, num_layers) -> bool:
@@ -26,196 +27,180 @@ def sign_words(N, dev):
     return torch.empty((N + 31) // 32, 64, dtype=torch.int32, device=dev)
 
 
-def _weight_grad(L, dz, inp, dw, ws):
-    N, (O, K) = dz.shape[0], dw.shape
-    check(L.instag_linear_weight_grad(ptr(dz), ptr(inp), ptr(dw), ptr(ws), ws.numel(), N, O, K,
-                                      _lib.current_stream()), "linear_weight_grad")
+def _forward(L, x, w1, w2, w3, keep):
+    """MLP(x) for contiguous fp32 x [N,K0] and weights [out,in] (w3 None: two layers) -> (y, a1, a2, s1, s2): the hidden
+    activations and ReLU sign words that the gradients read, None without ``keep`` (a2, s2: and with two layers)."""
+    N, K0 = x.shape
+    H = w1.shape[0]
+    NL = 2 if w3 is None else 3
+    O = (w2 if NL == 2 else w3).shape[0]
+    y = torch.empty(N, O, dtype=torch.float32, device=x.device)
+    a1 = torch.empty(N, H, dtype=torch.float32, device=x.device) if keep else None
+    a2 = torch.empty(N, H, dtype=torch.float32, device=x.device) if (keep and NL == 3) else None
+    s1 = sign_words(N, x.device) if keep else None
+    s2 = sign_words(N, x.device) if (keep and NL == 3) else None
+    check(L.instag_mlp_forward(ptr(x), ptr(w1), ptr(w2), ptr(w3), ptr(y), ptr(a1), ptr(a2), ptr(s1), ptr(s2),
+                               N, K0, H, O, NL, _lib.current_stream()), "mlp_forward")
+    STATS["fwd_flops"] += 2 * N * (K0 * H + (H * H if NL == 3 else 0) + H * O)
+    return y, a1, a2, s1, s2
+
+
+def _wgrad_launches(jobs):
+    """Indices of the jobs of each launch: equal N, at most MAX_WGRAD_JOBS, at most one with virtual input rows."""
+    by_n = {}
+    for i, (dz, _, _) in enumerate(jobs):
+        by_n.setdefault(dz.shape[0], []).append(i)
+    for group in by_n.values():
+        cur = []
+        for i in group:
+            if len(cur) == MAX_WGRAD_JOBS or (jobs[i][2] is not None and any(jobs[j][2] is not None for j in cur)):
+                yield cur
+                cur = []
+            cur.append(i)
+        yield cur
+
+
+def weight_grads(jobs):
+    """dW = dz^T @ inp, [O,K] fp32, for every job (dz [N,O], inp [N,K], virt) of one device, in job order: one launch
+    for all jobs of one N (see _wgrad_launches).  ``virt`` = (aud, eye_pre, enc_a, enc_e): the input rows were never
+    stored, they are cat(inp, aud * enc_a, relu(eye_pre) * enc_e) (glue._GlueSigma) and the kernel assembles them
+    while loading; None: inp holds the rows."""
+    L = _lib.lib()
+    dev = jobs[0][0].device
+    dws = [None] * len(jobs)
+    for chunk in _wgrad_launches(jobs):
+        arr = (_lib.WgradJob * len(chunk))()
+        total, glue = 0, None
+        for slot, i in enumerate(chunk):
+            dz, inp, virt = jobs[i]
+            N, O, K = dz.shape[0], dz.shape[1], inp.shape[1]
+            if virt is not None:
+                glue = (slot, virt)
+                K += virt[0].shape[1] + virt[1].shape[1]
+            dws[i] = torch.empty(O, K, dtype=torch.float32, device=dev)
+            arr[slot] = _lib.WgradJob(dz.data_ptr(), inp.data_ptr(), dws[i].data_ptr(), N, O, K)
+            total += (L.instag_linear_weight_grad_workspace_bytes(N, O, K) + 255) // 256 * 256
+        ws = torch.empty(total, dtype=torch.uint8, device=dev)
+        if glue is None:
+            check(L.instag_linear_weight_grad_batched(arr, len(chunk), ptr(ws), total, _lib.current_stream()),
+                  "linear_weight_grad_batched")
+        else:
+            slot, (aud, eye_pre, enc_a, enc_e) = glue
+            check(L.instag_linear_weight_grad_batched_glue(arr, len(chunk), slot, ptr(aud), ptr(eye_pre), ptr(enc_a),
+                                                           ptr(enc_e), aud.shape[1], eye_pre.shape[1], ptr(ws), total,
+                                                           _lib.current_stream()), "linear_weight_grad_batched_glue")
+    return dws
+
+
+def emit_weight_grads(jobs, weights, wanted):
+    """The weight gradients of one autograd node, for its backward to return: jobs[i] = (dz, inp, virt) yields the
+    gradient of weights[i] (None: a two-layer MLP has no third), wanted[i] = the weight's ``needs_input_grad``.  Only the
+    optimizer reads them: inside a ``deferred_grads`` block (instag_amd/deferred.py) whose node's weights are all leaf
+    parameters they are queued for the block's batched launch and autograd gets None; otherwise they are computed
+    now, in one launch."""
+    slots = [i for i, job in enumerate(jobs) if job is not None and wanted[i]]
+    grads = [None] * len(weights)
+    if deferred.active() and all(w is None or w.is_leaf for w in weights):
+        for i in slots:
+            dz, inp, virt = jobs[i]
+            deferred.defer_weight_grad(dz, inp, weights[i], virt)
+    elif slots:
+        for i, dw in zip(slots, weight_grads([jobs[i] for i in slots])):
+            grads[i] = dw
+    return grads
 
 
 class _FusedMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, w2, w3):
-        L = _lib.lib()
         x = x.contiguous().float()
         w1c, w2c = w1.contiguous().float(), w2.contiguous().float()
         w3c = None if w3 is None else w3.contiguous().float()
-        N, K0 = x.shape
-        H = w1c.shape[0]
-        NL = 2 if w3c is None else 3
-        O = (w2c if NL == 2 else w3c).shape[0]
-        y = torch.empty(N, O, dtype=torch.float32, device=x.device)
-        need = any(ctx.needs_input_grad)
-        a1 = torch.empty(N, H, dtype=torch.float32, device=x.device) if need else None
-        a2 = torch.empty(N, H, dtype=torch.float32, device=x.device) if (need and NL == 3) else None
-        s1 = sign_words(N, x.device) if need else None
-        s2 = sign_words(N, x.device) if (need and NL == 3) else None
-        check(L.instag_mlp_forward(ptr(x), ptr(w1c), ptr(w2c), ptr(w3c), ptr(y), ptr(a1), ptr(a2), ptr(s1), ptr(s2),
-                                   N, K0, H, O, NL, _lib.current_stream()), "mlp_forward")
+        y, a1, a2, s1, s2 = _forward(_lib.lib(), x, w1c, w2c, w3c, any(ctx.needs_input_grad))
         ctx.save_for_backward(x, w1c, w2c, w3c, a1, a2, s1, s2)
         ctx.weights = (w1, w2, w3)          # the caller's tensors (leaf parameters in the deferred-gradient mode)
-        ctx.dims = (N, K0, H, O, NL)
-        STATS["fwd_flops"] += 2 * N * (K0 * H + (H * H if NL == 3 else 0) + H * O)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
         x, w1, w2, w3, a1, a2, s1, s2 = ctx.saved_tensors
-        N, K0, H, O, NL = ctx.dims
+        (N, K0), H = x.shape, w1.shape[0]
+        NL = 2 if w3 is None else 3
+        O = dy.shape[1]
         dy = dy.contiguous().float()
-        stream = _lib.current_stream()
         dev = dy.device
         dz1 = torch.empty(N, H, dtype=torch.float32, device=dev)
         dz2 = torch.empty(N, H, dtype=torch.float32, device=dev) if NL == 3 else None
         dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         check(L.instag_mlp_backward(ptr(dy), ptr(s1), ptr(s2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2), ptr(dx),
-                                    N, K0, H, O, NL, stream), "mlp_backward")
+                                    N, K0, H, O, NL, _lib.current_stream()), "mlp_backward")
         STATS["bwd_flops"] += 2 * N * (H * O + (H * H if NL == 3 else 0) + (K0 * H if dx is not None else 0))
-        # weight gradients: only the optimizer reads them.  Inside a ``deferred_grads`` block (instag_amd/deferred.py)
-        # they are queued and computed after the rest of the backward pass in one batched launch
-        from . import deferred
-        layers = [(dz1, x, 1, (H, K0))]
-        layers += [(dz2, a1, 2, (H, H)), (dy, a2, 3, (O, H))] if NL == 3 else [(dy, a1, 2, (O, H))]
-        layers = [(dz, inp, idx, shp) for dz, inp, idx, shp in layers if ctx.needs_input_grad[idx]]
-
-        def compute():
-            out = {}
-            for dz, inp, idx, shp in layers:
-                dw = torch.empty(*shp, dtype=torch.float32, device=dev)
-                ws = torch.empty(L.instag_linear_weight_grad_workspace_bytes(N, shp[0], shp[1]), dtype=torch.uint8,
-                                 device=dev)
-                _weight_grad(L, dz, inp, dw, ws)
-                out[idx] = dw
-            return out
-
-        if deferred.active() and all(w is None or w.is_leaf for w in ctx.weights):
-            for dz, inp, idx, shp in layers:
-                deferred.defer_weight_grad(dz, inp, ctx.weights[idx - 1])
-            if EAGER_FLUSH_ROWS and N >= EAGER_FLUSH_ROWS:
-                # a per-Gaussian MLP: its weight-gradient GEMMs are the big ones (sigma_net: a third of the step's MFMA
-                # work) and their operands exist now -- start them on the side stream beside the rest of the backward
-                # chain instead of in one lump beside the personalised field's backward, which they slow down
-                deferred.flush_async(dev)
-            return dx, None, None, None
-        dws = compute()
-        dw1, dw2, dw3 = dws.get(1), dws.get(2), dws.get(3)
-        return dx, dw1, dw2, dw3
-
-
-# Rows from which an MLP's weight gradients are launched right after its backward (0 = wait for the flush points of
-# renderer.py / gridencoder.py).  Measured on the C3 step (round 2): starting sigma_net's three GEMMs beside the glue
-# backward doubles that kernel (33 -> 75 us, it is on the critical path) and the graph executor then queues the
-# personalised field's backward behind the next flush: 1.072 ms/step with 0, 1.088 with 32768.
-EAGER_FLUSH_ROWS = 0
-
-
-FUSE_SHARED_HEADS = True      # False: one launch per head (tests compare the two)
+        jobs = [(dz1, x, None)] + ([(dz2, a1, None), (dy, a2, None)] if NL == 3 else [(dy, a1, None), None])
+        return (dx, *emit_weight_grads(jobs, ctx.weights, ctx.needs_input_grad[1:]))
 
 
 class _SharedInputMLPs(torch.autograd.Function):
     """Two 2-layer MLPs over the SAME input x plus x itself as a third output (for the input's other consumers):
     (MLP_a(x), MLP_b(x), x).  The reference runs aud_ch_att_net(enc_x), eye_att_net(enc_x) and then concatenates
     enc_x into sigma_net's input (scene/motion_net.py:281-306), so autograd sums three gradients of enc_x with two
-    elementwise launches; here the sum happens inside the two backward kernels (instag_mlp_backward_add)."""
+    elementwise launches; here the sum happens inside the backward kernel (instag_mlp2_backward; a shape pair without
+    one runs the heads one by one, instag_mlp_backward_add)."""
 
     @staticmethod
     def forward(ctx, x, wa1, wa2, wb1, wb2):
         L = _lib.lib()
         x = x.contiguous().float()
         N, K0 = x.shape
-        outs, saved, dims = [], [x], []
-        if FUSE_SHARED_HEADS and L.instag_mlp2_supported(K0, wa1.shape[0], wa2.shape[0], wb1.shape[0], wb2.shape[0]):
+        ws = [w.contiguous().float() for w in (wa1, wa2, wb1, wb2)]
+        (HA, OA), (HB, OB) = (ws[0].shape[0], ws[1].shape[0]), (ws[2].shape[0], ws[3].shape[0])
+        keep = any(ctx.needs_input_grad)          # forward only (inference, the jaw feature): nothing is kept
+        ctx.weights = (wa1, wa2, wb1, wb2)
+        ctx.fused = bool(L.instag_mlp2_supported(K0, HA, OA, HB, OB))
+        if ctx.fused:
             # both heads in one launch: the tile of x is loaded once (csrc/mlp.hip: mlp2_forward_kernel)
-            ws = [w.contiguous().float() for w in (wa1, wa2, wb1, wb2)]
-            (HA, OA), (HB, OB) = (ws[0].shape[0], ws[1].shape[0]), (ws[2].shape[0], ws[3].shape[0])
             ya = torch.empty(N, OA, dtype=torch.float32, device=x.device)
             yb = torch.empty(N, OB, dtype=torch.float32, device=x.device)
-            keep = any(ctx.needs_input_grad)          # forward only (inference, the jaw feature): nothing is kept
             a1a = torch.empty(N, HA, dtype=torch.float32, device=x.device) if keep else None
             a1b = torch.empty(N, HB, dtype=torch.float32, device=x.device) if keep else None
-            s1 = sign_words(N, x.device) if keep else None          # both heads' bits: A low half, B high half
+            s1a = s1b = sign_words(N, x.device) if keep else None   # both heads' bits: A low half, B high half
             check(L.instag_mlp2_forward(ptr(x), ptr(ws[0]), ptr(ws[1]), ptr(ws[2]), ptr(ws[3]), ptr(ya), ptr(yb),
-                                        ptr(a1a), ptr(a1b), ptr(s1), N, K0, HA, OA, HB, OB, _lib.current_stream()),
+                                        ptr(a1a), ptr(a1b), ptr(s1a), N, K0, HA, OA, HB, OB, _lib.current_stream()),
                   "mlp2_forward")
             STATS["fwd_flops"] += 2 * N * (K0 * HA + HA * OA + K0 * HB + HB * OB)
-            ctx.save_for_backward(x, ws[0], ws[1], a1a, s1, ws[2], ws[3], a1b, s1)
-            ctx.weights = (wa1, wa2, wb1, wb2)
-            ctx.dims = (N, K0, [(HA, OA), (HB, OB)])
-            ctx.fused = True
-            return ya, yb, x.view_as(x)
-        ctx.fused = False
-        for w1, w2 in ((wa1, wa2), (wb1, wb2)):
-            w1c, w2c = w1.contiguous().float(), w2.contiguous().float()
-            H, O = w1c.shape[0], w2c.shape[0]
-            y = torch.empty(N, O, dtype=torch.float32, device=x.device)
-            a1 = torch.empty(N, H, dtype=torch.float32, device=x.device)
-            s1 = sign_words(N, x.device)
-            check(L.instag_mlp_forward(ptr(x), ptr(w1c), ptr(w2c), None, ptr(y), ptr(a1), None, ptr(s1), None, N, K0, H,
-                                       O, 2, _lib.current_stream()), "mlp_forward")
-            STATS["fwd_flops"] += 2 * N * (K0 * H + H * O)
-            outs.append(y)
-            saved += [w1c, w2c, a1, s1]
-            dims.append((H, O))
-        ctx.save_for_backward(*saved)
-        ctx.weights = (wa1, wa2, wb1, wb2)
-        ctx.dims = (N, K0, dims)
-        return outs[0], outs[1], x.view_as(x)
+        else:
+            ya, a1a, _, s1a, _ = _forward(L, x, ws[0], ws[1], None, keep)
+            yb, a1b, _, s1b, _ = _forward(L, x, ws[2], ws[3], None, keep)
+        ctx.save_for_backward(x, ws[0], ws[1], a1a, s1a, ws[2], ws[3], a1b, s1b)
+        return ya, yb, x.view_as(x)
 
     @staticmethod
     def backward(ctx, dya, dyb, dx_other):
-        from . import deferred
+        # (all three are tensors: autograd hands in zeros for an output that nothing read)
         L = _lib.lib()
-        x = ctx.saved_tensors[0]
-        N, K0, dims = ctx.dims
+        x, wa1, wa2, a1a, s1a, wb1, wb2, a1b, s1b = ctx.saved_tensors
+        N, K0 = x.shape
+        (HA, OA), (HB, OB) = (wa1.shape[0], wa2.shape[0]), (wb1.shape[0], wb2.shape[0])
         dev = x.device
         stream = _lib.current_stream()
         want_dx = ctx.needs_input_grad[0]
         dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if want_dx else None
-        add = None if dx_other is None else dx_other.contiguous().float()
-        jobs = []
-        fused = ctx.fused and dya is not None and dyb is not None
-        if fused:
-            wa1, wa2, a1a, s1, wb1, wb2, a1b = ctx.saved_tensors[1:8]
-            (HA, OA), (HB, OB) = dims
-            dya, dyb = dya.contiguous().float(), dyb.contiguous().float()
-            dz1a = torch.empty(N, HA, dtype=torch.float32, device=dev)
-            dz1b = torch.empty(N, HB, dtype=torch.float32, device=dev)
-            check(L.instag_mlp2_backward(ptr(dya), ptr(dyb), ptr(s1), ptr(s1), ptr(wa1), ptr(wa2), ptr(wb1),
-                                         ptr(wb2), ptr(dz1a), ptr(dz1b), ptr(dx), ptr(add) if want_dx else None,
-                                         N, K0, HA, OA, HB, OB, stream), "mlp2_backward")
-            STATS["bwd_flops"] += 2 * N * (HA * OA + HB * OB + (K0 * (HA + HB) if want_dx else 0))
-            add = dx if want_dx else add
-            jobs = [(dz1a, x, 1, (HA, K0)), (dya, a1a, 2, (OA, HA)), (dz1b, x, 3, (HB, K0)), (dyb, a1b, 4, (OB, HB))]
-        for k, dy in enumerate(() if fused else (dya, dyb)):
-            if dy is None:
-                continue
-            w1, w2, a1, s1 = ctx.saved_tensors[1 + 4 * k:5 + 4 * k]
-            if ctx.fused and k == 1:
-                s1 = s1 >> 16                 # the fused forward packed head B's bits into the high half
-            H, O = dims[k]
-            dy = dy.contiguous().float()
-            dz1 = torch.empty(N, H, dtype=torch.float32, device=dev)
-            check(L.instag_mlp_backward_add(ptr(dy), ptr(s1), None, ptr(w1), ptr(w2), None, ptr(dz1), None, ptr(dx),
-                                            ptr(add) if want_dx else None, N, K0, H, O, 2, stream), "mlp_backward")
-            STATS["bwd_flops"] += 2 * N * (H * O + (K0 * H if want_dx else 0))
-            if want_dx:
-                add = dx                      # the next kernel adds onto what is already there
-            jobs += [(dz1, x, 1 + 2 * k, (H, K0)), (dy, a1, 2 + 2 * k, (O, H))]
-        if want_dx and add is not dx:         # neither head carried a gradient
-            dx = torch.zeros(N, K0, dtype=torch.float32, device=dev) if dx_other is None else dx_other
-        jobs = [(dz, inp, idx, shp) for dz, inp, idx, shp in jobs if ctx.needs_input_grad[idx]]
-        grads = [None] * 4
-        if deferred.active() and all(w.is_leaf for w in ctx.weights):
-            for dz, inp, idx, shp in jobs:
-                deferred.defer_weight_grad(dz, inp, ctx.weights[idx - 1])
+        add = dx_other.contiguous().float() if want_dx else None
+        dya, dyb = dya.contiguous().float(), dyb.contiguous().float()
+        dz1a = torch.empty(N, HA, dtype=torch.float32, device=dev)
+        dz1b = torch.empty(N, HB, dtype=torch.float32, device=dev)
+        if ctx.fused:
+            check(L.instag_mlp2_backward(ptr(dya), ptr(dyb), ptr(s1a), ptr(s1b), ptr(wa1), ptr(wa2), ptr(wb1),
+                                         ptr(wb2), ptr(dz1a), ptr(dz1b), ptr(dx), ptr(add), N, K0, HA, OA, HB, OB,
+                                         stream), "mlp2_backward")
         else:
-            for dz, inp, idx, shp in jobs:
-                dw = torch.empty(*shp, dtype=torch.float32, device=dev)
-                ws = torch.empty(L.instag_linear_weight_grad_workspace_bytes(N, shp[0], shp[1]), dtype=torch.uint8,
-                                 device=dev)
-                _weight_grad(L, dz, inp, dw, ws)
-                grads[idx - 1] = dw
-        return (dx, *grads)
+            for dy, s1, w1, w2, dz1 in ((dya, s1a, wa1, wa2, dz1a), (dyb, s1b, wb1, wb2, dz1b)):
+                check(L.instag_mlp_backward_add(ptr(dy), ptr(s1), None, ptr(w1), ptr(w2), None, ptr(dz1), None, ptr(dx),
+                                                ptr(add), N, K0, w1.shape[0], w2.shape[0], 2, stream), "mlp_backward")
+                add = dx                          # the second kernel adds onto what the first wrote
+        STATS["bwd_flops"] += 2 * N * (HA * OA + HB * OB + (K0 * (HA + HB) if want_dx else 0))
+        jobs = [(dz1a, x, None), (dya, a1a, None), (dz1b, x, None), (dyb, a1b, None)]
+        return (dx, *emit_weight_grads(jobs, ctx.weights, ctx.needs_input_grad[1:]))
 
 
 def shared_input_mlps(x, weights_a, weights_b):

@@ -525,7 +525,7 @@ def test_glue_sigma_backward_kernel_matches_the_two_operators(hidden, with_amb):
 @pytest.mark.parametrize("in_block", [True, False])
 def test_glue_sigma_unstored_input_rows_give_the_same_bits(hidden, in_block, monkeypatch):
     """sigma_net's input rows not written by the forward, assembled again by the first layer's weight gradient
-    (instag_linear_weight_grad_batched_glue; outside a deferred block by torch) == rows stored by the forward: the same
+    (instag_linear_weight_grad_batched_glue, inside a deferred block and outside) == rows stored by the forward: the same
     products in the same order, so every output and gradient bit for bit."""
     from instag_amd import glue
     from instag_amd.deferred import deferred_grads

@@ -98,8 +98,57 @@ def test_motion_networks_on_gpu_match_reference_golden(golden_dir):
         assert net.encoder_xy.embeddings.grad is not None and net.sigma_net.net[0].weight.grad is not None
 
 
+def _dw_bound(N, ref):
+    """test_fused_mlp_forward_backward's bound for a weight gradient summed over N rows"""
+    return 2e-5 * max(1.0, np.sqrt(N) / 16) * max(1.0, float(ref.abs().max()))
+
+
+@pytest.mark.parametrize("K0,H,O,NL", [(74, 64, 11, 3), (5, 7, 3, 2)])
+@pytest.mark.parametrize("N", [1, 4999])
+def test_immediate_weight_grads_with_an_idle_slot(K0, H, O, NL, N):
+    """Outside a deferred_grads block a node's weight gradients leave in one launch of as many jobs as weights want
+    one: w1 and w3 (the 2-layer shape has no w3) but not w2 == fp64 autograd, and w2 gets none."""
+    from instag_amd.mlp import fused_mlp
+    g = torch.Generator().manual_seed(N + K0)
+    dims = [K0] + [H] * (NL - 1) + [O]
+    ws = [torch.randn(dims[i + 1], dims[i], generator=g) / np.sqrt(dims[i]) for i in range(NL)]
+    x, gy = torch.randn(N, K0, generator=g), torch.randn(N, O, generator=g)
+    wd = [w.double().requires_grad_(i != 1) for i, w in enumerate(ws)]
+    (_ref(x.double(), wd) * gy.double()).sum().backward()
+    wh = [w.cuda().requires_grad_(i != 1) for i, w in enumerate(ws)]
+    (fused_mlp(x.cuda(), wh) * gy.cuda()).sum().backward()
+    assert wh[1].grad is None
+    for i in (0, 2)[:NL - 1]:
+        err = float((wh[i].grad.cpu().double() - wd[i].grad).abs().max())
+        print(f"dW{i + 1}: max err {err:.3e} bound {_dw_bound(N, wd[i].grad):.3e}")
+        assert err <= _dw_bound(N, wd[i].grad), (i, err)
+
+
+@pytest.mark.parametrize("N,O,K", [(1, 3, 7), (4999, 64, 96)])
+def test_single_job_entry_point_is_a_batch_of_one(N, O, K):
+    """instag_linear_weight_grad, with the workspace it asks for and not a byte more, == the batched launch of that
+    job bit for bit, and dz^T @ inp in fp64; a smaller workspace is refused."""
+    from instag_amd import _lib
+    from instag_amd._lib import ptr
+    from instag_amd.mlp import weight_grads
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(N + K)
+    dz, inp = torch.randn(N, O, generator=g).cuda(), torch.randn(N, K, generator=g).cuda()
+    nbytes = L.instag_linear_weight_grad_workspace_bytes(N, O, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    dw = torch.empty(O, K, device="cuda")
+    args = (ptr(dz), ptr(inp), ptr(dw), ptr(ws))
+    assert L.instag_linear_weight_grad(*args, nbytes, N, O, K, _lib.current_stream()) == 0, L.instag_last_error()
+    assert torch.equal(dw, weight_grads([(dz, inp, None)])[0])
+    ref = dz.cpu().double().t() @ inp.cpu().double()
+    assert float((dw.cpu().double() - ref).abs().max()) <= _dw_bound(N, ref)
+    assert L.instag_linear_weight_grad(*args, nbytes - 1, N, O, K, _lib.current_stream()) != 0
+    assert b"workspace too small" in L.instag_last_error()
+
+
 def test_deferred_batched_weight_grads_match_autograd():
-    """deferred_grads(): the MLPs' weight gradients are queued and computed in one batched launch, same values."""
+    """deferred_grads(): the MLPs' weight gradients are queued and computed in one batched launch, same values as one
+    launch per MLP outside a block, and both the gradients of the fp64 nets."""
     import torch
     from instag_amd.deferred import deferred_grads
     from instag_amd.mlp import fused_mlp
@@ -127,6 +176,14 @@ def test_deferred_batched_weight_grads_match_autograd():
     for wr, wg in zip(ref, got):
         for a, b in zip(wr, wg):
             assert b.grad is not None and torch.equal(a.grad, b.grad)
+    # both run the same kernels: anchor them to fp64 autograd of the same three nets
+    for x, wg in zip(xs, got):
+        wd = [w.detach().cpu().double().requires_grad_(True) for w in wg]
+        (_ref(x.cpu().double(), wd) ** 2).sum().backward()
+        for i, (d, b) in enumerate(zip(wd, wg)):
+            err = float((b.grad.cpu().double() - d.grad).abs().max())
+            print(f"K0 {x.shape[1]} dW{i + 1}: max err {err:.3e} bound {_dw_bound(N, d.grad):.3e}")
+            assert err <= _dw_bound(N, d.grad), (x.shape[1], i, err)
     # a second backward inside a block accumulates like autograd does
     with deferred_grads("cuda"):
         loss(got).backward()
@@ -166,3 +223,59 @@ def test_shared_input_mlps_match_separate_mlps():
     ya, yb, xo = shared_input_mlps(x, wa, wb)
     (xo * gx).sum().backward()
     assert torch.equal(x.grad, gx)
+
+
+def _shared_against_separate(N, dims_a, dims_b, use_a=True, use_b=True):
+    """shared_input_mlps against two fused_mlp calls and autograd's own sum of the input's gradients, for the loss over
+    the used heads and the pass-through, at test_shared_input_mlps_match_separate_mlps's bound.  -> the weights'
+    gradients of the shared run."""
+    from instag_amd.mlp import fused_mlp, shared_input_mlps
+    torch.manual_seed(3 + N)
+    (K0, HA, OA), (_, HB, OB) = dims_a, dims_b
+    x0 = torch.randn(N, K0, device="cuda")
+    w0 = [torch.randn(HA, K0, device="cuda") * 0.3, torch.randn(OA, HA, device="cuda") * 0.3,
+          torch.randn(HB, K0, device="cuda") * 0.3, torch.randn(OB, HB, device="cuda") * 0.3]
+    ga, gb, gx = torch.randn(N, OA, device="cuda"), torch.randn(N, OB, device="cuda"), torch.randn(N, K0, device="cuda")
+
+    def run(shared):
+        x = x0.clone().requires_grad_(True)
+        ws = [w.clone().requires_grad_(True) for w in w0]
+        if shared:
+            ya, yb, xo = shared_input_mlps(x, ws[:2], ws[2:])
+        else:
+            ya, yb, xo = fused_mlp(x, ws[:2]), fused_mlp(x, ws[2:]), x
+        loss = (xo * gx).sum()
+        loss = loss + (ya * ga).sum() if use_a else loss
+        loss = loss + (yb * gb).sum() if use_b else loss
+        loss.backward()
+        return [ya.detach(), yb.detach(), x.grad] + [w.grad for w in ws]
+
+    ref, got = run(False), run(True)
+    names = ["ya", "yb", "dx", "dwa1", "dwa2", "dwb1", "dwb2"]
+    unused = [] if use_a and use_b else names[5:] if use_a else names[3:5]
+    for n_, r, g in zip(names, ref, got):
+        assert (r is None) == (n_ in unused), n_
+        if r is None:                  # a separate MLP outside the loss: autograd never reaches its weights
+            continue
+        scale = float(r.abs().max())
+        err = float((r - g).abs().max())
+        print(f"{n_}: max err {err:.3e} bound {2e-5 * scale + 1e-6:.3e}")
+        assert err <= 2e-5 * scale + 1e-6, (n_, err, scale)
+    return got[3:]
+
+
+@pytest.mark.parametrize("N", [1, 33, 5003])
+def test_shared_input_mlps_without_a_fused_kernel(N):
+    """A shape pair without an mlp2 kernel runs the heads one by one, the second adding onto the first's dx."""
+    from instag_amd import _lib
+    assert _lib.lib().instag_mlp2_supported(36, 32, 32, 32, 6) == 0
+    _shared_against_separate(N, (36, 32, 32), (36, 32, 6))
+
+
+@pytest.mark.parametrize("use_a,use_b", [(True, False), (False, True)])
+def test_shared_input_mlps_one_head_unused(use_a, use_b):
+    """Only one head and the pass-through in the loss (the fused pair, 5003 rows): autograd hands the backward zeros
+    for the other head, whose weights therefore get gradients of exact zeros from the fused kernels."""
+    dws = _shared_against_separate(5003, (36, 32, 32), (36, 16, 6), use_a, use_b)
+    for dw in dws[2:] if use_a else dws[:2]:
+        assert dw is not None and not bool(dw.any())
