@@ -32,6 +32,11 @@ ABI_VERSION = _CONSTANTS["INSTAG_ABI_VERSION"]     # a stale libinstag_hip.so mu
 E_ARG = _CONSTANTS["INSTAG_E_ARG"]
 FACE_LOSS = {k[len("INSTAG_FACE_LOSS_"):]: v for k, v in _CONSTANTS.items() if k.startswith("INSTAG_FACE_LOSS_")}
 
+# The wav2vec network's part of the ABI has a header of its own, include/instag_wav2vec.h, read by the same reader:
+# struct Wav2vecWeights, instag_wav2vec_workspace_bytes / instag_wav2vec_forward and the INSTAG_WAV2VEC_* bounds.
+_WAV2VEC_STRUCTS, _WAV2VEC_PROTOTYPES, WAV2VEC = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_wav2vec.h"))
+globals().update((cls.__name__, cls) for cls in _WAV2VEC_STRUCTS.values())
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -197,7 +202,9 @@ def lib():
         # "no ROCm-capable device is detected" from the second one.
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOTYPES.items():
+        for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES}.items():
+            if not hasattr(handle, name):
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -59,6 +59,7 @@ SOURCES = {
     "teeth.hip": [],
     "track.hip": [],
     "mesh_render.hip": [],
+    "wav2vec.hip": [],
 }
 
 
@@ -81,7 +82,8 @@ def _digest(paths, flags):
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
-    hs.append(os.path.join(ROOT, "include", "instag_hip.h"))
+    inc = os.path.join(ROOT, "include")
+    hs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
     return hs
 
 
