@@ -5,17 +5,16 @@
 // is relu(scale * conv_nobias(x) + shift [+ x]).
 //   layer 0      (1 -> 32, K = 9): VALU, fused with the window gather: it reads mel[T,80] at starts[i] (transposed
 //                access), or a stack of [n,1,80,16] windows, so the windows are never materialised.
-//   layers 1..10 implicit GEMM on the f32-input MFMA (v_mfma_f32_32x32x2_f32) as in lpips.hip: D[cout][m] with
+//   layers 1..10 the convolution kernel of conv_mfma.hpp (plain source, 3 x 3, a stride per axis): D[cout][m] with
 //                m = (window, oy, ox) tiled jointly -- from layer 6 on a window has at most 54 pixels and the batch is
-//                what fills the tile -- and k = (cin, ky, kx) gathered from NCHW activations.  Scale, shift, the residual
-//                read (the layer's own input) and the ReLU are applied to the accumulator registers; two activation
-//                buffers alternate.
+//                what fills the tile.  The residual is the layer's own input; two activation buffers alternate.  The
+//                tile is 32 x 128 for the 32-channel layers and 64 x 64 for the others.
 //   layers 11+12 are 1x1 spatial, [B,2304] x [2304,512] and [B,512] x [512,512]: one launch, a workgroup keeps the 512
-//                channels of its 32 windows in LDS between the two products.
-// Every sum is a k-ordered FMA chain per K tile of 32 with the tiles added in order (lpips.hip: blocked summation), there
-// are no atomics, and an output element reads nothing but its own window: a window's 512 values do not depend on the
+//                channels of its 32 windows in LDS between the two products and its weights in registers.
+// Every sum is a k-ordered FMA chain per K tile of 32 with the tiles added in order (mfma_tile.hpp: blocked summation),
+// there are no atomics, and an output element reads nothing but its own window: a window's 512 values do not depend on the
 // batch, the chunk or the tile column it sat in, and two runs give the same bits.
-#include "common.hpp"
+#include "conv_mfma.hpp"
 
 namespace instag {
 namespace {
@@ -24,10 +23,6 @@ constexpr int NLAYER = 13;
 constexpr int MAX_BATCH = 256;
 constexpr int MEL = 80, WIN = 16, PIX0 = MEL * WIN;      // a window is [80 bands][16 frames]
 constexpr int C0 = 32;                                   // channels of layers 0..2: the largest activation, 32 x 80 x 16
-constexpr int TB = 256;
-constexpr int BK = 32;
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 struct LayerDesc { int cin, cout, sh, sw, residual, hi, wi, ho, wo; };
 // layers 1..10 (3x3, pad 1); extents for an [80,16] window: floor((h + 2 - 3) / s) + 1
@@ -78,103 +73,6 @@ __global__ void __launch_bounds__(TB) first_layer_kernel(FirstArgs a) {
 #pragma unroll
     for (int j = 0; j < 9; ++j) s = fmaf(v[j], ws[c * 9 + j], s);
     o[(size_t)c * PIX0] = fmaxf(fmaf(s, sc[c], sf[c]), 0.f);
-  }
-}
-
-// ---- layers 1..10: 3x3 convolution, pad 1, as implicit GEMM ------------------------------------------------------------
-struct ConvArgs {
-  const float* in;      // [B, cin, hi, wi]
-  const float* wt;      // [cin * 9][cout]
-  const float* scale;   // [cout]
-  const float* shift;
-  float* out;           // [B, cout, ho, wo]
-  int B;
-  LayerDesc d;
-};
-
-// BM output channels x BN = 128 * 32 / BM positions per workgroup: four waves of one 32 x 32 accumulator each
-template <int BM>
-__global__ void __launch_bounds__(TB) conv_kernel(ConvArgs a) {
-  constexpr int WR = BM / 32, WC = 4 / WR, BN = 32 * WC;
-  constexpr int NA = BK * BM / TB, NB = BK * BN / TB;          // elements a thread stages per K tile
-  constexpr int RA = TB / BM, RB = TB / BN;                    // K rows one pass of the workgroup covers
-  __shared__ float As[BK][BM];
-  __shared__ float Bs[BK][BN];
-  const LayerDesc d = a.d;
-  const int HWo = d.ho * d.wo;
-  const int N = a.B * HWo;
-  const int n0 = blockIdx.x * BN, c0 = blockIdx.y * BM;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave / WC, wc = wave % WC;
-  const int ta = t % BM, ka = t / BM;
-  const int tb = t % BN, kb = t / BN;
-
-  // this thread's column of the gathered operand: one output position of one window
-  const int ng = n0 + tb;
-  const bool nv = ng < N;
-  int img = 0, oy = 0, ox = 0;
-  if (nv) {
-    img = ng / HWo;
-    const int pos = ng - img * HWo;
-    oy = pos / d.wo;
-    ox = pos - oy * d.wo;
-  }
-  const float* src = a.in + (size_t)img * d.cin * d.hi * d.wi;
-  const int iy0 = oy * d.sh - 1, ix0 = ox * d.sw - 1;
-
-  auto gather = [&](int k) -> float {
-    const int ci = k / 9;
-    const int r = k - ci * 9;
-    const int ky = r / 3, kx = r - ky * 3;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    if (!nv || iy < 0 || iy >= d.hi || ix < 0 || ix >= d.wi) return 0.f;
-    return src[(ci * d.hi + iy) * d.wi + ix];
-  };
-
-  float ra[NA], rb[NB];
-  auto load = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) ra[i] = a.wt[(size_t)(kt * BK + ka + RA * i) * d.cout + c0 + ta];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) rb[i] = gather(kt * BK + kb + RB * i);
-  };
-
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  const int nk = d.cin * 9 / BK;                               // cin is a multiple of 32
-  load(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NA; ++i) As[ka + RA * i][ta] = ra[i];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) Bs[kb + RB * i][tb] = rb[i];
-    __syncthreads();
-    if (kt + 1 < nk) load(kt + 1);
-    f32x16 part;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-      const float av = As[kk * 2 + (lane >> 5)][wr * 32 + (lane & 31)];
-      const float bv = Bs[kk * 2 + (lane >> 5)][wc * 32 + (lane & 31)];
-      part = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, part, 0, 0, 0);
-    }
-    acc += part;
-  }
-
-  // D: column (lane & 31) = output position, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = output channel
-  const int nc = n0 + wc * 32 + (lane & 31);
-  if (nc >= N) return;
-  const int oimg = nc / HWo, opos = nc - oimg * HWo;
-  const size_t obase = (size_t)oimg * d.cout * HWo + opos;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = c0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const size_t o = obase + (size_t)co * HWo;
-    float v = fmaf(acc[r], a.scale[co], a.shift[co]);
-    if (d.residual) v += a.in[o];                              // cin == cout and the extents are kept
-    a.out[o] = fmaxf(v, 0.f);
   }
 }
 
@@ -253,7 +151,7 @@ __global__ void __launch_bounds__(TAIL_TB) tail_kernel(TailArgs a) {
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = ch0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int co = mfma_row(ch0 + j * 32, r, lane);
       Hs[co][col] = fmaxf(fmaf(acc[j][r], a.s11[co], a.h11[co]), 0.f);
     }
   __syncthreads();
@@ -282,7 +180,7 @@ __global__ void __launch_bounds__(TAIL_TB) tail_kernel(TailArgs a) {
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = ch0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int co = mfma_row(ch0 + j * 32, r, lane);
       a.out[(size_t)b * CT + co] = fmaxf(fmaf(acc[j][r], a.s12[co], a.h12[co]), 0.f);
     }
 }
@@ -324,14 +222,18 @@ int instag_ave_encoder_forward(const instag_ave_encoder_weights* w, const float*
 
   int cur = 0;
   for (int l = 1; l <= 10; ++l) {
-    ConvArgs c{buf[cur], w->w[l], w->scale[l], w->shift[l], buf[cur ^ 1], n, LAYERS[l - 1]};
-    const int N = n * c.d.ho * c.d.wo;
-    if (c.d.cout == 32) {
-      conv_kernel<32><<<dim3((unsigned)div_up(N, 128), 1), TB, 0, st>>>(c);
+    const LayerDesc& d = LAYERS[l - 1];
+    ConvArgs c{};
+    c.in = buf[cur]; c.wt = w->w[l]; c.scale = w->scale[l]; c.shift = w->shift[l]; c.out = buf[cur ^ 1];
+    c.res = d.residual ? buf[cur] : nullptr;                     // cin == cout and the extents are kept
+    c.B = n; c.cin = c.c_split = d.cin; c.cout = d.cout; c.hi = d.hi; c.wi = d.wi; c.ho = d.ho; c.wo = d.wo;
+    c.stride_h = d.sh; c.stride_w = d.sw; c.relu = 1;
+    // 32 x 128 where cout == 32 (64 rows would idle half the MFMAs on the two largest activations), else 64 x 64
+    if (d.cout == 32) {
+      INSTAG_TRY((launch_conv_kernel<3, 1, 1, SRC_PLAIN>(c, st)));
     } else {
-      conv_kernel<64><<<dim3((unsigned)div_up(N, 64), (unsigned)(c.d.cout / 64)), TB, 0, st>>>(c);
+      INSTAG_TRY((launch_conv_kernel<3, 2, 1, SRC_PLAIN>(c, st)));
     }
-    INSTAG_CHECK_LAUNCH();
     cur ^= 1;
   }
 

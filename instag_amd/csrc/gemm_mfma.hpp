@@ -8,21 +8,16 @@
 // groups ride on blockIdx.z.  The epilogue works on the accumulator registers: + bias, erf-GELU, + residual (read at D's
 // index; D may be the residual itself).
 //
-// As in conv_mfma.hpp the tile is chosen per launch to fill the chip and does not enter the arithmetic: an output
-// element is one k-ordered FMA chain over all of K from 0 (the MFMA accumulates in place, which also halves the
-// accumulator registers against a partial sum per K tile), whatever tile it sat in.  K is a multiple of 32, N and lda
-// multiples of 4 (the operands are staged with 16-byte loads); M and N may end inside a tile.
+// The tile scheme is that of mfma_tile.hpp, in its in-place form.  As in conv_mfma.hpp the tile is chosen per launch to
+// fill the chip and does not enter the arithmetic: an output element is one k-ordered FMA chain over all of K from 0
+// (the MFMA accumulates in place, which also halves the accumulator registers against a partial sum per K tile),
+// whatever tile it sat in.  K is a multiple of 32, N and lda multiples of 4 (the operands are staged with 16-byte
+// loads); M and N may end inside a tile.
 #pragma once
-#include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace instag {
 namespace {
-
-constexpr int GEMM_TB = 256;
-constexpr int GEMM_BK = 32;
-constexpr int GEMM_MIN_BLOCKS = 512;    // two workgroups for each of the 256 CUs
-
-using gemm_f32x16 = __attribute__((ext_vector_type(16))) float;
 
 struct GemmArgs {
   const float* a;
@@ -43,12 +38,12 @@ __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + er
 
 // four waves as 2 x 2, each with WM x WN accumulators of 32 x 32: a workgroup owns 64 WM rows x 64 WN columns
 template <int WM, int WN>
-__global__ void __launch_bounds__(GEMM_TB) gemm_kernel(GemmArgs g) {
-  constexpr int BM = 64 * WM, BN = 64 * WN, BK = GEMM_BK;
+__global__ void __launch_bounds__(TB) gemm_kernel(GemmArgs g) {
+  constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr int LDA_S = BM + 4;                       // the transposed A tile: k-major, padded against bank conflicts
-  constexpr int NA = BM * BK / 4 / GEMM_TB;           // float4 a thread stages per K tile
-  constexpr int NB = BK * BN / 4 / GEMM_TB;
-  constexpr int BROWS = GEMM_TB / (BN / 4);           // K rows of W one pass of the workgroup covers
+  constexpr int NA = BM * BK / 4 / TB;                // float4 a thread stages per K tile
+  constexpr int NB = BK * BN / 4 / TB;
+  constexpr int BROWS = TB / (BN / 4);                // K rows of W one pass of the workgroup covers
   __shared__ float As[BK][LDA_S];
   __shared__ __attribute__((aligned(16))) float Bs[BK][BN];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1;
@@ -81,7 +76,7 @@ __global__ void __launch_bounds__(GEMM_TB) gemm_kernel(GemmArgs g) {
                     : make_float4(0.f, 0.f, 0.f, 0.f);
   };
 
-  gemm_f32x16 acc[WM][WN];
+  f32x16 acc[WM][WN];
 #pragma unroll
   for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -104,22 +99,10 @@ __global__ void __launch_bounds__(GEMM_TB) gemm_kernel(GemmArgs g) {
     for (int i = 0; i < NB; ++i) *reinterpret_cast<float4*>(&Bs[bk + BROWS * i][bn]) = rb[i];
     __syncthreads();
     if (kt + 1 < nk) load(kt + 1);
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-      const int k = kk * 2 + (lane >> 5);
-      float av[WM], bv[WN];
-#pragma unroll
-      for (int i = 0; i < WM; ++i) av[i] = As[k][(wr * WM + i) * 32 + (lane & 31)];
-#pragma unroll
-      for (int j = 0; j < WN; ++j) bv[j] = Bs[k][(wc * WN + j) * 32 + (lane & 31)];
-#pragma unroll
-      for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    }
+    mfma_k_tile<WM, WN, false>(As, Bs, wr * WM * 32, wc * WN * 32, lane, acc);
   }
 
-  // D: column (lane & 31) = n, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = m
+  // D: column = n, row = m
 #pragma unroll
   for (int j = 0; j < WN; ++j) {
     const int n = n0 + (wc * WN + j) * 32 + (lane & 31);
@@ -130,7 +113,7 @@ __global__ void __launch_bounds__(GEMM_TB) gemm_kernel(GemmArgs g) {
     for (int i = 0; i < WM; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m0 + (wr * WM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int m = mfma_row(m0 + (wr * WM + i) * 32, r, lane);
         if (m >= g.M) continue;
         const int b = m / g.rows, tt = m - b * g.rows;
         const int64_t o = (int64_t)b * g.d_batch + (int64_t)tt * g.ldd + col;
@@ -145,15 +128,15 @@ __global__ void __launch_bounds__(GEMM_TB) gemm_kernel(GemmArgs g) {
 template <int WM, int WN>
 int launch_gemm_tile(const GemmArgs& g, hipStream_t st) {
   const dim3 grid((unsigned)div_up(g.M, 64 * WM), (unsigned)div_up(g.N, 64 * WN), (unsigned)g.groups);
-  gemm_kernel<WM, WN><<<grid, GEMM_TB, 0, st>>>(g);
+  gemm_kernel<WM, WN><<<grid, TB, 0, st>>>(g);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }
 
 inline bool gemm_ok(const GemmArgs& g) {
-  return g.M >= 1 && g.rows >= 1 && g.M % g.rows == 0 && g.N >= 4 && g.N % 4 == 0 && g.K >= GEMM_BK &&
-         g.K % GEMM_BK == 0 && g.lda % 4 == 0 && g.a_batch % 4 == 0 && g.a_group % 4 == 0 && g.groups >= 1 &&
-         g.groups <= 65535 && div_up(g.N, 64) <= 65535;
+  return g.M >= 1 && g.rows >= 1 && g.M % g.rows == 0 && g.N >= 4 && g.N % 4 == 0 && g.K >= BK && g.K % BK == 0 &&
+         g.lda % 4 == 0 && g.a_batch % 4 == 0 && g.a_group % 4 == 0 && g.groups >= 1 && g.groups <= 65535 &&
+         div_up(g.N, 64) <= 65535;
 }
 
 // the largest tile that still gives every CU two workgroups (the arithmetic does not depend on the choice)
@@ -161,7 +144,7 @@ inline bool gemm_ok(const GemmArgs& g) {
 inline int launch_gemm(const GemmArgs& g, hipStream_t st, int tile = 0) {
   INSTAG_REQUIRE(gemm_ok(g), "gemm: K a multiple of 32, N, lda and the strides of A multiples of 4");
   auto blocks = [&](int wm, int wn) { return (int64_t)div_up(g.M, 64 * wm) * div_up(g.N, 64 * wn) * g.groups; };
-  if (tile == 0) tile = blocks(2, 2) >= GEMM_MIN_BLOCKS ? 3 : blocks(1, 2) >= GEMM_MIN_BLOCKS ? 2 : 1;
+  if (tile == 0) tile = blocks(2, 2) >= MIN_BLOCKS ? 3 : blocks(1, 2) >= MIN_BLOCKS ? 2 : 1;
   if (tile == 3) return launch_gemm_tile<2, 2>(g, st);
   if (tile == 2) return launch_gemm_tile<1, 2>(g, st);
   return launch_gemm_tile<1, 1>(g, st);

@@ -3,22 +3,22 @@
 //
 // Convolutions are implicit GEMMs on the f32-input MFMA (v_mfma_f32_32x32x2_f32): D[cout][m] = sum_k W[cout][k] X[k][m]
 // with m = (image, oy, ox) and k = (cin, ky, kx) gathered from NCHW activations, 64 x 64 x 32 tiles, four waves of one
-// 32 x 32 accumulator each.  The MFMA is a k-ordered fp32 FMA chain -- run per K tile of 32 and the tiles added in
-// order (blocked summation, see the K loop) -- and every other sum below runs in a fixed order (no float atomics), so
-// two runs give the same bits.  The data gradient of the stride-1 layers is the same kernel on
-// flipped, transposed weights (prepared by the caller); conv1 (stride 4, three input channels) has a gather kernel.
+// 32 x 32 accumulator each (the tile scheme of mfma_tile.hpp).  The MFMA is a k-ordered fp32 FMA chain -- run per K
+// tile of 32 and the tiles added in order (mfma_tile.hpp: blocked summation) -- and every other sum below runs in a
+// fixed order (no float atomics), so two runs give the same bits.  The data gradient of the stride-1 layers is the
+// same kernel on flipped, transposed weights (prepared by the caller); conv1 (stride 4, three input channels) has a
+// gather kernel.
 //
 // The patch size lives in device memory: every kernel derives the patch count and the layer extents from it, buffers
 // and grids are sized for the worst case of the declared range [p_min, p_max], and workgroups beyond the live extent
 // exit.  A captured launch sequence therefore serves every patch size of its range; a value outside the range makes
 // every kernel exit without touching memory.
-#include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace instag {
 namespace {
 
 constexpr int NTAP = 5;
-constexpr int TB = 256;
 
 struct Geo {
   const int32_t* p_dev;
@@ -70,9 +70,6 @@ struct ConvArgs {
   const float* bg;
   int Cin, Cout, Kreal, Kpad, both;
 };
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-constexpr int BK = 32;
 
 template <int KH, int S, int PAD, int EIN, int EOUT, int EPI, bool FIRST>
 __global__ void __launch_bounds__(TB) conv_kernel(ConvArgs a) {
@@ -149,9 +146,9 @@ __global__ void __launch_bounds__(TB) conv_kernel(ConvArgs a) {
     }
   };
 
-  f32x16 acc;
+  f32x16 acc[1][1];                                            // mfma_k_tile takes [WM][WN] accumulators
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int i = 0; i < 16; ++i) acc[0][0][i] = 0.f;
   const int nk = a.Kpad / BK;
   load(0);
   for (int kt = 0; kt < nk; ++kt) {
@@ -163,33 +160,19 @@ __global__ void __launch_bounds__(TB) conv_kernel(ConvArgs a) {
     }
     __syncthreads();
     if (kt + 1 < nk) load(kt + 1);
-    // blocked summation: each K tile is an FMA chain of 32 terms from zero, the tiles are then added in order.  One
-    // chain over the whole K (up to 4,800 terms) left the activations of conv2..5 2.5 - 3x further from the fp64 values
-    // than the library convolutions are (1.1e-5 against 4e-6 at magnitudes of 7); this form is at or below the
-    // library's error in every layer.  It matters where two pool inputs are within rounding of each other or a
-    // pre-activation is within rounding of zero: the backward pass then routes the gradient through another unit.
-    f32x16 part;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) part[i] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-      const float av = As[kk * 2 + (lane >> 5)][wr * 32 + (lane & 31)];
-      const float bv = Bs[kk * 2 + (lane >> 5)][wc * 32 + (lane & 31)];
-      part = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, part, 0, 0, 0);
-    }
-    acc += part;
+    mfma_k_tile<1, 1, true>(As, Bs, wr * 32, wc * 32, lane, acc);
   }
 
-  // D: column (lane & 31) = output position, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = output channel
+  // D: column = output position, row = output channel
   const int mc = m0 + wc * 32 + (lane & 31);
   if (mc >= M) return;
   const int oimg = mc / HWo, opos = mc - oimg * HWo;
   const size_t obase = (size_t)oimg * a.Cout * HWo + opos;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int co = c0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int co = mfma_row(c0 + wr * 32, r, lane);
     const size_t o = obase + (size_t)co * HWo;
-    float v = acc[r];
+    float v = acc[0][0][r];
     if (EPI == EPI_RELU) {
       v = fmaxf(v + a.bias[co], 0.f);
     } else if (EPI == EPI_MASKADD) {

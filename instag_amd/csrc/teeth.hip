@@ -22,7 +22,7 @@
 // element reads nothing but its own frame: a frame's outputs do not depend on the batch, the chunk or the tile it sat
 // in, and two runs give the same bits.
 #include "common.hpp"
-#include "conv_mfma.hpp"
+#include "conv_net.hpp"
 
 namespace instag {
 namespace {

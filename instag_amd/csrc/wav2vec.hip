@@ -16,7 +16,6 @@
 namespace instag {
 namespace {
 
-constexpr int TB = 256;
 constexpr int N_CONV = 7;
 constexpr int CONV_K[N_CONV] = {10, 3, 3, 3, 3, 2, 2};
 constexpr int CONV_S[N_CONV] = {5, 2, 2, 2, 2, 2, 2};
