@@ -3,7 +3,9 @@ constants are derived from its text.
 
 ``parse(text)`` -> (structs, protos, constants): struct typedef name -> ``ctypes.Structure`` subclass, function name ->
 ``(restype, [argtypes])``, ``#define INSTAG_*`` name -> int, each in the header's order.  It takes the C subset the header
-is written in and raises ValueError, naming the declaration, on anything else.
+is written in and raises ValueError, naming the declaration, on anything else.  The reader does
+not follow ``#include``: a header whose prototypes take a struct of another header is read with ``declared``, the
+structs that header gave (they are not returned again).
 """
 import ctypes as C
 import os
@@ -56,8 +58,9 @@ def _declarators(text, structs, what):
     return out
 
 
-def parse(text):
+def parse(text, declared=None):
     structs, protos, constants = {}, {}, {}
+    seen = dict(declared or {})                                      # what a declaration may point to: theirs and ours
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     for line in re.findall(r"^[ \t]*#.*$", text, flags=re.M):
         m = re.match(r"\s*#\s*define\s+(INSTAG_\w+)(.*)", line)
@@ -79,10 +82,10 @@ def parse(text):
         m = _STRUCT.match(text, pos)
         if m:
             tag, body, name = m.groups()
-            if tag not in ("", name) or name in structs:
+            if tag not in ("", name) or name in seen:
                 raise ValueError(f"{name}: struct tag {tag!r} differs from the typedef, or the struct is declared twice")
-            fields = [f for stmt in body.split(";") if stmt.strip() for f in _declarators(stmt, structs, name)]
-            structs[name] = type(class_name(name), (C.Structure,),
+            fields = [f for stmt in body.split(";") if stmt.strip() for f in _declarators(stmt, seen, name)]
+            seen[name] = structs[name] = type(class_name(name), (C.Structure,),
                                  {"_fields_": fields, "__doc__": f"struct {name} (include/instag_hip.h)."})
             end = m.end()
         else:
@@ -97,10 +100,10 @@ def parse(text):
                 ret = ret.replace("*", " * ").split()
                 if name in protos or not ret or any(s != "*" for s in ret[1:]):
                     raise ValueError(f"{name}: declared twice, or cannot read the return type {m.group(1).strip()!r}")
-                res = _ctype(ret[0], len(ret) - 1, structs, f"{name}: return type", ret=True)
+                res = _ctype(ret[0], len(ret) - 1, seen, f"{name}: return type", ret=True)
                 args = []
                 if params.strip() != "void":
-                    args = [t for p in params.split(",") for _, t in _declarators(p, structs, name)]
+                    args = [t for p in params.split(",") for _, t in _declarators(p, seen, name)]
                     if any(issubclass(t, C.Array) for t in args):
                         raise ValueError(f"{name}: an array parameter is a pointer in C: declare it as one")
                 class_name(name)                                     # (the instag_ prefix)
@@ -109,6 +112,6 @@ def parse(text):
     return structs, protos, constants
 
 
-def read(path=HEADER):
+def read(path=HEADER, declared=None):
     with open(path) as f:
-        return parse(f.read())
+        return parse(f.read(), declared)

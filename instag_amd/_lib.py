@@ -37,6 +37,11 @@ FACE_LOSS = {k[len("INSTAG_FACE_LOSS_"):]: v for k, v in _CONSTANTS.items() if k
 _WAV2VEC_STRUCTS, _WAV2VEC_PROTOTYPES, WAV2VEC = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_wav2vec.h"))
 globals().update((cls.__name__, cls) for cls in _WAV2VEC_STRUCTS.values())
 
+# The HuBERT encoder's part, include/instag_hubert.h, likewise: it declares no struct of its own and takes the wav2vec
+# header's weights, which the reader is told of; instag_hubert_* and the INSTAG_HUBERT_MAX_FRAMES bound.
+_HUBERT_STRUCTS, _HUBERT_PROTOTYPES, HUBERT = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_hubert.h"),
+                                                         _WAV2VEC_STRUCTS)
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -202,7 +207,7 @@ def lib():
         # "no ROCm-capable device is detected" from the second one.
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

@@ -60,6 +60,7 @@ SOURCES = {
     "track.hip": [],
     "mesh_render.hip": [],
     "wav2vec.hip": [],
+    "hubert.hip": [],
 }
 
 

@@ -44,8 +44,9 @@ class Wav2Vec2Dims:
     pos_groups: int = 16
     vocab: int = 44
 
-    def check(self) -> "Wav2Vec2Dims":
-        """The shapes csrc/wav2vec.hip takes (include/instag_wav2vec.h); ValueError naming the field otherwise."""
+    def check(self, head: bool = True) -> "Wav2Vec2Dims":
+        """The shapes csrc/wav2vec.hip takes (include/instag_wav2vec.h); ValueError naming the field otherwise.
+        ``head=False``: the network without its CTC head (csrc/hubert.hip), where ``vocab`` plays no part."""
         from . import _lib
         rules = (
             ("heads", self.heads >= 1 and self.hidden == self.heads * HEAD_DIM, f"hidden / heads must be {HEAD_DIM}"),
@@ -60,7 +61,7 @@ class Wav2Vec2Dims:
             ("vocab", 4 <= self.vocab <= 65536 and self.vocab % 4 == 0, "a multiple of 4"),
         )
         for field, ok, rule in rules:
-            if not ok:
+            if not ok and (head or field != "vocab"):
                 raise ValueError(f"wav2vec 2.0 config: {field} = {getattr(self, field)} is not supported: {rule}")
         return self
 
@@ -81,13 +82,14 @@ _REQUIRED = (("do_stable_layer_norm", True, False), ("feat_extract_norm", "layer
              ("layer_norm_eps", LN_EPS, LN_EPS))
 
 
-def dims_of(config) -> Wav2Vec2Dims:
+def dims_of(config, required=_REQUIRED, head: bool = True) -> Wav2Vec2Dims:
     """``config``: a Wav2Vec2Dims, or the dict of a config.json (the group-norm 'base' variant and anything else the
-    kernels are not written for raise ValueError naming the field)."""
+    kernels are not written for raise ValueError naming the field).  ``required``: the (field, value, default) rules;
+    ``head=False``: no CTC head, ``vocab_size`` may be missing."""
     if isinstance(config, Wav2Vec2Dims):
-        return config.check()
+        return config.check(head)
     cfg = dict(config)
-    for field, want, default in _REQUIRED:
+    for field, want, default in required:
         got = cfg.get(field, default)
         got = list(got) if isinstance(got, (list, tuple)) else got
         if got != want:
@@ -99,7 +101,8 @@ def dims_of(config) -> Wav2Vec2Dims:
         return Wav2Vec2Dims(conv_dim=int(conv_dim[0]), hidden=int(cfg["hidden_size"]), heads=int(cfg["num_attention_heads"]),
                             intermediate=int(cfg["intermediate_size"]), layers=int(cfg["num_hidden_layers"]),
                             pos_kernel=int(cfg.get("num_conv_pos_embeddings", 128)),
-                            pos_groups=int(cfg.get("num_conv_pos_embedding_groups", 16)), vocab=int(cfg["vocab_size"])).check()
+                            pos_groups=int(cfg.get("num_conv_pos_embedding_groups", 16)),
+                            vocab=int(cfg["vocab_size"] if head else cfg.get("vocab_size", 32))).check(head)
     except KeyError as e:
         raise ValueError(f"wav2vec 2.0 config: misses the field {e.args[0]!r}") from None
 
@@ -111,15 +114,16 @@ def frames_of(n: int) -> int:
     return n
 
 
-def macs(dims: Wav2Vec2Dims, n: int = RUN_SAMPLES) -> int:
-    """Multiply-accumulates of one run of ``n`` samples (the products only: MACS of the bench)."""
+def macs(dims: Wav2Vec2Dims, n: int = RUN_SAMPLES, head: bool = True) -> int:
+    """Multiply-accumulates of one run of ``n`` samples (the products only: MACS of the bench); ``head=False``: without
+    the CTC head's product."""
     d, t, total = dims, n, 0
     for l, (k, s) in enumerate(zip(CONV_KERNEL, CONV_STRIDE)):
         t = (t - k) // s + 1
         total += t * d.conv_dim * k * (1 if l == 0 else d.conv_dim)
     total += t * d.conv_dim * d.hidden + t * d.hidden * (d.hidden // d.pos_groups) * d.pos_kernel
     per_layer = 4 * d.hidden * d.hidden + 2 * d.hidden * d.intermediate + 2 * t * d.hidden
-    return total + d.layers * t * per_layer + t * d.hidden * d.vocab
+    return total + d.layers * t * per_layer + (t * d.hidden * d.vocab if head else 0)
 
 
 # ---- weights ----------------------------------------------------------------------------------------------------------
@@ -129,8 +133,8 @@ _POS_SPELLINGS = ((_POS + "weight_g", _POS + "weight_v"),
 _IGNORED = ("masked_spec_embed",)
 
 
-def _shapes(d: Wav2Vec2Dims) -> dict:
-    """Canonical key (no ``wav2vec2.`` prefix, the old weight-norm spelling) -> shape."""
+def _shapes(d: Wav2Vec2Dims, head: bool = True) -> dict:
+    """Canonical key (no ``wav2vec2.`` prefix, the old weight-norm spelling) -> shape; ``head``: with ``lm_head.*``."""
     s = {}
     for i, k in enumerate(CONV_KERNEL):
         p = f"feature_extractor.conv_layers.{i}."
@@ -154,20 +158,31 @@ def _shapes(d: Wav2Vec2Dims) -> dict:
         s[p + "feed_forward.output_dense.weight"] = (d.hidden, d.intermediate)
         s[p + "feed_forward.output_dense.bias"] = (d.hidden,)
         s[p + "final_layer_norm.weight"] = s[p + "final_layer_norm.bias"] = (d.hidden,)
-    s["lm_head.weight"] = (d.vocab, d.hidden)
-    s["lm_head.bias"] = (d.vocab,)
+    if head:
+        s["lm_head.weight"] = (d.vocab, d.hidden)
+        s["lm_head.bias"] = (d.vocab,)
     return s
 
 
-class Wav2Vec2Weights:
-    """The frozen parameters in fp32 on the CPU, under the checkpoint's keys without the ``wav2vec2.`` prefix; the
-    positional convolution's weight norm stays as its two factors (``weight_g`` [1,1,k], ``weight_v``)."""
+class EncoderWeights:
+    """What Wav2Vec2Weights and hubert.HubertWeights share: the frozen parameters in fp32 on the CPU, under the
+    checkpoint's keys without the model's prefix; the positional convolution's weight norm stays as its two factors
+    (``weight_g`` [1,1,k], ``weight_v``).  A subclass names its prefix, whether it has the CTC head, its config rules
+    and itself (for the messages)."""
+    PREFIX, HEAD, REQUIRED, WHAT = "wav2vec2.", True, _REQUIRED, "wav2vec 2.0"
 
     def __init__(self, dims: Wav2Vec2Dims, tensors: dict):
         self.dims, self.tensors = dims, tensors
 
     @classmethod
-    def load(cls, path) -> "Wav2Vec2Weights":
+    def dims_of(cls, config) -> Wav2Vec2Dims:
+        try:
+            return dims_of(config, cls.REQUIRED, cls.HEAD)
+        except ValueError as e:
+            raise ValueError(str(e).replace("wav2vec 2.0", cls.WHAT, 1)) from None
+
+    @classmethod
+    def load(cls, path):
         """``path``: the model directory (config.json beside pytorch_model.bin, or model.safetensors where the
         safetensors package imports)."""
         path = str(path)
@@ -189,37 +204,37 @@ class Wav2Vec2Weights:
         return cls.from_state_dict(sd, config)
 
     @classmethod
-    def from_state_dict(cls, sd, config) -> "Wav2Vec2Weights":
-        """``sd``: the keys of a ``Wav2Vec2ForCTC`` with or without the ``wav2vec2.`` prefix, the positional
+    def from_state_dict(cls, sd, config):
+        """``sd``: the keys of the ``transformers`` module with or without the model's prefix, the positional
         convolution's weight norm as ``weight_g`` / ``weight_v`` (old checkpoints) or
         ``parametrizations.weight.original0`` / ``original1``; ``masked_spec_embed`` and keys the network does not have
         are ignored.  A missing key, a wrong shape and an unsupported config field raise ValueError naming it."""
-        dims = dims_of(config)
-        flat = {(k[len("wav2vec2."):] if k.startswith("wav2vec2.") else k): v for k, v in sd.items()}
+        dims = cls.dims_of(config)
+        flat = {(k[len(cls.PREFIX):] if k.startswith(cls.PREFIX) else k): v for k, v in sd.items()}
         for old, new in zip(*_POS_SPELLINGS):
             if old not in flat and new in flat:
                 flat[old] = flat[new]
         tensors = {}
-        for key, shape in _shapes(dims).items():
+        for key, shape in _shapes(dims, cls.HEAD).items():
             if key not in flat:
-                raise ValueError(f"wav2vec 2.0 weights: the state dict misses {key!r}")
+                raise ValueError(f"{cls.WHAT} weights: the state dict misses {key!r}")
             t = torch.as_tensor(flat[key]).detach().to(device="cpu", dtype=torch.float32).contiguous()
             if tuple(t.shape) != shape:
-                raise ValueError(f"wav2vec 2.0 weights: {key!r} has shape {tuple(t.shape)}, the config says {shape}")
+                raise ValueError(f"{cls.WHAT} weights: {key!r} has shape {tuple(t.shape)}, the config says {shape}")
             tensors[key] = t.clone()
         return cls(dims, tensors)
 
     @classmethod
-    def random(cls, config=Wav2Vec2Dims(), seed: int = 0) -> "Wav2Vec2Weights":
+    def random(cls, config=Wav2Vec2Dims(), seed: int = 0):
         """Seeded stand-ins in the checkpoint's keys (tests, benches).  Matrices are drawn with a gain over
         1 / sqrt(fan-in): 1.4 in front of a GELU so that the LayerNorm behind it sees both of its sides, 1.5 for q and
         k so that the scores have a standard deviation near 2 and the attention is far from uniform, 1 elsewhere;
         LayerNorm gains are 1 +- 0.2, every bias and shift is 0.1 wide, and the head's gain is 1 so that the classes
         of a row differ by about the row's size."""
-        dims = dims_of(config)
+        dims = cls.dims_of(config)
         g = torch.Generator().manual_seed(seed)
         tensors = {}
-        for key, shape in _shapes(dims).items():
+        for key, shape in _shapes(dims, cls.HEAD).items():
             if key.endswith("weight_g"):
                 continue                        # follows weight_v, below
             if len(shape) == 1:
@@ -238,9 +253,11 @@ class Wav2Vec2Weights:
         tensors[_POS + "weight_g"] = norm * (1.0 + 0.1 * torch.randn(norm.shape, generator=g))
         return cls(dims, {k: t.float().contiguous() for k, t in tensors.items()})
 
-    def state_dict(self, prefix: str = "wav2vec2.", weight_norm: str = "parametrizations") -> dict:
-        """The keys of a ``Wav2Vec2ForCTC`` (``lm_head.*`` carries no prefix); ``weight_norm``: "parametrizations"
-        (torch >= 2.1 modules) or "weight_g" (old checkpoints)."""
+    def state_dict(self, prefix=None, weight_norm: str = "parametrizations") -> dict:
+        """The keys of the ``transformers`` module, under the model's prefix unless ``prefix`` says otherwise
+        (``lm_head.*`` carries none); ``weight_norm``: "parametrizations" (torch >= 2.1 modules) or "weight_g" (old
+        checkpoints)."""
+        prefix = self.PREFIX if prefix is None else prefix
         if weight_norm not in ("parametrizations", "weight_g"):
             raise ValueError(f"weight_norm 'parametrizations' or 'weight_g', got {weight_norm!r}")
         rename = dict(zip(*_POS_SPELLINGS)) if weight_norm == "parametrizations" else {}
@@ -290,7 +307,8 @@ class Wav2Vec2Weights:
         s.pos_w = put(self.pos_weight().reshape(d.pos_groups, cg, cg, d.pos_kernel).permute(0, 3, 2, 1).float())
         s.pos_b = put(t[_POS + "bias"])
         s.enc_ln_g, s.enc_ln_b = put(t["encoder.layer_norm.weight"]), put(t["encoder.layer_norm.bias"])
-        s.head_w, s.head_b = put(t["lm_head.weight"].t()), put(t["lm_head.bias"])
+        if self.HEAD:
+            s.head_w, s.head_b = put(t["lm_head.weight"].t()), put(t["lm_head.bias"])
         for l in range(d.layers):
             p = f"encoder.layers.{l}."
             qkv = [p + f"attention.{n}_proj." for n in "qkv"]
@@ -306,15 +324,30 @@ class Wav2Vec2Weights:
         return s, keep
 
 
+class Wav2Vec2Weights(EncoderWeights):
+    """The parameters of a ``Wav2Vec2ForCTC``: keys without the ``wav2vec2.`` prefix, ``lm_head.*`` among them."""
+
+
 # ---- plain-torch statement -------------------------------------------------------------------------------------------
 def wav2vec2_torch(weights: Wav2Vec2Weights, segments, taps=None):
     """``Wav2Vec2ForCTC(input_values=normalised segments).logits`` in eval mode, segments [B,n] -> [B,T,V], in the
     segments' dtype on their device; no attention mask.  ``taps``: a list that receives (name, tensor) of every stage,
     the attention probabilities [B,heads,T,T] of every layer among them."""
-    d = weights.dims
     x = torch.as_tensor(segments)
     if x.dim() != 2 or x.shape[1] < 400:
         raise ValueError(f"wav2vec2: segments [B, n >= 400], got {tuple(x.shape)}")
+    w = weights.to(x.device, x.dtype)
+    x = (x - x.mean(dim=1, keepdim=True)) / torch.sqrt(x.var(dim=1, keepdim=True, unbiased=False) + NORM_EPS)
+    out = F.linear(encoder_torch(weights, x, taps), w["lm_head.weight"], w["lm_head.bias"])
+    if taps is not None:
+        taps.append(("logits", out))
+    return out
+
+
+def encoder_torch(weights: EncoderWeights, x, taps=None):
+    """The network behind the samples' normalisation, up to and including the encoder's last LayerNorm: input values
+    [B,n] -> [B,T,hidden].  What ``wav2vec2_torch`` and ``hubert.hubert_torch`` share."""
+    d = weights.dims
     w = weights.to(x.device, x.dtype)
 
     def tap(name, v):
@@ -325,7 +358,6 @@ def wav2vec2_torch(weights: Wav2Vec2Weights, segments, taps=None):
     def ln(v, prefix, dim):
         return F.layer_norm(v, (dim,), w[prefix + ".weight"], w[prefix + ".bias"], LN_EPS)
 
-    x = (x - x.mean(dim=1, keepdim=True)) / torch.sqrt(x.var(dim=1, keepdim=True, unbiased=False) + NORM_EPS)
     x = x.unsqueeze(1)
     for i, stride in enumerate(CONV_STRIDE):
         p = f"feature_extractor.conv_layers.{i}."
@@ -349,7 +381,7 @@ def wav2vec2_torch(weights: Wav2Vec2Weights, segments, taps=None):
                             w[p + "feed_forward.intermediate_dense.bias"]))
         h = tap(f"layer{l}.feed_forward", h + F.linear(y, w[p + "feed_forward.output_dense.weight"],
                                                        w[p + "feed_forward.output_dense.bias"]))
-    return tap("logits", F.linear(ln(h, "encoder.layer_norm", d.hidden), w["lm_head.weight"], w["lm_head.bias"]))
+    return ln(h, "encoder.layer_norm", d.hidden)
 
 
 # ---- HIP operator -----------------------------------------------------------------------------------------------------

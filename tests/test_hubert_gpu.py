@@ -1,0 +1,205 @@
+"""GPU tests of the HuBERT operator (csrc/hubert.hip): the streaming-softmax attention alone against fp64
+softmax(q k^T / 8) v at every length that takes another path (one key, a key short of a tile, a tile, a key more, two
+tiles, the real clip) and on crafted rows, then the network against golden G17 and the fp64 CPU statement, every stage
+through the debug taps, batch, tile and call independence bit for bit, the frame bound and the features of a wav.
+
+Tolerance: that of test_wav2vec_gpu.py.  e32 = max|fp32 torch statement on the CPU - fp64| / max|fp64| is measured on
+each test's own inputs and must lie in (1e-8, 1e-4); the operator must be within 8 x e32 of the fp64 result (relative
+to its largest entry).  One key is the exception: the softmax is 1 and the output is v in any precision, so e32 is 0
+and the operator has to be exact.  Every test prints the operator's error beside e32 and the bar before it asserts.
+The input conditions (a softmax row above 2 / T, no dead row or stage, the crafted rows' patterns) are tests/
+test_hubert_host.py's, on the same cached cases.
+
+Observed on an MI355X.  Attention alone: e32 6.7e-8 .. 1.6e-6, operator 1.0e-7 .. 1.5e-6, 0.5 .. 3.9 x e32 (the
+largest ratio at T = 2; at T = 1000 0.7 .. 1.6 x); one key exact; the crafted rows at 0.4 .. 2.9 x their own row's e32
+(T = 1000: rising 0.8, first 1.1, equal 2.9, huge 1.8, spike 1.0).  Network: G17 e32 6.6e-7, operator 8.8e-7; config S
+e32 3.6e-7 .. 8.3e-7, operator 4.0e-7 .. 2.7e-6, at most 4.1 x e32 (n = 320000; n = 320080: 3.4 x); config O at most
+2.2 x; stage by stage 0.7 .. 4.9 x the stage's own e32 (the largest: S at n = 64400 behind the first attention); the
+chunked call 3.0 x; the features of a wav differ from the torch chain's by 1.04e-5 under a bound of 2.59e-5.
+scripts/bench_hubert.py (profiles/hubert_bench.json): the three clips of a one-minute wav at the real size take 27.9 ms
+against 34.4 ms for hubert_torch in fp32 (0.81 x, bar 1.05 x); the attention kernel takes 96.3 us per layer at B = 2,
+T = 1000 (85.1 TFLOP/s) against 110.1 us for torch's scaled_dot_product_attention in fp32, 54.9 us against 103.4 us at
+B = 1, T = 999.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests import hubert_helpers as H
+
+pytestmark = pytest.mark.gpu
+
+FACTOR = 8.0
+GUARD = 4096
+
+
+def _check(name, got, want, e32, scale):
+    err = float((got.detach().double().cpu() - want).abs().max()) / scale
+    print(f"{name}: operator {err:.3e} e32 {e32:.3e} bar {FACTOR * e32:.3e} scale {scale:.3e} ratio {err / max(e32, 1e-30):.2f}")
+    assert tuple(got.shape) == tuple(want.shape) and got.dtype == torch.float32
+    assert bool(torch.isfinite(got).all())
+    assert err <= FACTOR * e32, (name, err, e32)
+
+
+def _attention_with_guards(case):
+    """instag_hubert_attention into the middle of a buffer of NaN-free sentinels: ctx, the guards around it, qkv after."""
+    from instag_amd import _lib
+    qkv = case.qkv.cuda()
+    before = qkv.clone()
+    B, T, H = case.B, case.T, 64 * case.heads
+    buf = torch.full((GUARD + B * T * H + GUARD,), -7.25, dtype=torch.float32, device="cuda")
+    ctx = buf[GUARD:GUARD + B * T * H].view(B, T, H)
+    _lib.check_arg(_lib.lib().instag_hubert_attention(_lib.ptr(qkv), _lib.ptr(ctx), B, T, case.heads, _lib.current_stream()),
+                   "hubert_attention")
+    torch.cuda.synchronize()
+    assert torch.equal(qkv, before)
+    assert bool((buf[:GUARD] == -7.25).all()) and bool((buf[GUARD + B * T * H:] == -7.25).all())
+    return ctx
+
+
+@pytest.mark.parametrize("T,heads,B", H.ATTENTION_SHAPES)
+def test_attention_matches_fp64(T, heads, B):
+    from instag_amd.hubert import attention
+    case = H.attention_case(T, heads, B)
+    e32, scale = case.e32()
+    ctx = _attention_with_guards(case)
+    _check(f"attention T={T} heads={heads} B={B}", ctx, case.want, e32, scale)
+    assert torch.equal(attention(case.qkv.cuda(), heads), ctx)      # the Python entry, and a second call: the same bits
+    if B == 2:                                                      # a segment's bits do not depend on its batch
+        assert torch.equal(attention(case.qkv[1:].cuda(), heads)[0], ctx[1])
+
+
+@pytest.mark.parametrize("T", [200, 1000])
+def test_attention_crafted_rows(T):
+    """Rows that rescale on every tile, peak at key 0, are flat, need the running maximum, or peak at the first key of
+    the last, partial tile: each within the bar of the whole output and, sharper, of its own row."""
+    case = H.attention_case(T, 1, 1, crafted=True)
+    e32, scale = case.e32()
+    ctx = _attention_with_guards(case)
+    _check(f"crafted T={T}", ctx, case.want, e32, scale)
+    for name, r in case.rows.items():
+        row_scale = float(case.want[0, r].abs().max())
+        row_e32 = max(float((case.got32[0, r] - case.want[0, r]).abs().max()) / row_scale, 2.0 ** -24)
+        err = float((ctx[0, r].double().cpu() - case.want[0, r]).abs().max()) / row_scale
+        print(f"  {name} (row {r}): operator {err:.3e} row e32 {row_e32:.3e} bar {FACTOR * row_e32:.3e}")
+        assert err <= FACTOR * row_e32, (name, err, row_e32)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    """One operator per config, kept for the module."""
+    from instag_amd.hubert import HubertEncoder
+    return {name: HubertEncoder(H.weights(name), "cuda") for name in H.CONFIGS}
+
+
+def test_hidden_matches_g17(golden_dir):
+    from instag_amd.hubert import HubertEncoder, normalise_utterance
+    g17 = np.load(f"{golden_dir}/g17_hubert.npz")
+    w = H.weights("S", int(g17["weights_seed"]))
+    values = normalise_utterance(torch.from_numpy(g17["audio"].astype(np.float32))[0])[None]
+    assert torch.equal(values, torch.from_numpy(g17["input_values"]).float())
+    case = H.Case(w, values)
+    want = torch.from_numpy(g17["last_hidden_state"])
+    scale = float(want.abs().max())
+    e32 = float((case.got32 - want).abs().max()) / scale            # (the golden starts from the fp64 input values)
+    assert H.E32_WINDOW[0] < e32 < H.E32_WINDOW[1], e32
+    got = HubertEncoder(w, "cuda").hidden(values.cuda())
+    assert got.is_cuda and not got.requires_grad
+    _check("g17", got, want, e32, scale)
+
+
+@pytest.mark.parametrize("n", [400, 719, 6130, 41200, 41520, 320000, 320080])
+@pytest.mark.parametrize("B", [1, 2])
+def test_config_s_matches_fp64(ops, B, n):
+    case = H.case("S", n)
+    assert case.T == {400: 1, 719: 1, 6130: 18, 41200: 128, 41520: 129, 320000: 999, 320080: 1000}[n]
+    e32, scale = case.e32(slice(0, B))
+    got = ops["S"].hidden(case.values[:B].cuda())
+    _check(f"S B={B} n={n}", got, case.want[:B], e32, scale)
+
+
+@pytest.mark.parametrize("n", [400, 6130, 64400])
+def test_config_o_matches_fp64(ops, n):
+    case = H.case("O", n)
+    assert case.T == {400: 1, 6130: 18, 64400: 201}[n]
+    e32, scale = case.e32()
+    got = ops["O"].hidden(case.values.cuda())
+    _check(f"O n={n}", got, case.want, e32, scale)
+
+
+@pytest.mark.parametrize("name,n", [("S", 6130), ("O", 6130), ("S", 64400), ("O", 64400)])
+def test_every_stage_matches_fp64(ops, name, n):
+    """The operator's debug taps against the statement's, stage by stage: each within 8 x that stage's own e32."""
+    from instag_amd.hubert import hubert_torch
+    case = H.case(name, n)
+    want = {k: v for k, v in case.taps if not k.endswith("attn_probs") and k != "hidden"}
+    taps32 = []
+    hubert_torch(case.w, case.values.float(), taps32)
+    got = []
+    hidden = ops[name].hidden(case.values.cuda(), taps=got)
+    assert [k for k, _ in got] == list(want)
+    assert torch.equal(hidden, ops[name].hidden(case.values.cuda()))
+    for (k, g), (_, s32) in zip(got, [kv for kv in taps32 if kv[0] in want]):
+        scale = float(want[k].abs().max())
+        e32 = float((s32.double() - want[k]).abs().max()) / scale
+        assert 1e-8 < e32 < 1e-4, (k, e32)
+        _check(f"{name} n={n} {k}", g, want[k], e32, scale)
+
+
+def test_too_many_frames_is_an_argument_error(ops):
+    from instag_amd import _lib
+    bound = _lib.HUBERT["INSTAG_HUBERT_MAX_FRAMES"]
+    n = 400 + 320 * bound                                   # bound + 1 frames
+    with pytest.raises(ValueError, match="INSTAG_HUBERT_MAX_FRAMES"):
+        ops["S"].hidden(torch.zeros(1, n, device="cuda"))
+    with pytest.raises(ValueError):
+        ops["S"].hidden(torch.zeros(1, 399, device="cuda"))
+    w, L = ops["S"], _lib.lib()
+    one = torch.full((64,), 3.0, device="cuda")
+    rc = L.instag_hubert_forward(C.byref(w._struct), _lib.ptr(one), 1, n, _lib.ptr(one), _lib.ptr(one), 4 * one.numel(), 0,
+                                 None, _lib.current_stream())
+    assert rc == _lib.E_ARG
+    torch.cuda.synchronize()
+    assert bool((one == 3.0).all())                         # nothing was launched
+
+
+def test_bits_do_not_depend_on_call_operator_batch_or_tile():
+    """Two calls and a second operator give the same bits; segment b of a chunked call over max_batch + 1 segments
+    (max_batch = 2) equals the single-segment call bit for bit; so does every GEMM tile."""
+    from instag_amd.hubert import HubertEncoder
+    case = H.case("S", 64400, 3)
+    w, values = case.w, case.values.cuda()
+    op = HubertEncoder(w, "cuda", max_batch=2)
+    first = op.hidden(values).clone()
+    assert torch.equal(first, op.hidden(values)) and float(first.abs().max()) > 0
+    assert torch.equal(first, HubertEncoder(w, "cuda").hidden(values))
+    for b in range(3):
+        assert torch.equal(op.hidden(values[b:b + 1])[0], first[b]), b
+    assert not torch.equal(first[0], first[2])
+    for tile in (1, 2, 3):
+        assert torch.equal(HubertEncoder(w, "cuda", tile=tile).hidden(values), first), tile
+    e32, scale = case.e32()
+    _check("chunked", first, case.want, e32, scale)
+
+
+def test_features_of_a_wav():
+    """hubert_features on the GPU == the same with the torch statement (fp32, on the GPU) in place of the operator: one
+    full clip of 1000 rows plus a remainder of 31.  Both are within 8 x e32 (the operator, tested above) and e32 (the
+    statement) of the fp64 rows, so they differ by at most 9 e32 scale per entry, as test_features_to_frame_codes of
+    test_wav2vec_gpu.py argues."""
+    from instag_amd.hubert import hubert_features, hubert_torch
+    w = H.weights("S")
+    wav, clips = H.features_wav()
+    e32, scale = 0.0, 0.0
+    for clip in clips:
+        e, sc = clip.e32()
+        e32, scale = max(e32, e), max(scale, sc)
+    feats_h = hubert_features(wav, w, "cuda")
+    feats_t = hubert_features(wav, w, "cuda", encoder=hubert_torch)
+    assert feats_h.shape == feats_t.shape == (515, 2, 128) and feats_h.dtype == np.float32
+    delta = (FACTOR + 1.0) * e32 * scale
+    diff = float(np.abs(feats_h - feats_t).max())
+    print(f"features: diff {diff:.3e} bound {delta:.3e} (e32 {e32:.3e} scale {scale:.3e})")
+    assert diff <= delta and float(np.abs(feats_t).max()) > 0
