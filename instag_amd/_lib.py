@@ -42,6 +42,10 @@ globals().update((cls.__name__, cls) for cls in _WAV2VEC_STRUCTS.values())
 _HUBERT_STRUCTS, _HUBERT_PROTOTYPES, HUBERT = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_hubert.h"),
                                                          _WAV2VEC_STRUCTS)
 
+# The per-frame codes of a 'hubert' head, include/instag_frame_code_wide.h: the three instag_frame_code_wide_* entry
+# points (instag_amd/audio.py), no struct and no constant.
+_, _FRAME_CODE_WIDE_PROTOTYPES, _ = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_frame_code_wide.h"))
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -207,7 +211,8 @@ def lib():
         # "no ROCm-capable device is detected" from the second one.
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES}.items():
+        for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
+                                  **_FRAME_CODE_WIDE_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

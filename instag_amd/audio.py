@@ -6,6 +6,8 @@ Replaces, on the device, the reference's chain
 (~11 conv1d / GEMM launches plus activations, three times that in backward) by one launch each way.
 A network built with audio_extractor == 'ave' has AudioNet_ave (scene/motion_net.py:132-149: three linear layers on
 [8, 1, 512] windows) in AudioNet's place: the instag_frame_code_ave_* pair, 20 parameters instead of 26.
+A 'hubert' network has the stock AudioNet at dim_in 1024 / mid 128 on windows of two samples, [8, 1024, 2]: the
+instag_frame_code_wide_* pair, the 26 parameters of the stock family.
 """
 from __future__ import annotations
 
@@ -45,6 +47,7 @@ class _Variant:
 
 _STOCK = _Variant("frame_code", True)          # AudioNet: a [8, dim_in, 16], dims (dim_in, mid, dim_aud), 26 parameters
 _AVE = _Variant("frame_code_ave", False)       # AudioNet_ave: a [8, 512], dims (dim_aud,), 20 parameters
+_WIDE = _Variant("frame_code_wide", False)     # AudioNet of a 'hubert' head: a [8, dim_in, 2], dims and parameters of _STOCK
 
 
 class _FrameCodes(torch.autograd.Function):
@@ -89,7 +92,7 @@ class _FrameCodes(torch.autograd.Function):
         d_enc_e = d_enc_e.contiguous().float() if (ctx.has_e and d_enc_e is not None) else None
         grads = [None if p is None else torch.empty_like(p) for p in params]
         # stock: eight workgroups (one per audio window), each with its own row of parameter gradients in `ws`;
-        # 'ave': sixteen workgroups write disjoint rows of the two large weight gradients, no workspace
+        # 'ave' / wide: sixteen workgroups write disjoint rows of the large weight gradients, no workspace
         ws = torch.empty(variant.symbol("backward_workspace_bytes")(*dims), dtype=torch.uint8,
                          device=a.device) if (variant.workspace and SPLIT_BACKWARD) else None
         check(variant.symbol("backward")(ptr(a), ptr(e), _ptr_array(params), ptr(saved), ptr(d_enc_a), ptr(d_enc_e),
@@ -186,14 +189,16 @@ def supported(field, a, e) -> bool:
         if tuple(a.shape[1:]) != (1, 512) or _module_params_ave(field) is None:
             return False
         return _lib.lib().instag_frame_code_ave_saved_floats(field.audio_att_net.dim_aud) > 0
-    if a.shape[2] != 16:
+    if a.shape[2] not in (16, 2):
         return False
     params = _module_params(field)
     if params is None or a.shape[1] != field.audio_net.encoder_conv[0].in_channels:
         return False
-    L = _lib.lib()
-    return L.instag_frame_code_saved_floats(a.shape[1], field.audio_net.encoder_conv[0].out_channels,
-                                            field.audio_att_net.dim_aud) > 0
+    # windows of two samples (a 'hubert' head): the wide family, which answers -1 unless mid == 128 and dim_in is one
+    # of its sizes
+    variant = _STOCK if a.shape[2] == 16 else _WIDE
+    return variant.symbol("saved_floats")(a.shape[1], field.audio_net.encoder_conv[0].out_channels,
+                                          field.audio_att_net.dim_aud) > 0
 
 
 def frame_codes(field, a, e):
@@ -215,7 +220,7 @@ def frame_codes(field, a, e):
     if entry is not None and (handle in entry[1] or len(entry[1]) < _ARRIVAL_SLOTS):
         slot = entry[1].setdefault(handle, len(entry[1]))
         arrivals = entry[0][slot:slot + 1]
-    elif ave:
+    elif ave or a.shape[2] == 2:
         arrivals = None                         # no word this call can own: the single-workgroup forward needs none
     else:
         arrivals = torch.zeros(1, dtype=torch.int32, device=a.device)      # owned by this call (and its capture) only
@@ -225,5 +230,5 @@ def frame_codes(field, a, e):
                                          *params)
     else:
         dims = (int(a.shape[1]), int(field.audio_net.encoder_conv[0].out_channels), int(field.audio_att_net.dim_aud))
-        enc_a, enc_e = _FrameCodes.apply(a, e_flat, _STOCK, dims, arrivals, *params)
+        enc_a, enc_e = _FrameCodes.apply(a, e_flat, _STOCK if a.shape[2] == 16 else _WIDE, dims, arrivals, *params)
     return enc_a, (enc_e if e is not None else None)

@@ -11,18 +11,20 @@
 //   linear 8->8, softmax, enc_a = sum_t y[t] * feat[t]
 //   expression: relu(W1[16x5] e[:5]), W2[5x16], enc_e = (.., e[5])
 //
-// Two kernel families share that tail: the stock AudioNet (frame_code_*) and AudioNet_ave (frame_code_ave_*, below).
+// Three kernel families share that tail: the stock AudioNet on windows of 16 samples (frame_code_*), AudioNet_ave
+// (frame_code_ave_*, below) and the wide AudioNet of a 'hubert' head on windows of two samples (frame_code_wide_*, last).
 // Their front parts are different algorithms and stay apart; everything behind the feature block [8][A] exists once:
 //   att_layer / att_layout / stage_attention  the attention layer table, its LDS segments and their staging
 //   attention_forward<T, SPLIT_CONV>          AudioAttNet + expression MLP forward (all three forward kernels)
 //   attention_backward                        their backward (both backward kernels)
 //   last_to_arrive                            the hand-off of a split forward to its last workgroup
 #include "common.hpp"
+#include "instag_frame_code_wide.h"
 
 namespace instag {
 namespace {
 
-constexpr int FT = 1024;          // threads of the single workgroup
+constexpr int FT = 1024;         // threads of the single workgroup
 constexpr int NB = 8;             // audio windows per frame (= attention sequence length)
 constexpr int WIN = 16;
 constexpr float SLOPE = 0.02f;
@@ -650,28 +652,45 @@ inline bool ave_dims_ok(int A) {
          ave_forward_floats(A) * sizeof(float) <= 160u * 1024u;
 }
 
-// sum_k row[k] * x[w][k] (k < K) for the window w = lane >> 3, in every lane.  x [8][K] lives in LDS (16-byte aligned);
-// `vec`: row is 16-byte aligned.  A lane multiplies its K / 64 weights with all eight windows, then the eight partial
-// sums per lane are folded: three exchange steps that halve the windows a lane holds, three plain steps.
-template <int K>
+// The eight partial sums a lane holds, one per window, added up over the wave: the sum of window w = lane >> 3 in every
+// lane.  Three exchange steps that halve the windows a lane holds, three plain steps; the order is fixed.
+__device__ __forceinline__ float wave_fold8(const float (&acc)[NB], int lane) {
+  const bool h5 = (lane & 32) != 0, h4 = (lane & 16) != 0, h3 = (lane & 8) != 0;
+  float u[4], t2[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) u[i] = (h5 ? acc[4 + i] : acc[i]) + __shfl_xor(h5 ? acc[i] : acc[4 + i], 32);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) t2[i] = (h4 ? u[2 + i] : u[i]) + __shfl_xor(h4 ? u[i] : u[2 + i], 16);
+  float r = (h3 ? t2[1] : t2[0]) + __shfl_xor(h3 ? t2[0] : t2[1], 8);
+  r += __shfl_xor(r, 4);
+  r += __shfl_xor(r, 2);
+  r += __shfl_xor(r, 1);
+  return r;
+}
+
+// sum_k w[k] * x[w][k] (k < K) for the window w = lane >> 3, in every lane.  x [8][K] lives in LDS (16-byte aligned).
+// STRIDE == 1: w = row, a dense row (`vec`: it is 16-byte aligned).  STRIDE == 3: w[k] = row[3 k + 1], the centre taps
+// of a k3 convolution row [K][3] whose outer taps only meet padding: they are not loaded.  A lane multiplies its K / 64
+// weights with all eight windows, then wave_fold8.
+template <int K, int STRIDE = 1>
 __device__ __forceinline__ float wave_dot8(const float* __restrict__ row, bool vec, const float* x, int lane) {
-  constexpr int V = K >= 256 ? 4 : 2;         // consecutive floats per lane and chunk
+  constexpr int V = K >= 256 ? 4 : K >= 128 ? 2 : 1;         // consecutive weights per lane and chunk
   constexpr int NC = K / (64 * V);
   float w[NC][V];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    const float* src = row + c * 64 * V + lane * V;
-    if (vec) {
+    const float* src = row + (c * 64 * V + lane * V) * STRIDE + STRIDE / 2;
+    if (STRIDE == 1 && V > 1 && vec) {
       if constexpr (V == 4) {
         const float4 t = *reinterpret_cast<const float4*>(src);
         w[c][0] = t.x; w[c][1] = t.y; w[c][2] = t.z; w[c][3] = t.w;
-      } else {
+      } else if constexpr (V == 2) {
         const float2 t = *reinterpret_cast<const float2*>(src);
         w[c][0] = t.x; w[c][1] = t.y;
       }
     } else {
 #pragma unroll
-      for (int j = 0; j < V; ++j) w[c][j] = src[j];
+      for (int j = 0; j < V; ++j) w[c][j] = src[j * STRIDE];
     }
   }
   float acc[NB];
@@ -684,24 +703,16 @@ __device__ __forceinline__ float wave_dot8(const float* __restrict__ row, bool v
       if constexpr (V == 4) {
         const float4 t = *reinterpret_cast<const float4*>(xs);
         s0 += w[c][0] * t.x; s0 += w[c][1] * t.y; s0 += w[c][2] * t.z; s0 += w[c][3] * t.w;
-      } else {
+      } else if constexpr (V == 2) {
         const float2 t = *reinterpret_cast<const float2*>(xs);
         s0 += w[c][0] * t.x; s0 += w[c][1] * t.y;
+      } else {
+        s0 += w[c][0] * xs[0];
       }
     }
     acc[b] = s0;
   }
-  const bool h5 = (lane & 32) != 0, h4 = (lane & 16) != 0, h3 = (lane & 8) != 0;
-  float u[4], t2[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) u[i] = (h5 ? acc[4 + i] : acc[i]) + __shfl_xor(h5 ? acc[i] : acc[4 + i], 32);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) t2[i] = (h4 ? u[2 + i] : u[i]) + __shfl_xor(h4 ? u[i] : u[2 + i], 16);
-  float r = (h3 ? t2[1] : t2[0]) + __shfl_xor(h3 ? t2[0] : t2[1], 8);
-  r += __shfl_xor(r, 4);
-  r += __shfl_xor(r, 2);
-  r += __shfl_xor(r, 1);
-  return r;
+  return wave_fold8(acc, lane);
 }
 
 // vec: bit 0 / 1 / 2 = the weight of fc1 / fc2 / fc3 is 16-byte aligned
@@ -865,6 +876,304 @@ inline int set_ave_lds_limit() {
   return set_max_dynamic_lds(reinterpret_cast<const void*>(frame_code_ave_backward_kernel), 160 * 1024);
 }
 
+// ---- the 'hubert' extractor: the wide AudioNet -----------------------------------------------------------------
+// AudioNet(dim_in = D, dim_aud = A) on windows a [8][D][2] (scene/motion_net.py:67-99 with D = 1024): the slice keeps
+// both samples, the lengths go 2 -> 1 -> 1 -> 1 -> 1, and the four k3 s2 p1 convolutions D -> 128 -> 128 -> 64 -> 64 are
+// linear layers in disguise:
+//   conv1   z1[b][co] = bias[co] + sum_ci (w[co][ci][1] a[b][ci][0] + w[co][ci][2] a[b][ci][1])   tap 0 meets padding only
+//   conv2-4 only the centre tap w[co][ci][1] is live
+// then Linear 64 -> 64 (leaky), Linear 64 -> A, AudioAttNet and the expression MLP as everywhere.  The parameters are
+// the 26 of frame_code_*; the design is the 'ave' one: nothing of conv1 (1.5 MB at D = 1024) or conv2 passes
+// through LDS in the forward pass, a wave owns an output neuron (wave_dot8 / wave_dot8_taps), dead taps are neither read for a product nor
+// multiplied by zero, and their gradients are written as zeros.
+//   forward : conv1's 128 neurons are split over the workgroups of the launch; the last one to arrive runs conv2 .. fc2
+//             (weights straight from global memory, one neuron per wave), the attention stage and the expression MLP.
+//             A launch of ONE workgroup does everything and needs no arrival word.
+//   backward: every workgroup stages the small tail's weights (fc2, fc1, the centre taps of conv4 and conv3, the eight
+//             columns of conv2's centre taps that belong to ITS conv1 neurons) in one round of loads, repeats the tail
+//             down to d z1 of its 8 neurons, then writes its rows of dW1 (3 D contiguous floats each: tap 0 zero, taps 1
+//             and 2 eight-term sums in window order) and db1.  Workgroup 0 writes every other gradient.  No workspace,
+//             no float atomics, no reduce launch.
+constexpr int WIDE_M = 128, WIDE_C = 64;
+constexpr int WIDE_WG = 16;       // workgroups of the split passes
+constexpr int WIDE_ROWS = WIDE_M / WIDE_WG;
+constexpr int WIDE_WAVES = FT / 64;
+constexpr int WIDE_MAX_CHUNKS = 4;             // D = 256 chunks of 4 channels x 64 lanes
+
+struct WideDims { int D, A, has_exp; };
+
+// float offsets inside the saved block (and its LDS copy): z1, z2 [8][128], z3, z4, f1 [8][64] (all after their
+// LeakyReLU), f2 [8][A], then FrameLayout's xt .. eh
+struct WideLayout { int z1, z2, z3, z4, f1, f2, att, end; };
+__host__ __device__ inline WideLayout wide_layout(int A) {
+  const FrameLayout L = frame_layout(1, 1, A);
+  WideLayout Y;
+  Y.z1 = 0;
+  Y.z2 = Y.z1 + NB * WIDE_M;
+  Y.z3 = Y.z2 + NB * WIDE_M;
+  Y.z4 = Y.z3 + NB * WIDE_C;
+  Y.f1 = Y.z4 + NB * WIDE_C;
+  Y.f2 = Y.f1 + NB * WIDE_C;
+  Y.att = Y.f2 + NB * A;
+  Y.end = Y.att + (L.end - L.xt);
+  return Y;
+}
+
+// backward: the tail's weights [fc2 A x 64][fc1 64 x 64][conv4 centre 64 x 64][conv3 centre 64 x 128]; the windows
+// [8][2 D] take the same floats once the tail is through
+__host__ __device__ inline int wide_tail_floats(int A) { return A * WIDE_C + 2 * WIDE_C * WIDE_C + WIDE_C * WIDE_M; }
+__host__ __device__ inline int wide_region_floats(int D, int A) { return max(NB * 2 * D, wide_tail_floats(A)); }
+
+inline size_t wide_forward_floats(int D, int A) {
+  return (size_t)NB * 2 * D + wide_layout(A).end + att_floats(A) + 4;
+}
+inline size_t wide_backward_floats(int D, int A) {
+  return (size_t)wide_region_floats(D, A) + WIDE_M * WIDE_ROWS + 2 * (size_t)wide_layout(A).end + att_floats(A);
+}
+inline bool wide_dims_ok(int D, int M, int A) {
+  if (M != WIDE_M || D < 256 || D > 256 * WIDE_MAX_CHUNKS || D % 256 != 0 || A < 1 || A > 4096) return false;
+  return wide_backward_floats(D, A) * sizeof(float) <= 160u * 1024u &&
+         wide_forward_floats(D, A) * sizeof(float) <= 160u * 1024u;
+}
+
+// conv1 of the wide AudioNet, one output neuron: sum_ci (row[ci][1] x[w][ci][0] + row[ci][2] x[w][ci][1]) for the window
+// w = lane >> 3, in every lane.  row [D][3] in global memory (`vec`: 16-byte aligned), x [8][D][2] in LDS, nc = D / 256.
+// A lane takes four channels per chunk: 12 contiguous weights (three 16-byte loads, all chunks' loads issued before
+// the first product) against 8 contiguous window floats (two 16-byte LDS reads); tap 0 takes no part.
+__device__ __forceinline__ float wave_dot8_taps(const float* __restrict__ row, bool vec, const float* x, int lane,
+                                                int nc) {
+  float w[WIDE_MAX_CHUNKS][12];
+#pragma unroll
+  for (int c = 0; c < WIDE_MAX_CHUNKS; ++c) {
+    if (c < nc) {
+      const float* src = row + (c * 256 + lane * 4) * 3;
+      if (vec) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const float4 t = reinterpret_cast<const float4*>(src)[q];
+          w[c][4 * q] = t.x; w[c][4 * q + 1] = t.y; w[c][4 * q + 2] = t.z; w[c][4 * q + 3] = t.w;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) w[c][j] = src[j];
+      }
+    }
+  }
+  const int D = nc * 256;
+  float acc[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) acc[b] = 0.f;
+#pragma unroll
+  for (int c = 0; c < WIDE_MAX_CHUNKS; ++c) {
+    if (c < nc) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float* xs = x + b * 2 * D + (c * 256 + lane * 4) * 2;
+        const float4 t0 = *reinterpret_cast<const float4*>(xs), t1 = *reinterpret_cast<const float4*>(xs + 4);
+        float s0 = acc[b];
+        s0 += w[c][1] * t0.x; s0 += w[c][2] * t0.y; s0 += w[c][4] * t0.z; s0 += w[c][5] * t0.w;
+        s0 += w[c][7] * t1.x; s0 += w[c][8] * t1.y; s0 += w[c][10] * t1.z; s0 += w[c][11] * t1.w;
+        acc[b] = s0;
+      }
+    }
+  }
+  return wave_fold8(acc, lane);
+}
+
+// one layer of the tail, forward: y[w][j] = act(bias[j] + sum_k W[j][k] x[w][k]), a wave per neuron j < n
+template <int K, int STRIDE>
+__device__ __forceinline__ void wide_tail_layer(const float* __restrict__ W, const float* __restrict__ bias,
+                                                const float* x, float* y, int n, bool act) {
+  const int lane = threadIdx.x & 63;
+  for (int j = threadIdx.x >> 6; j < n; j += WIDE_WAVES) {
+    const float v = wave_dot8<K, STRIDE>(W + (size_t)j * K * STRIDE, false, x, lane);
+    if ((lane & 7) == 0) y[(lane >> 3) * n + j] = act ? leaky(v + bias[j]) : v + bias[j];
+  }
+}
+
+// vec: bit 0 = conv1's weight is 16-byte aligned
+__global__ void __launch_bounds__(FT)
+frame_code_wide_forward_kernel(WideDims d, ParamPtrs P, const float* __restrict__ a, const float* __restrict__ e,
+                               float* __restrict__ enc_a, float* __restrict__ enc_e, float* saved, uint32_t* arrivals,
+                               int vec) {
+  extern __shared__ __align__(16) float s[];
+  const int D = d.D, A = d.A, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwg = gridDim.x;
+  const FrameLayout L = frame_layout(1, 1, A);
+  const WideLayout Y = wide_layout(A);
+  float* xa = s;                                // a [8][D][2]
+  float* act = xa + NB * 2 * D;                 // the saved block
+  float* sw = act + Y.end;                      // attention + expression weights
+  volatile uint32_t* s_ticket = reinterpret_cast<volatile uint32_t*>(sw + att_floats(A));
+  for (int i = tid; i < NB * 2 * D; i += FT) xa[i] = a[i];
+  const AttW aw = att_layout(A);
+  stage_attention<FT>(sw, aw, P.p + 12, A, d.has_exp, false);
+  __syncthreads();
+  // conv1: this workgroup's neurons, all eight windows
+  const int per = WIDE_M / nwg, n0 = (int)blockIdx.x * per;
+  for (int j = wave; j < per; j += WIDE_WAVES) {
+    const int n = n0 + j;
+    const float v = wave_dot8_taps(P.p[0] + (size_t)n * D * 3, (vec & 1) != 0, xa, lane, D / 256);
+    if ((lane & 7) == 0) {
+      const int w = lane >> 3;
+      const float z = leaky(v + P.p[1][n]);
+      saved[Y.z1 + w * WIDE_M + n] = z;
+      if (nwg == 1) act[Y.z1 + w * WIDE_M + n] = z;
+    }
+  }
+  if (nwg > 1) {
+    if (!last_to_arrive(arrivals, s_ticket, nwg)) return;
+    // the last workgroup reads all of z1
+    for (int i = tid; i < NB * WIDE_M; i += FT) act[Y.z1 + i] = saved[Y.z1 + i];
+  }
+  __syncthreads();
+  wide_tail_layer<WIDE_M, 3>(P.p[2], P.p[3], act + Y.z1, act + Y.z2, WIDE_M, true);   __syncthreads();
+  wide_tail_layer<WIDE_M, 3>(P.p[4], P.p[5], act + Y.z2, act + Y.z3, WIDE_C, true);   __syncthreads();
+  wide_tail_layer<WIDE_C, 3>(P.p[6], P.p[7], act + Y.z3, act + Y.z4, WIDE_C, true);   __syncthreads();
+  wide_tail_layer<WIDE_C, 1>(P.p[8], P.p[9], act + Y.z4, act + Y.f1, WIDE_C, true);   __syncthreads();
+  wide_tail_layer<WIDE_C, 1>(P.p[10], P.p[11], act + Y.f1, act + Y.f2, A, false);     __syncthreads();
+  // activations in FrameLayout order from xt on: aa[L.<act>] for act in xt .. eh
+  attention_forward<FT, false>(act + Y.f2, act + Y.att - L.xt, L, sw, aw, A, e, enc_a, enc_e, d.has_exp);
+  for (int i = tid; i < Y.end - Y.z2; i += FT) saved[Y.z2 + i] = act[Y.z2 + i];
+}
+
+// Gradients of a k3 convolution [cout][cin][3] whose outer taps only met padding: the centre tap's eight-term sum in
+// window order, the outer taps 0.0 (torch's value) without a product; and the bias gradient.  x [8][cin], g_out [8][cout].
+__device__ __forceinline__ void centre_tap_grads(const float* x, const float* g_out, float* __restrict__ dW,
+                                                 float* __restrict__ dbias, int cin, int cout) {
+  const int nW = cout * cin * 3;
+  for (int idx = threadIdx.x; idx < nW + cout; idx += FT) {
+    float acc = 0.f;
+    if (idx < nW) {
+      if (idx % 3 == 1) {
+        const int ci = (idx / 3) % cin, co = idx / (3 * cin);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc += g_out[b * cout + co] * x[b * cin + ci];
+      }
+      dW[idx] = acc;
+    } else {
+      const int co = idx - nW;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc += g_out[b * cout + co];
+      dbias[co] = acc;
+    }
+  }
+}
+
+// dst[i] = the centre tap of src [n][3]
+__device__ __forceinline__ void stage_centre_taps(float* dst, const float* __restrict__ src, int n) {
+#pragma unroll 4
+  for (int i = threadIdx.x; i < n; i += FT) dst[i] = src[3 * i + 1];
+}
+
+// vec: bit 0 = the gradient of conv1's weight is 16-byte aligned
+__global__ void __launch_bounds__(FT)
+frame_code_wide_backward_kernel(WideDims d, ParamPtrs P, GradPtrs G, const float* __restrict__ a,
+                                const float* __restrict__ e, const float* __restrict__ saved,
+                                const float* __restrict__ d_enc_a, const float* __restrict__ d_enc_e, int vec) {
+  static_assert(FT == 1024 && WIDE_ROWS == 8 && NB == 8, "the thread maps below assume these");
+  extern __shared__ __align__(16) float s[];
+  const int D = d.D, A = d.A, tid = threadIdx.x;
+  const bool first = blockIdx.x == 0;           // writes the gradients that are the same in every workgroup
+  const int n0 = (int)blockIdx.x * WIDE_ROWS;   // this workgroup's conv1 neurons
+  const FrameLayout L = frame_layout(1, 1, A);
+  const WideLayout Y = wide_layout(A);
+  float* wfc2 = s;                              // [A][64]; the region holds a [8][D][2] later
+  float* wfc1 = wfc2 + A * WIDE_C;              // [64][64]
+  float* w4c = wfc1 + WIDE_C * WIDE_C;          // conv4 centre taps [64][64]
+  float* w3c = w4c + WIDE_C * WIDE_C;           // conv3 centre taps [64][128]
+  float* xa = s;
+  float* w2col = s + wide_region_floats(D, A);  // conv2 centre taps [128][8]: the columns of this workgroup's neurons
+  float* act = w2col + WIDE_M * WIDE_ROWS;      // saved activations
+  float* g = act + Y.end;                       // their gradients, same offsets
+  float* sw = g + Y.end;                        // attention + expression weights
+  const AttW aw = att_layout(A);
+  // every load of the tail is issued here
+  for (int i = tid; i < Y.end; i += FT) act[i] = saved[i];
+  stage_attention<FT>(sw, aw, P.p + 12, A, d.has_exp, true);
+  stage<FT>(wfc2, P.p[10], A * WIDE_C);
+  stage<FT>(wfc1, P.p[8], WIDE_C * WIDE_C);
+  stage_centre_taps(w4c, P.p[6], WIDE_C * WIDE_C);
+  stage_centre_taps(w3c, P.p[4], WIDE_C * WIDE_M);
+  w2col[tid] = P.p[2][((tid >> 3) * WIDE_M + n0 + (tid & 7)) * 3 + 1];
+  __syncthreads();
+  float* gF2 = g + Y.f2;
+  auto G0 = [&](int i) -> float* { return first ? G.p[i] : nullptr; };
+  // sa[L.<act>], ga[L.<act>] for act in xt .. eh
+  attention_backward(act + Y.f2, gF2, act + Y.att - L.xt, g + Y.att - L.xt, L, sw, aw, A, e, d_enc_a, d_enc_e, G.p + 12,
+                     first, d.has_exp);
+  __syncthreads();
+  // fc2 (no activation behind it), fc1: their gradients once, d(pre-activation) of the layer below in every workgroup
+  conv_backward<1, 1>(act + Y.f1, gF2, wfc2, G0(10), G0(11), g + Y.f1, NB, WIDE_C, A, 1, 1, true);
+  __syncthreads();
+  conv_backward<1, 1>(act + Y.z4, g + Y.f1, wfc1, G0(8), G0(9), g + Y.z4, NB, WIDE_C, WIDE_C, 1, 1, true);
+  __syncthreads();
+  // conv4, conv3: linear layers on their centre taps
+  conv_backward<1, 1>(act + Y.z3, g + Y.z4, w4c, nullptr, nullptr, g + Y.z3, NB, WIDE_C, WIDE_C, 1, 1, true);
+  if (first) centre_tap_grads(act + Y.z3, g + Y.z4, G.p[6], G.p[7], WIDE_C, WIDE_C);
+  __syncthreads();
+  conv_backward<1, 1>(act + Y.z2, g + Y.z3, w3c, nullptr, nullptr, g + Y.z2, NB, WIDE_M, WIDE_C, 1, 1, true);
+  if (first) centre_tap_grads(act + Y.z2, g + Y.z3, G.p[4], G.p[5], WIDE_M, WIDE_C);
+  __syncthreads();
+  // the tail's weights are through: the windows take their floats (complete at the barrier behind d z1)
+  for (int i = tid; i < NB * 2 * D; i += FT) xa[i] = a[i];
+  const float* z1 = act + Y.z1;
+  const float* gz2 = g + Y.z2;
+  if (first) centre_tap_grads(z1, gz2, G.p[2], G.p[3], WIDE_M, WIDE_M);
+  // d z1 of this workgroup's 8 neurons: 16 lanes per (window, neuron), each sums 8 of the 128 conv2 rows
+  float* gz1 = g + Y.z1;                        // [8][8]: only this workgroup's neurons
+  {
+    const int out = tid >> 4, part = tid & 15, b = out >> 3, kk = out & 7;
+    float acc = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+      const int j = part * 8 + jj;
+      acc += w2col[j * WIDE_ROWS + kk] * gz2[b * WIDE_M + j];
+    }
+    acc += __shfl_xor(acc, 8);
+    acc += __shfl_xor(acc, 4);
+    acc += __shfl_xor(acc, 2);
+    acc += __shfl_xor(acc, 1);
+    if (part == 0) gz1[b * WIDE_ROWS + kk] = acc * dleaky(z1[b * WIDE_M + n0 + kk]);
+  }
+  __syncthreads();
+  // dW1 rows n0 .. n0 + 7 (3 D contiguous floats each) and db1: a thread owns four channels of a row, 12 floats
+  const int nq = D / 4;
+  for (int idx = tid; idx < WIDE_ROWS * nq; idx += FT) {
+    const int c = idx % nq, kk = idx / nq;
+    float t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = 0.f;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const float gv = gz1[b * WIDE_ROWS + kk];
+      const float4 x0 = *reinterpret_cast<const float4*>(xa + b * 2 * D + 8 * c);
+      const float4 x1 = *reinterpret_cast<const float4*>(xa + b * 2 * D + 8 * c + 4);
+      t[0] += gv * x0.x; t[1] += gv * x0.y; t[2] += gv * x0.z; t[3] += gv * x0.w;
+      t[4] += gv * x1.x; t[5] += gv * x1.y; t[6] += gv * x1.z; t[7] += gv * x1.w;
+    }
+    float* dst = G.p[0] + (size_t)(n0 + kk) * D * 3 + 12 * c;
+    if (vec & 1) {
+      reinterpret_cast<float4*>(dst)[0] = make_float4(0.f, t[0], t[1], 0.f);
+      reinterpret_cast<float4*>(dst)[1] = make_float4(t[2], t[3], 0.f, t[4]);
+      reinterpret_cast<float4*>(dst)[2] = make_float4(t[5], 0.f, t[6], t[7]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { dst[3 * i] = 0.f; dst[3 * i + 1] = t[2 * i]; dst[3 * i + 2] = t[2 * i + 1]; }
+    }
+  }
+  if (tid < WIDE_ROWS) {
+    float acc = 0.f;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc += gz1[b * WIDE_ROWS + tid];
+    G.p[1][n0 + tid] = acc;
+  }
+}
+
+inline int set_wide_lds_limit() {
+  if (int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(frame_code_wide_forward_kernel), 160 * 1024)) return rc;
+  return set_max_dynamic_lds(reinterpret_cast<const void*>(frame_code_wide_backward_kernel), 160 * 1024);
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // The n parameter pointers of an entry point into P and, for a backward pass, the gradient pointers into G (else
@@ -999,6 +1308,53 @@ int instag_frame_code_ave_backward(const float* a, const float* e, const float* 
   const AveDims d{dim_aud, has_exp};
   frame_code_ave_backward_kernel<<<AVE_WG, FT, ave_backward_floats(dim_aud) * sizeof(float), (hipStream_t)stream>>>(
       d, P, G, a, e, saved, d_enc_a, d_enc_e, aligned16(G.p[0]) ? 1 : 0);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+int64_t instag_frame_code_wide_saved_floats(int32_t dim_in, int32_t mid, int32_t dim_aud) {
+  if (!wide_dims_ok(dim_in, mid, dim_aud)) return -1;
+  return wide_layout(dim_aud).end;
+}
+
+int instag_frame_code_wide_forward(const float* a, const float* e, const float* const* params, float* enc_a,
+                                   float* enc_e, float* saved, int32_t dim_in, int32_t mid, int32_t dim_aud,
+                                   uint32_t* arrivals, instag_stream_t stream) {
+  INSTAG_REQUIRE(a && params && enc_a && saved, "frame_code_wide_forward: NULL tensor");
+  INSTAG_REQUIRE(wide_dims_ok(dim_in, mid, dim_aud),
+                 "frame_code_wide: dim_in must be 256, 512, 768 or 1024, mid 128, and dim_aud fit the 160 KB LDS");
+  INSTAG_REQUIRE((e == nullptr) == (enc_e == nullptr), "frame_code_wide_forward: e and enc_e go together");
+  const int has_exp = e != nullptr;
+  ParamPtrs P;
+  if (int rc = gather_params(P.p, nullptr, params, nullptr, NPARAM, has_exp, "frame_code_wide_forward: NULL parameter"))
+    return rc;
+  if (int rc = set_wide_lds_limit()) return rc;
+  const WideDims d{dim_in, dim_aud, has_exp};
+  // with an arrival word conv1 is split over WIDE_WG workgroups and the last one to arrive runs the rest
+  frame_code_wide_forward_kernel<<<arrivals ? WIDE_WG : 1, FT, wide_forward_floats(dim_in, dim_aud) * sizeof(float),
+                                   (hipStream_t)stream>>>(d, P, a, e, enc_a, enc_e, saved, arrivals,
+                                                          aligned16(P.p[0]) ? 1 : 0);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+int instag_frame_code_wide_backward(const float* a, const float* e, const float* const* params, const float* saved,
+                                    const float* d_enc_a, const float* d_enc_e, float* const* grads, int32_t dim_in,
+                                    int32_t mid, int32_t dim_aud, void*, size_t, instag_stream_t stream) {
+  INSTAG_REQUIRE(a && params && saved && d_enc_a && grads, "frame_code_wide_backward: NULL tensor");
+  INSTAG_REQUIRE(wide_dims_ok(dim_in, mid, dim_aud),
+                 "frame_code_wide: dim_in must be 256, 512, 768 or 1024, mid 128, and dim_aud fit the 160 KB LDS");
+  const int has_exp = e != nullptr;
+  ParamPtrs P;
+  GradPtrs G;
+  if (int rc = gather_params(P.p, G.p, params, grads, NPARAM, has_exp,
+                             "frame_code_wide_backward: NULL parameter / gradient"))
+    return rc;
+  if (int rc = set_wide_lds_limit()) return rc;
+  const WideDims d{dim_in, dim_aud, has_exp};
+  frame_code_wide_backward_kernel<<<WIDE_WG, FT, wide_backward_floats(dim_in, dim_aud) * sizeof(float),
+                                    (hipStream_t)stream>>>(d, P, G, a, e, saved, d_enc_a, d_enc_e,
+                                                           aligned16(G.p[0]) ? 1 : 0);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
 }

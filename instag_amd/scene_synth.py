@@ -118,12 +118,14 @@ def synthetic_frame(size=512, seed=0, device="cpu", priors=False, background=Fal
     """Per-frame training inputs of config C3 (audio window, AU vector, GT image, masks).  ``priors`` adds the
     monocular normal [3,H,W] (unit vectors) / depth [H,W] maps of train_face.py:466-504, ``background`` the
     per-camera scene background [3,H,W] of train_fuse_con.py:113.  ``audio_extractor="ave"`` makes the audio window
-    [8, 1, 512] (dataset_readers.py:139-149, get_audio_features mode 2) in place of [8, 29, 16]; everything else of the
-    frame is the same."""
+    [8, 1, 512] (dataset_readers.py:139-149, get_audio_features mode 2) in place of [8, 29, 16], ``"hubert"`` [8, 1024, 2] (two
+    hidden states of 1024 features per window); everything else of the frame is the same."""
     g = torch.Generator().manual_seed(1000 + seed)
     auds = torch.randn(8, 29, 16, generator=g)
     if audio_extractor == "ave":
         auds = torch.randn(8, 1, 512, generator=torch.Generator().manual_seed(5000 + seed))
+    elif audio_extractor == "hubert":
+        auds = torch.randn(8, 1024, 2, generator=torch.Generator().manual_seed(7000 + seed))
     au_exp = torch.rand(6, generator=g)
     gt = torch.rand(3, size, size, generator=g)
     yy, xx = torch.meshgrid(torch.arange(size), torch.arange(size), indexing="ij")
