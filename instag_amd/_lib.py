@@ -46,6 +46,12 @@ _HUBERT_STRUCTS, _HUBERT_PROTOTYPES, HUBERT = _cabi.read(os.path.join(os.path.di
 # points (instag_amd/audio.py), no struct and no constant.
 _, _FRAME_CODE_WIDE_PROTOTYPES, _ = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_frame_code_wide.h"))
 
+# The DeepSpeech network's part, include/instag_deepspeech.h (instag_amd/deepspeech.py): struct DeepspeechWeights, the
+# four instag_deepspeech_* entry points and the INSTAG_DEEPSPEECH_* bounds.
+_DEEPSPEECH_STRUCTS, _DEEPSPEECH_PROTOTYPES, DEEPSPEECH = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER),
+                                                                              "instag_deepspeech.h"))
+globals().update((cls.__name__, cls) for cls in _DEEPSPEECH_STRUCTS.values())
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -212,7 +218,7 @@ def lib():
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
-                                  **_FRAME_CODE_WIDE_PROTOTYPES}.items():
+                                  **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

@@ -61,6 +61,7 @@ SOURCES = {
     "mesh_render.hip": [],
     "wav2vec.hip": [],
     "hubert.hip": [],
+    "deepspeech.hip": [],
 }
 
 
