@@ -52,6 +52,12 @@ _DEEPSPEECH_STRUCTS, _DEEPSPEECH_PROTOTYPES, DEEPSPEECH = _cabi.read(os.path.joi
                                                                               "instag_deepspeech.h"))
 globals().update((cls.__name__, cls) for cls in _DEEPSPEECH_STRUCTS.values())
 
+# The face landmark network's part, include/instag_landmarks.h (instag_amd/landmarks.py): struct LandmarksWeights, the
+# four instag_landmarks_* entry points and the INSTAG_LANDMARKS_* bounds.
+_LANDMARKS_STRUCTS, _LANDMARKS_PROTOTYPES, LANDMARKS = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER),
+                                                                             "instag_landmarks.h"))
+globals().update((cls.__name__, cls) for cls in _LANDMARKS_STRUCTS.values())
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -218,7 +224,8 @@ def lib():
         import torch  # noqa: F401
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
-                                  **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES}.items():
+                                  **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES,
+                                  **_LANDMARKS_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

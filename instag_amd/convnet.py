@@ -66,6 +66,7 @@ class ConvWeights:
     STRUCT = ""             # the ctypes struct of _lib
     STEM_K = None           # the first layer's K is padded with zero rows to this
     COUT_MAJOR = ()          # layers the kernels read as stored, [cout][cin ky kx], not as [K][cout]
+    PRE = ()                 # layers whose BatchNorm stands in FRONT of the convolution: its tensors have cin entries
 
     def __init__(self, layers):
         if len(layers) != len(self.TABLE):
@@ -77,7 +78,7 @@ class ConvWeights:
             cout = self.classes if cout is None else cout
             lay = {f: lay[f].detach().float().contiguous().cpu() for f, _ in keys(row)}
             for f, t in lay.items():
-                want = (cout, cin, k, k) if f == "weight" else (cout,)
+                want = (cout, cin, k, k) if f == "weight" else (cin if l in self.PRE and f != "bias" else cout,)
                 if tuple(t.shape) != want:
                     raise ValueError(f"{self.LABEL}: {self._layer_name(l)} {f} has shape {tuple(t.shape)}, expected {want}")
             self.layers.append(lay)

@@ -2,8 +2,10 @@
 
 The reference scores its result twice: train_face.py:821-878 reports L1 and utils/image_utils.py ``psnr`` on held-out
 cameras at the test iterations (``face_validation``), and metrics.py:105-217 reports PSNR and LPIPS between the 8-bit
-frames of the rendered and the ground-truth videos (``Evaluator`` with ``quantize=True``; LMD, metrics.py:8-102, needs a
-landmark detector and is not here).  synthesize_fuse.py:65-76 dilates the mouth alpha and writes ``uint8 [H,W,3]``
+frames of the rendered and the ground-truth videos (``Evaluator`` with ``quantize=True``); LMD, metrics.py:8-102, is the
+mean distance between the mouth landmarks of the two frames, each set taken off its own mean (``landmarks.lmd_torch``),
+and joins the report when the Evaluator is given a ``landmarks.LandmarkNet`` and one face box per frame -- the boxes are
+the caller's: the face detector the reference's meter runs in front of the landmark network is not here.  synthesize_fuse.py:65-76 dilates the mouth alpha and writes ``uint8 [H,W,3]``
 frames (``infer_compose``, reached through ``infer.FuseRenderer(dilate=, as_uint8=)``).
 
     r = FuseRenderer(g, net, gm, netm, bg).enable_graph(frames[0], frames_per_replay=4)
@@ -67,11 +69,12 @@ def infer_compose_torch(face, a_face, mouth, a_mouth, bg, scene=None, dilate=1):
 # ---- device state ----------------------------------------------------------------------------------------------------
 class Meter:
     """Running sums of an evaluation on ``device``: double[6] = the five frame figures and the frame count (what
-    ``instag_frame_metrics`` adds to), then the LPIPS sum and its count.  Means are means of per-frame values, as the
+    ``instag_frame_metrics`` adds to), then the LPIPS sum and its count, then the LMD sum and its count (its mean joins
+    the report only where an evaluation measured it).  Means are means of per-frame values, as the
     reference's meters keep them (metrics.py:123-133: the mean of per-frame PSNR, not the PSNR of the mean MSE)."""
 
     def __init__(self, device="cpu"):
-        self.state = torch.zeros(8, dtype=torch.float64, device=device)
+        self.state = torch.zeros(10, dtype=torch.float64, device=device)
 
     def clear(self):
         self.state.zero_()
@@ -81,19 +84,23 @@ class Meter:
         self.state[:5] += per_frame.double().sum(0)
         self.state[5] += per_frame.shape[0]
 
-    def add_lpips(self, values):
+    def add_lpips(self, values, slot: int = 6):
         """``values`` [n] fp32 into the LPIPS slot (one launch on the device, no synchronisation)."""
         n = int(values.shape[0])
         if n == 0:
             return
         if not self.state.is_cuda:
-            self.state[6] += values.double().sum()
-            self.state[7] += n
+            self.state[slot] += values.double().sum()
+            self.state[slot + 1] += n
             return
         from . import _lib
         values = values.contiguous().float()
-        _lib.check(_lib.lib().instag_meter_add(_lib.ptr(values), n, _lib.ptr(self.state[6:]), _lib.current_stream()),
+        _lib.check(_lib.lib().instag_meter_add(_lib.ptr(values), n, _lib.ptr(self.state[slot:]), _lib.current_stream()),
                    "meter_add")
+
+    def add_lmd(self, values):
+        """``values`` [n] fp32 into the LMD slot, as ``add_lpips``."""
+        self.add_lpips(values, slot=8)
 
     def report(self) -> dict:
         """Synchronises.  -> means over the frames seen; ``lpips`` is None when nothing was added to its slot."""
@@ -101,6 +108,8 @@ class Meter:
         n = s[5]
         out = {k: (s[i] / n if n else float("nan")) for i, k in enumerate(COLUMNS)}
         out["lpips"] = s[6] / s[7] if s[7] else None
+        if s[9]:
+            out["lmd"] = s[8] / s[9]                    # only where an evaluation measured it
         out["frames"] = int(n)
         return out
 
@@ -218,10 +227,13 @@ class Evaluator:
     """Scores what ``renderer`` (infer.FuseRenderer) renders against ground-truth frames.  ``quantize=True``: the figures
     metrics.py prints for the two videos synthesize_fuse.py writes (PSNR, and LPIPS when ``lpips`` -- a FrameLPIPS -- is
     given), plus L1 / MSE / SSIM of the same 8-bit frames.  ``group``: frames per render and per metrics launch
-    (default: the renderer's captured ``frames_per_replay``, 1 without a graph)."""
+    (default: the renderer's captured ``frames_per_replay``, 1 without a graph).  ``lmd``: ``(LandmarkNet, boxes [N,4] or
+    [4])`` -- the report gains ``lmd``, the reference's mouth landmark distance between the 8-bit rendered and
+    ground-truth frames, both cropped by the frame's box; a frame whose box has a NaN stays out of its mean."""
 
-    def __init__(self, renderer, lpips: Optional[FrameLPIPS] = None, quantize: bool = True, group: Optional[int] = None):
-        self.renderer, self.lpips, self.quantize, self.group = renderer, lpips, bool(quantize), group
+    def __init__(self, renderer, lpips: Optional[FrameLPIPS] = None, quantize: bool = True, group: Optional[int] = None,
+                 lmd=None):
+        self.renderer, self.lpips, self.quantize, self.group, self.lmd = renderer, lpips, bool(quantize), group, lmd
 
     @torch.no_grad()
     def evaluate(self, frames, gts, scene_backgrounds=None) -> dict:
@@ -232,6 +244,9 @@ class Evaluator:
         r = self.renderer
         K = int(self.group or getattr(r, "frames_per_replay", 1))
         meter = Meter(r.bg.device)
+        if self.lmd is not None:
+            from . import landmarks as LM
+            net, boxes = self.lmd[0], LM.check_boxes(self.lmd[1], len(frames))
         for g0 in range(0, len(frames), K):
             idx = [min(g0 + k, len(frames) - 1) for k in range(K)]
             n = min(K, len(frames) - g0)
@@ -244,6 +259,12 @@ class Evaluator:
                 if self.quantize:
                     images, gt = quantize_frame(images), quantize_frame(gt)
                 self.lpips(images[:n], gt[:n], meter=meter)
+            if self.lmd is not None:
+                keep = [k for k in range(n) if bool(LM.usable(boxes[idx[k]][None]))]
+                if keep:
+                    as_u8 = lambda t: (t[keep].clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1)   # metrics.py:69
+                    rows = boxes[[idx[k] for k in keep]]
+                    meter.add_lmd(LM.lmd_torch(net.landmarks(as_u8(images), rows), net.landmarks(as_u8(gt), rows)))
         return meter.report()
 
 
