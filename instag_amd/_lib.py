@@ -58,6 +58,12 @@ _LANDMARKS_STRUCTS, _LANDMARKS_PROTOTYPES, LANDMARKS = _cabi.read(os.path.join(o
                                                                              "instag_landmarks.h"))
 globals().update((cls.__name__, cls) for cls in _LANDMARKS_STRUCTS.values())
 
+# The face detector's part, include/instag_face_detect.h (instag_amd/face_detect.py): struct FaceDetectWeights, the
+# instag_face_detect* entry points and the INSTAG_FACE_DETECT_* bounds.
+_FACE_DETECT_STRUCTS, _FACE_DETECT_PROTOTYPES, FACE_DETECT = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER),
+                                                                                   "instag_face_detect.h"))
+globals().update((cls.__name__, cls) for cls in _FACE_DETECT_STRUCTS.values())
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -225,7 +231,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
                                   **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES,
-                                  **_LANDMARKS_PROTOTYPES}.items():
+                                  **_LANDMARKS_PROTOTYPES, **_FACE_DETECT_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

@@ -65,6 +65,8 @@ SOURCES = {
     # landmarks: the crop's and the decode's fp64 transform is the torch statement's operation by operation, and its
     # result is truncated to an integer; the convolution's FMAs are written out and stay
     "landmarks.hip": ["-ffp-contract=off"],
+    # face_detect: the tail's fp64 box decode and overlap are the torch statement's operations one by one
+    "face_detect.hip": ["-ffp-contract=off"],
 }
 
 

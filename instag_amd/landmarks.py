@@ -5,11 +5,11 @@ The reference makes these files with the ``face_alignment`` package (data_utils/
 ``FaceAlignment(LandmarksType._2D, flip_input=False).get_landmarks(image)``, the 68 points saved with
 ``np.savetxt(..., '%f')``).  That package runs a face detector (S3FD) and then FAN-2D-4 on a crop around each detected
 box.  Here is the second half: the crop, the network and the decode, for boxes that are given -- as the package itself
-takes them through ``detected_faces=``.  The detector is not here.
+takes them through ``detected_faces=`` -- or that a ``face_detect.FaceDetector``, the first half, finds.
 
     w = FANWeights.load("2DFAN4-11f355bf06.pth.tar")                 # a file a user of the package has; none shipped or fetched
-    boxes = boxes_from_labels(parser.labels(frames))                  # a STAND-IN for the detector, see below
-    lms = landmarks_identity("data/May", w, "cuda", boxes)            # reads ori_imgs/*.jpg, writes ori_imgs/*.lms
+    detector = FaceDetector(S3FDWeights.load("s3fd-619a316812.pth"), "cuda")       # face_detect.py
+    lms = landmarks_identity("data/May", w, "cuda", detector=detector)    # reads ori_imgs/*.jpg, writes ori_imgs/*.lms
 
 On the GPU the crop, the network and the decode run in csrc/landmarks.hip (inference only, fp32); ``crop_torch``,
 ``fan_torch``, ``decode_torch`` and ``landmarks_torch`` are the plain-torch statement of the same arithmetic (any dtype,
@@ -530,18 +530,22 @@ def write_landmarks(path, lms):
     np.savetxt(path, np.asarray(lms, dtype=np.float32), "%f")
 
 
-def landmarks_identity(path, weights: FANWeights, device="cuda", boxes=None, write: bool = True, batch: int = 32):
+def landmarks_identity(path, weights: FANWeights, device="cuda", boxes=None, write: bool = True, batch: int = 32,
+                       detector=None):
     """ori_imgs/<i>.jpg of ``path`` (ascending numeric order) and ``boxes`` [N,4] (or [4]) in that order -> landmarks
-    float32 [N,68,2] on ``device``.  ``write``: also ori_imgs/<i>.lms, what ``track.read_landmarks`` reads; a frame whose
-    box row has a NaN gets no file (and a NaN row), as a frame without a detection gets none in the reference."""
+    float32 [N,68,2] on ``device``.  Without boxes, ``detector`` (a ``face_detect.FaceDetector``) finds them: each
+    batch's boxes are ``detector.first(frames)``, the face process.py takes.  ``write``: also ori_imgs/<i>.lms, what
+    ``track.read_landmarks`` reads; a frame whose box row has a NaN gets no file (and a NaN row), as a frame without a
+    detection gets none in the reference."""
     from .prepare import list_frames
-    if boxes is None:
+    if boxes is None and detector is None:
         raise ValueError("landmarks_identity: boxes [N,4], one per frame (the face detector is not part of this project)")
-    boxes = check_boxes(boxes, len(list_frames(path)))
+    if boxes is not None:
+        boxes = check_boxes(boxes, len(list_frames(path)))
     net = LandmarkNet(weights, torch.device(device), max_batch=batch)
     out, at = [], 0
     for ids, frames, _ in convnet.frame_batches(path, batch):
-        lms = net.landmarks(frames, boxes[at:at + len(ids)])
+        lms = net.landmarks(frames, detector.first(frames) if boxes is None else boxes[at:at + len(ids)])
         at += len(ids)
         out.append(lms)
         if write:
@@ -556,8 +560,9 @@ def boxes_from_labels(labels_u8):
     of the pixels of the face classes (skin, brows, eyes, glasses, nose, mouth, lips), x2 and y2 one past the last
     pixel; a NaN row where a frame has none.  Plain torch, on the labels' device.
 
-    **A stand-in until the face detector (S3FD) is here, and this project's rule: the reference's boxes come from the
-    detector, these do not, and nothing is claimed about how close the landmarks they lead to are to the reference's.**"""
+    **This project's rule, for a caller without S3FD weights: the reference's boxes come from the face detector, which is
+    ``face_detect.FaceDetector`` (``landmarks_identity(detector=...)``); these do not, and nothing is claimed about how
+    close the landmarks they lead to are to the reference's.**"""
     lab = torch.as_tensor(labels_u8)
     if lab.dim() != 3:
         raise ValueError(f"landmarks: labels [N,H,W], got {tuple(lab.shape)}")

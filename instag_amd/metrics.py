@@ -4,8 +4,9 @@ The reference scores its result twice: train_face.py:821-878 reports L1 and util
 cameras at the test iterations (``face_validation``), and metrics.py:105-217 reports PSNR and LPIPS between the 8-bit
 frames of the rendered and the ground-truth videos (``Evaluator`` with ``quantize=True``); LMD, metrics.py:8-102, is the
 mean distance between the mouth landmarks of the two frames, each set taken off its own mean (``landmarks.lmd_torch``),
-and joins the report when the Evaluator is given a ``landmarks.LandmarkNet`` and one face box per frame -- the boxes are
-the caller's: the face detector the reference's meter runs in front of the landmark network is not here.  synthesize_fuse.py:65-76 dilates the mouth alpha and writes ``uint8 [H,W,3]``
+and joins the report when the Evaluator is given a ``landmarks.LandmarkNet`` and either one face box per frame or a
+``face_detect.FaceDetector``, the face detector the reference's meter runs in front of the landmark network on the
+rendered and on the ground-truth frame.  synthesize_fuse.py:65-76 dilates the mouth alpha and writes ``uint8 [H,W,3]``
 frames (``infer_compose``, reached through ``infer.FuseRenderer(dilate=, as_uint8=)``).
 
     r = FuseRenderer(g, net, gm, netm, bg).enable_graph(frames[0], frames_per_replay=4)
@@ -75,9 +76,11 @@ class Meter:
 
     def __init__(self, device="cpu"):
         self.state = torch.zeros(10, dtype=torch.float64, device=device)
+        self.lmd_skipped = None                         # a host count, kept only by an evaluation that detects faces
 
     def clear(self):
         self.state.zero_()
+        self.lmd_skipped = None
 
     def add_rows(self, per_frame):
         """CPU path of ``frame_metrics``: rows [n,5] into the sums."""
@@ -110,6 +113,8 @@ class Meter:
         out["lpips"] = s[6] / s[7] if s[7] else None
         if s[9]:
             out["lmd"] = s[8] / s[9]                    # only where an evaluation measured it
+        if self.lmd_skipped is not None:
+            out["lmd_skipped"] = int(self.lmd_skipped)   # frames a face detector found no face in (Evaluator)
         out["frames"] = int(n)
         return out
 
@@ -229,7 +234,11 @@ class Evaluator:
     given), plus L1 / MSE / SSIM of the same 8-bit frames.  ``group``: frames per render and per metrics launch
     (default: the renderer's captured ``frames_per_replay``, 1 without a graph).  ``lmd``: ``(LandmarkNet, boxes [N,4] or
     [4])`` -- the report gains ``lmd``, the reference's mouth landmark distance between the 8-bit rendered and
-    ground-truth frames, both cropped by the frame's box; a frame whose box has a NaN stays out of its mean."""
+    ground-truth frames, both cropped by the frame's box; a frame whose box has a NaN stays out of its mean.  Or
+    ``(LandmarkNet, face_detect.FaceDetector)``: as in the reference's meter (metrics.py:78-79) the boxes are detected
+    separately on the 8-bit rendered frame and on the ground truth, ``detector.last(...)`` being the reference's
+    ``[-1]``; a frame where either has no detection is left out of the mean and counted in the report as
+    ``lmd_skipped`` (the reference would raise there; reading the boxes synchronises once per group)."""
 
     def __init__(self, renderer, lpips: Optional[FrameLPIPS] = None, quantize: bool = True, group: Optional[int] = None,
                  lmd=None):
@@ -246,7 +255,11 @@ class Evaluator:
         meter = Meter(r.bg.device)
         if self.lmd is not None:
             from . import landmarks as LM
-            net, boxes = self.lmd[0], LM.check_boxes(self.lmd[1], len(frames))
+            net, detector = self.lmd[0], self.lmd[1] if hasattr(self.lmd[1], "last") else None
+            if detector is None:
+                boxes = LM.check_boxes(self.lmd[1], len(frames))
+            else:
+                meter.lmd_skipped = 0
         for g0 in range(0, len(frames), K):
             idx = [min(g0 + k, len(frames) - 1) for k in range(K)]
             n = min(K, len(frames) - g0)
@@ -259,7 +272,16 @@ class Evaluator:
                 if self.quantize:
                     images, gt = quantize_frame(images), quantize_frame(gt)
                 self.lpips(images[:n], gt[:n], meter=meter)
-            if self.lmd is not None:
+            if self.lmd is not None and detector is not None:
+                as_u8 = lambda t: (t[:n].clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1)             # metrics.py:69
+                p8, g8 = as_u8(images), as_u8(gt)
+                pb, gb = LM.check_boxes(detector.last(p8)), LM.check_boxes(detector.last(g8))
+                keep = torch.nonzero(LM.usable(pb) & LM.usable(gb))[:, 0]
+                meter.lmd_skipped += n - int(keep.shape[0])
+                if keep.numel():
+                    k = keep.to(p8.device)
+                    meter.add_lmd(LM.lmd_torch(net.landmarks(p8[k], pb[keep]), net.landmarks(g8[k], gb[keep])))
+            elif self.lmd is not None:
                 keep = [k for k in range(n) if bool(LM.usable(boxes[idx[k]][None]))]
                 if keep:
                     as_u8 = lambda t: (t[keep].clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1)   # metrics.py:69
