@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from . import convnet
 from .convnet import BN_EPS
+from .device_op import DeviceOperator
 
 # (cin, cout, kernel, (stride_h, stride_w), padding, residual): scene/motion_net.py:106-123
 LAYERS = (
@@ -116,40 +117,30 @@ def cut_windows(mel, starts=None):
 
 
 # ---- HIP operator -----------------------------------------------------------------------------------------------------
-class AudioEncoder:
+class AudioEncoder(DeviceOperator):
     """``encode(mel [T,80]) -> [n,512]`` and ``encode_windows([B,1,80,16]) -> [B,512]``, fp32 on ``device``, on
     torch's current stream; inference only (no autograd node), as the reference runs the network.  On the GPU the windows
-    go through csrc/ave_encoder.hip in chunks of at most ``max_batch`` with one workspace, so memory does not grow with
-    the clip (the workspace is the operator's: use one operator per stream); on the CPU both are the torch statement."""
+    go through csrc/ave_encoder.hip in chunks of at most ``max_batch`` with the one kept workspace of
+    device_op.DeviceOperator, so memory does not grow with the clip; on the CPU both are the torch statement.  The
+    workspace's size depends on the batch alone and never decreases as it grows (two buffers of ``buffer_floats`` of
+    csrc/ave_encoder.hip: the batch times a constant, rounded up to 64 floats), so a workspace kept by its bytes is
+    replaced exactly when one kept by its batch would have been too small."""
+
+    CHECK = "check"
 
     def __init__(self, weights: AudioEncoderWeights, device="cuda"):
-        self.weights = weights
-        self.device = torch.device(device)
-        self._ws = None
+        super().__init__(weights, device)
         if self.device.type == "cuda":
-            from . import _lib
-            self._L = _lib.lib()
             self.max_batch = int(self._L.instag_ave_encoder_max_batch())
-            self._struct, self._keep = weights.device_pack(self.device)
-
-    def _workspace(self, batch):
-        from . import _lib
-        if self._ws is None or self._ws[0] < batch:
-            nbytes = _lib.workspace_bytes(self._L.instag_ave_encoder_workspace_bytes(batch))
-            self._ws = (batch, torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes)
-        return self._ws[1], self._ws[2]
 
     def _forward(self, src, T, starts, n):
         from . import _lib
         out = torch.empty(n, DIM_OUT, dtype=torch.float32, device=self.device)
-        ws, nbytes = self._workspace(min(n, self.max_batch))
-        with torch.cuda.device(self.device):
-            for i in range(0, n, self.max_batch):
-                m = min(self.max_batch, n - i)
-                first = src if starts is not None else src[i:i + m]
-                _lib.check(self._L.instag_ave_encoder_forward(
-                    C.byref(self._struct), _lib.ptr(first), int(T), _lib.ptr(None if starts is None else starts[i:i + m]),
-                    m, _lib.ptr(out[i:i + m]), _lib.ptr(ws), nbytes, _lib.current_stream()), "ave_encoder_forward")
+        nbytes = _lib.workspace_bytes(self._L.instag_ave_encoder_workspace_bytes(min(n, self.max_batch)))
+        self._each_chunk(n, nbytes, lambda c, m, ws, size: self._L.instag_ave_encoder_forward(
+            C.byref(self._struct), _lib.ptr(src if starts is not None else src[c]), int(T),
+            _lib.ptr(None if starts is None else starts[c]), m, _lib.ptr(out[c]), ws, size, _lib.current_stream()),
+            "ave_encoder_forward")
         return out
 
     @torch.no_grad()

@@ -7,9 +7,9 @@ shape (``cout=None``: ``self.classes``, which the subclass reads from the checkp
 supplies the table, its ``random`` rule and whatever else is its own; the shape validation, the checkpoint keys, the
 BatchNorm fold and the device copy are here.
 
-``FrameOperator`` is the base of the two operators that take uint8 frames [B,H,W,3]: the frame check, the kept
-workspace, the chunk loop and the CPU fall-back.  Its workspace is one byte tensor that grows when a call needs more
-than it holds and is kept otherwise, whatever the batch and frame size of the call.
+``FrameOperator`` is the base of the operators that take uint8 frames [B,H,W,3] (the parser, the teeth segmenter, the
+landmark net and the face detector): the frame check, the outputs and the CPU fall-back.  The weights' device copy,
+the kept workspace and the chunk loop are device_op.DeviceOperator's, which the audio operators share.
 """
 from __future__ import annotations
 
@@ -17,6 +17,8 @@ import os
 
 import numpy as np
 import torch
+
+from .device_op import DeviceOperator
 
 BN_EPS = 1e-5
 BN = (("gamma", "weight"), ("beta", "bias"), ("mean", "running_mean"), ("var", "running_var"))
@@ -199,10 +201,10 @@ def first_argmax(full):
 
 
 # ---- HIP operator -----------------------------------------------------------------------------------------------------
-class FrameOperator:
+class FrameOperator(DeviceOperator):
     """A network over u8 frames [B,H,W,3] on ``device``, on torch's current stream; inference only.  On the GPU the
-    frames go through the network's C entry point in chunks of at most ``max_batch`` with one workspace (module
-    docstring; it is the operator's: use one operator per stream); on the CPU every output is the torch statement.
+    frames go through the network's C entry point in chunks of at most ``max_batch`` with the one kept workspace of
+    device_op.DeviceOperator; on the CPU every output is the torch statement.
     A subclass sets ``NAME`` and the three functions of its torch statement, and supplies ``_workspace_bytes`` and
     ``_run(frames, want, ...)``, which allocates the outputs named in ``want`` and hands ``_chunks`` its launch."""
 
@@ -210,24 +212,8 @@ class FrameOperator:
     net_torch = normalise_torch = labels_torch = None       # staticmethods of the subclass
 
     def __init__(self, weights, device, max_batch):
-        if max_batch is not None and max_batch < 1:
-            raise ValueError(f"{type(self).__name__}: max_batch >= 1")
-        self.weights = weights
-        self.device = torch.device(device)
-        self.max_batch = max_batch
-        self._ws = None
-        if self.device.type == "cuda":
-            from . import _lib
-            self._L = _lib.lib()
-            self._struct, self._keep = weights.device_pack(self.device)
-
-    def _workspace(self, batch, H, W):
-        from . import _lib
-        nbytes = _lib.workspace_bytes(self._workspace_bytes(batch, H, W))
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws, int(self._ws.numel())
+        self.max_batch = self._at_least_one(max_batch, got=False)
+        super().__init__(weights, device)
 
     def _empty(self, want, **shapes):
         """One tensor per keyword, in order (``logits`` fp32, the others u8), None for those not in ``want``."""
@@ -238,13 +224,8 @@ class FrameOperator:
         """``launch(chunk slice, its length, workspace pointer, workspace bytes) -> return code`` for every chunk."""
         from . import _lib
         B = int(x.shape[0])
-        if B == 0:
-            return
-        ws, nbytes = self._workspace(min(B, self.max_batch), H, W)
-        with torch.cuda.device(self.device):
-            for i in range(0, B, self.max_batch):
-                m = min(self.max_batch, B - i)
-                _lib.check_arg(launch(slice(i, i + m), m, _lib.ptr(ws), nbytes), what)
+        if B:
+            self._each_chunk(B, _lib.workspace_bytes(self._workspace_bytes(min(B, self.max_batch), H, W)), launch, what)
 
     def _logits_torch(self, frames_u8):
         x, H, W = check_frames(self.NAME, frames_u8)

@@ -181,7 +181,8 @@ int attention(const float* qkv, float* ctx, int B, int T, int H, hipStream_t st)
   return INSTAG_OK;
 }
 
-constexpr const char* PLAN_ERROR = ": batch in [1, 4096], 400 <= n_samples <= 2^20 and at most INSTAG_HUBERT_MAX_FRAMES frames";
+constexpr Net NET = {"hubert", ": batch in [1, 4096], 400 <= n_samples <= 2^20 and at most INSTAG_HUBERT_MAX_FRAMES frames",
+                     MAX_T, false};
 
 }  // namespace
 }  // namespace instag
@@ -191,43 +192,20 @@ using namespace instag;
 extern "C" {
 
 size_t instag_hubert_workspace_bytes(const instag_wav2vec_weights* w, int32_t batch, int32_t n_samples) {
-  if (const char* e = shape_error(w, false)) {
-    set_error(std::string("hubert_workspace_bytes: ") + e);
-    return 0;
-  }
   Plan p;
-  if (!make_plan(w, batch, n_samples, MAX_T, &p)) {
-    set_error(std::string("hubert_workspace_bytes") + PLAN_ERROR);
-    return 0;
-  }
-  return p.total * sizeof(float);
+  return entry_plan(NET, "workspace_bytes", true, w, batch, n_samples, &p) ? p.total * sizeof(float) : 0;
 }
 
 size_t instag_hubert_taps_floats(const instag_wav2vec_weights* w, int32_t batch, int32_t n_samples) {
   Plan p;
-  if (shape_error(w, false) || !make_plan(w, batch, n_samples, MAX_T, &p)) {
-    set_error(std::string("hubert_taps_floats") + PLAN_ERROR);
-    return 0;
-  }
-  return taps_floats(w, batch, p);
+  return entry_plan(NET, "taps_floats", false, w, batch, n_samples, &p) ? taps_floats(w, batch, p) : 0;
 }
 
 int instag_hubert_forward(const instag_wav2vec_weights* w, const float* input_values, int32_t batch, int32_t n_samples,
                           float* hidden, void* workspace, size_t workspace_bytes, int32_t tile, float* taps,
                           instag_stream_t stream) {
-  if (const char* e = shape_error(w, false)) {
-    set_error(std::string("hubert_forward: ") + e);
-    return INSTAG_E_ARG;
-  }
-  INSTAG_REQUIRE(input_values && hidden && workspace, "hubert_forward: NULL tensor");
-  INSTAG_REQUIRE(tile >= 0 && tile <= 3, "hubert_forward: tile must be 0..3");
   Plan p;
-  INSTAG_REQUIRE(make_plan(w, batch, n_samples, MAX_T, &p), std::string("hubert_forward") + PLAN_ERROR);
-  INSTAG_TRY(require_weights(w, "hubert_forward", false));
-  if (workspace_bytes < p.total * sizeof(float)) {
-    set_error("hubert_forward: workspace smaller than instag_hubert_workspace_bytes(w, batch, n_samples)");
-    return INSTAG_E_SPACE;
-  }
+  INSTAG_TRY(forward_prologue(NET, w, input_values, hidden, batch, n_samples, workspace, workspace_bytes, tile, &p));
   return run_network(w, p, input_values, nullptr, batch, (float*)workspace, tile, taps, hidden, (hipStream_t)stream, attention);
 }
 

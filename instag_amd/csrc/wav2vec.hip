@@ -83,7 +83,8 @@ __global__ void __launch_bounds__(TB) attention_kernel(const float* __restrict__
   }
 }
 
-constexpr const char* PLAN_ERROR = ": batch in [1, 4096], 400 <= n_samples <= 2^20 and at most INSTAG_WAV2VEC_MAX_FRAMES frames";
+constexpr Net NET = {"wav2vec", ": batch in [1, 4096], 400 <= n_samples <= 2^20 and at most INSTAG_WAV2VEC_MAX_FRAMES frames",
+                     MAX_T, true};
 
 }  // namespace
 }  // namespace instag
@@ -93,43 +94,20 @@ using namespace instag;
 extern "C" {
 
 size_t instag_wav2vec_workspace_bytes(const instag_wav2vec_weights* w, int32_t batch, int32_t n_samples) {
-  if (const char* e = shape_error(w)) {
-    set_error(std::string("wav2vec_workspace_bytes: ") + e);
-    return 0;
-  }
   Plan p;
-  if (!make_plan(w, batch, n_samples, MAX_T, &p)) {
-    set_error(std::string("wav2vec_workspace_bytes") + PLAN_ERROR);
-    return 0;
-  }
-  return p.total * sizeof(float);
+  return entry_plan(NET, "workspace_bytes", true, w, batch, n_samples, &p) ? p.total * sizeof(float) : 0;
 }
 
 size_t instag_wav2vec_taps_floats(const instag_wav2vec_weights* w, int32_t batch, int32_t n_samples) {
   Plan p;
-  if (shape_error(w) || !make_plan(w, batch, n_samples, MAX_T, &p)) {
-    set_error(std::string("wav2vec_taps_floats") + PLAN_ERROR);
-    return 0;
-  }
-  return taps_floats(w, batch, p);
+  return entry_plan(NET, "taps_floats", false, w, batch, n_samples, &p) ? taps_floats(w, batch, p) : 0;
 }
 
 int instag_wav2vec_forward(const instag_wav2vec_weights* w, const float* segments, int32_t batch, int32_t n_samples,
                            float* logits, void* workspace, size_t workspace_bytes, int32_t tile, float* taps,
                            instag_stream_t stream) {
-  if (const char* e = shape_error(w)) {
-    set_error(std::string("wav2vec_forward: ") + e);
-    return INSTAG_E_ARG;
-  }
-  INSTAG_REQUIRE(segments && logits && workspace, "wav2vec_forward: NULL tensor");
-  INSTAG_REQUIRE(tile >= 0 && tile <= 3, "wav2vec_forward: tile must be 0..3");
   Plan p;
-  INSTAG_REQUIRE(make_plan(w, batch, n_samples, MAX_T, &p), std::string("wav2vec_forward") + PLAN_ERROR);
-  INSTAG_TRY(require_weights(w, "wav2vec_forward", true));
-  if (workspace_bytes < p.total * sizeof(float)) {
-    set_error("wav2vec_forward: workspace smaller than instag_wav2vec_workspace_bytes(w, batch, n_samples)");
-    return INSTAG_E_SPACE;
-  }
+  INSTAG_TRY(forward_prologue(NET, w, segments, logits, batch, n_samples, workspace, workspace_bytes, tile, &p));
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   const int B = batch, H = w->hidden, T = p.t[N_CONV];

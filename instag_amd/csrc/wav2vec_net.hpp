@@ -187,6 +187,52 @@ int require_weights(const instag_wav2vec_weights* w, const std::string& who, boo
   return INSTAG_OK;
 }
 
+// What tells the entries of wav2vec.hip and hubert.hip apart in their checks: the prefix of their names, the text for a
+// refused batch or length (it names the file's own frame bound), that bound, and whether the network ends in the CTC head.
+struct Net {
+  const char* name;
+  const char* plan_error;
+  int max_t;
+  bool head;
+};
+
+// The plan of entry instag_<net>_<fn>, or false with the error set.  shape_text: say what is wrong with the dimensions
+// (otherwise they are refused with the plan's text, as a batch or a length is).
+bool entry_plan(const Net& net, const char* fn, bool shape_text, const instag_wav2vec_weights* w, int batch, int n_samples,
+                Plan* p) {
+  const std::string who = std::string(net.name) + "_" + fn;
+  const char* e = shape_error(w, net.head);
+  if (e && shape_text) {
+    set_error(who + ": " + e);
+    return false;
+  }
+  if (e || !make_plan(w, batch, n_samples, net.max_t, p)) {
+    set_error(who + net.plan_error);
+    return false;
+  }
+  return true;
+}
+
+// What a forward entry checks before its first launch, in this order: the dimensions, the tensors, the tile, the plan,
+// the weights' pointers and the workspace's size.
+int forward_prologue(const Net& net, const instag_wav2vec_weights* w, const void* in, const void* out, int batch,
+                     int n_samples, const void* workspace, size_t workspace_bytes, int tile, Plan* p) {
+  const std::string who = std::string(net.name) + "_forward";
+  if (const char* e = shape_error(w, net.head)) {
+    set_error(who + ": " + e);
+    return INSTAG_E_ARG;
+  }
+  INSTAG_REQUIRE(in && out && workspace, who + ": NULL tensor");
+  INSTAG_REQUIRE(tile >= 0 && tile <= 3, who + ": tile must be 0..3");
+  if (!entry_plan(net, "forward", false, w, batch, n_samples, p)) return INSTAG_E_ARG;
+  INSTAG_TRY(require_weights(w, who, net.head));
+  if (workspace_bytes < p->total * sizeof(float)) {
+    set_error(who + ": workspace smaller than instag_" + net.name + "_workspace_bytes(w, batch, n_samples)");
+    return INSTAG_E_SPACE;
+  }
+  return INSTAG_OK;
+}
+
 int layernorm(const float* in, float* out, const float* g, const float* b, size_t rows, int C, int gelu, hipStream_t st) {
   layernorm_kernel<<<(unsigned)div_up(rows, (size_t)(TB / 64)), TB, 0, st>>>(in, out, g, b, (int)rows, C, gelu);
   INSTAG_CHECK_LAUNCH();

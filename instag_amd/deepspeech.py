@@ -32,6 +32,8 @@ from dataclasses import asdict, dataclass
 import numpy as np
 import torch
 
+from .device_op import DeviceOperator
+
 SAMPLE_RATE = 16000
 FRAME_LEN, FRAME_STEP, N_FFT = 400, 160, 512             # mfcc: winlen 0.025 s, winstep 0.01 s, nfft 512
 N_FILT, N_CEP, PREEMPHASIS, LIFTER = 26, 26, 0.97, 22
@@ -496,36 +498,23 @@ def deepspeech_torch(weights: DeepSpeechWeights, x, taps=None):
 
 
 # ---- HIP operator -----------------------------------------------------------------------------------------------------
-class DeepSpeechEncoder:
+class DeepSpeechEncoder(DeviceOperator):
     """``logits(x [S, n_in]) -> [S, n_out]``, fp32 on ``device``, on torch's current stream; inference only.  On the GPU
-    the rows go through csrc/deepspeech.hip with one kept workspace (the operator's: use one operator per stream).  The
+    the rows go through csrc/deepspeech.hip in one launch with the kept workspace of device_op.DeviceOperator.  The
     dense layers in front of the recurrence run in time blocks of at most ``max_rows`` steps; the default is the largest
     that keeps the workspace within 1 GiB (the input projections alone are 64 KB a step at the real size), and the
     result does not depend on it by a bit.  On a CPU device it is the torch statement.  ``tile``: 0, or 1..3 to pin the
     GEMM tile (tests)."""
 
     def __init__(self, weights: DeepSpeechWeights, device="cuda", max_rows=None, tile: int = 0):
-        self.weights, self.device, self.tile = weights, torch.device(device), int(tile)
-        self._ws = None
-        if max_rows is not None and int(max_rows) < 1:
-            raise ValueError(f"DeepSpeechEncoder: max_rows >= 1, got {max_rows}")
-        self.max_rows = None if max_rows is None else int(max_rows)
-        if self.device.type == "cuda":
-            from . import _lib
-            self._L = _lib.lib()
-            self._struct, self._keep = weights.device_pack(self.device)
+        self.max_rows, self.tile = self._at_least_one(max_rows, "max_rows"), int(tile)
+        super().__init__(weights, device)
 
     def rows_per_block(self, S: int) -> int:
         """``max_rows`` where given, else the largest block whose workspace for S steps stays within WORKSPACE_LIMIT."""
         if self.max_rows is not None:
             return self.max_rows
         return default_max_rows(self.weights.dims, S)
-
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     @torch.no_grad()
     def logits(self, x, taps=None):
@@ -537,31 +526,20 @@ class DeepSpeechEncoder:
             raise ValueError(f"DeepSpeechEncoder: input rows [S >= 1, {d.n_in}], got {tuple(x.shape)}")
         x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
         if self.device.type != "cuda":
-            stages = None if taps is None else []
-            out = deepspeech_torch(self.weights, x, stages)
-            if taps is not None:
-                taps += [(name, v) for name, v in stages if name != "logits"]
-            return out
+            return self._statement(deepspeech_torch, x, taps, ("logits",))
         from . import _lib
         S = x.shape[0]
         R = self.rows_per_block(S)
-        nbytes = _lib.workspace_bytes(self._L.instag_deepspeech_workspace_bytes(C.byref(self._struct), S, R))
-        ws = self._workspace(nbytes)
+        ws = self._workspace(_lib.workspace_bytes(self._L.instag_deepspeech_workspace_bytes(C.byref(self._struct), S, R)))
         out = torch.empty(S, d.n_out, dtype=torch.float32, device=self.device)
-        flat = None
-        if taps is not None:
-            flat = torch.empty(_lib.workspace_bytes(self._L.instag_deepspeech_taps_floats(C.byref(self._struct), S)),
-                               dtype=torch.float32, device=self.device)
+        flat = None if taps is None else self._taps_buffer(self._L.instag_deepspeech_taps_floats(C.byref(self._struct), S))
         with torch.cuda.device(self.device):
             _lib.check_arg(self._L.instag_deepspeech_forward(
                 C.byref(self._struct), _lib.ptr(x), S, R, _lib.ptr(out), _lib.ptr(ws), ws.numel(), self.tile,
                 _lib.ptr(flat), _lib.current_stream()), "deepspeech_forward")
         if taps is not None:
-            off = 0
-            for name, cols in (("h1", d.hidden), ("h2", d.hidden), ("h3", d.hidden), ("lstm", 2 * d.cell), ("h5", d.hidden)):
-                taps.append((name, flat[off:off + S * cols].view(S, cols)))
-                off += S * cols
-            assert off == flat.numel()
+            taps += self._cut(flat, [(name, (S, cols)) for name, cols in (
+                ("h1", d.hidden), ("h2", d.hidden), ("h3", d.hidden), ("lstm", 2 * d.cell), ("h5", d.hidden))])
         return out
 
     @torch.no_grad()

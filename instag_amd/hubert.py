@@ -13,17 +13,15 @@ The network is the wav2vec 2.0 "large" one of wav2vec.py (stable layer norm, lay
 CTC head: the output is the encoder's last LayerNorm.  On the GPU it runs in csrc/hubert.hip (fp32, inference only),
 whose attention streams the keys, so that a clip's 1000 rows need no 1000 x 1000 scores anywhere; ``hubert_torch`` is
 the plain-torch statement of the same arithmetic (any dtype, CPU or GPU) that the tests compare against and a CPU
-device runs.  The project ships no weights and fetches none.
+device runs.  ``HubertEncoder`` is wav2vec.SegmentEncoder with this file's entry points, statement and clip length.
+The project ships no weights and fetches none.
 """
 from __future__ import annotations
-
-import ctypes as C
 
 import numpy as np
 import torch
 
-from .wav2vec import (CONV_KERNEL, CONV_STRIDE, NORM_EPS, WORKSPACE_LIMIT, _REQUIRED, EncoderWeights, Wav2Vec2Dims,
-                      encoder_torch, frames_of)
+from .wav2vec import NORM_EPS, _REQUIRED, EncoderWeights, SegmentEncoder, encoder_torch, frames_of
 
 KERNEL, STRIDE, CLIP_ROWS = 400, 320, 1000               # hubert.py: one row per 320 samples behind the first 400
 CLIP_SAMPLES = STRIDE * (CLIP_ROWS - 1) + KERNEL           # 320,080
@@ -65,89 +63,20 @@ def normalise_utterance(x) -> torch.Tensor:
     return ((x - x.mean()) / torch.sqrt(x.var(unbiased=False) + NORM_EPS)).float()
 
 
-def default_max_batch(dims: Wav2Vec2Dims) -> int:
-    """The largest batch whose workspace for clips of 320,080 samples stays within WORKSPACE_LIMIT (the entry point
-    works out the size from the dimensions alone: no weights, no GPU)."""
-    from . import _lib
-    s = _lib.Wav2vecWeights()
-    for field, value in dims.__dict__.items():
-        setattr(s, field, value)
-    one = _lib.workspace_bytes(_lib.lib().instag_hubert_workspace_bytes(C.byref(s), 1, CLIP_SAMPLES))
-    return max(1, min(4096, (WORKSPACE_LIMIT - 4096) // one))
+class HubertEncoder(SegmentEncoder):
+    """``hidden(input_values [B,n]) -> [B,T,hidden]`` through csrc/hubert.hip (wav2vec.SegmentEncoder); the default
+    ``max_batch`` is sized for clips of 320,080 samples (4 at the real size: about 240 MB a clip, most of it the first
+    two convolution buffers)."""
+    ENTRY, STATEMENT, OUTPUT, DROPPED, SAMPLES = "hubert", staticmethod(hubert_torch), "hidden", "hidden", CLIP_SAMPLES
+    INPUT = "input values"
 
-
-class HubertEncoder:
-    """``hidden(input_values [B,n]) -> [B,T,hidden]``, fp32 on ``device``, on torch's current stream; inference only.  On
-    the GPU the clips go through csrc/hubert.hip in chunks of at most ``max_batch`` with one kept workspace (the
-    operator's: use one operator per stream); the default ``max_batch`` is the largest whose workspace for clips of
-    320,080 samples stays within 1 GiB (4 at the real size: about 240 MB a clip, most of it the first two convolution
-    buffers).  On a CPU device it is the torch statement.  ``tile``: 0, or 1..3 to pin the GEMM tile (tests)."""
-
-    def __init__(self, weights: HubertWeights, device="cuda", max_batch=None, tile: int = 0):
-        self.weights, self.device, self.tile = weights, torch.device(device), int(tile)
-        self._ws = None
-        if max_batch is not None and int(max_batch) < 1:
-            raise ValueError(f"HubertEncoder: max_batch >= 1, got {max_batch}")
-        self.max_batch = None if max_batch is None else int(max_batch)
-        if self.device.type == "cuda":
-            from . import _lib
-            self._L = _lib.lib()
-            self._struct, self._keep = weights.device_pack(self.device)
-            if self.max_batch is None:
-                self.max_batch = default_max_batch(weights.dims)
-
-    def _bytes(self, batch, n):
-        from . import _lib
-        return _lib.workspace_bytes(self._L.instag_hubert_workspace_bytes(C.byref(self._struct), batch, n))
-
-    @torch.no_grad()
     def hidden(self, input_values, taps=None):
         """``taps``: a list that receives (name, tensor) of every stage as ``hubert_torch``'s does, but for the
         attention probabilities and the output (debug: one chunk only, B <= max_batch)."""
-        x = torch.as_tensor(input_values)
-        if x.dim() != 2:
-            raise ValueError(f"HubertEncoder: input values [B,n], got {tuple(x.shape)}")
-        x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        if self.device.type != "cuda":
-            stages = None if taps is None else []
-            out = hubert_torch(self.weights, x, stages)
-            if taps is not None:
-                taps += [(name, v) for name, v in stages if not name.endswith("attn_probs") and name != "hidden"]
-            return out
-        from . import _lib
-        B, n = x.shape
-        nbytes = self._bytes(max(1, min(B, self.max_batch)), n)              # (refuses a clip that is too short or too long)
-        d, T = self.weights.dims, frames_of(n)
-        out = torch.empty(B, T, d.hidden, dtype=torch.float32, device=self.device)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        flat = None
-        if taps is not None:
-            if B > self.max_batch:
-                raise ValueError(f"HubertEncoder: taps are for one chunk, B = {B} > max_batch = {self.max_batch}")
-            flat = torch.empty(_lib.workspace_bytes(self._L.instag_hubert_taps_floats(C.byref(self._struct), B, n)),
-                               dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            for i in range(0, B, self.max_batch):
-                m = min(self.max_batch, B - i)
-                _lib.check_arg(self._L.instag_hubert_forward(
-                    C.byref(self._struct), _lib.ptr(x[i:i + m]), m, n, _lib.ptr(out[i:i + m]), _lib.ptr(self._ws),
-                    self._ws.numel(), self.tile, _lib.ptr(flat), _lib.current_stream()), "hubert_forward")
-        if taps is not None:
-            off, t = 0, n
-            for l, (k, s) in enumerate(zip(CONV_KERNEL, CONV_STRIDE)):
-                t = (t - k) // s + 1
-                size = B * t * d.conv_dim
-                taps.append((f"conv{l}", flat[off:off + size].view(B, t, d.conv_dim).transpose(1, 2)))
-                off += size
-            names = ["projection", "positional"] + [f"layer{l}.{part}" for l in range(d.layers)
-                                                    for part in ("attention", "feed_forward")]
-            for name in names:
-                taps.append((name, flat[off:off + B * T * d.hidden].view(B, T, d.hidden)))
-                off += B * T * d.hidden
-            assert off == flat.numel()
-        return out
+        return self._encode(input_values, taps)
+
+
+default_max_batch = HubertEncoder.default_max_batch
 
 
 def attention(qkv: torch.Tensor, heads: int, out=None) -> torch.Tensor:

@@ -9,8 +9,9 @@ from every run are joined to [M, 44], and sixteen rows around every second one a
     store, meta = open_identity("data/May", "train", "cuda", audio_extractor="esperanto", audio_features=feats)
 
 On the GPU the network runs in csrc/wav2vec.hip (fp32, inference only); ``wav2vec2_torch`` is the plain-torch statement of
-the same arithmetic (any dtype, CPU or GPU) that the tests compare against and a CPU device runs.  The project ships no
-weights and fetches none.
+the same arithmetic (any dtype, CPU or GPU) that the tests compare against and a CPU device runs.  The operator's host
+side is ``SegmentEncoder``, which hubert.py's operator shares: a device_op.DeviceOperator that states its entry points,
+its statement and its output.  The project ships no weights and fetches none.
 """
 from __future__ import annotations
 
@@ -22,6 +23,8 @@ from dataclasses import asdict, dataclass
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from .device_op import DeviceOperator
 
 CONV_KERNEL, CONV_STRIDE = (10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)
 HEAD_DIM = 64
@@ -385,79 +388,82 @@ def encoder_torch(weights: EncoderWeights, x, taps=None):
 
 
 # ---- HIP operator -----------------------------------------------------------------------------------------------------
-class Wav2Vec2CTC:
-    """``logits(segments [B,n]) -> [B,T,V]``, fp32 on ``device``, on torch's current stream; inference only.  On the GPU
-    the segments go through csrc/wav2vec.hip in chunks of at most ``max_batch`` with one kept workspace (the operator's:
-    use one operator per stream); the default ``max_batch`` is the largest whose workspace for full runs of 22,400
-    samples stays within 1 GiB.  On a CPU device it is the torch statement.  ``tile``: 0, or 1..3 to pin the GEMM tile
-    (the tests hold the tiles against each other bit for bit)."""
+class SegmentEncoder(DeviceOperator):
+    """The one body of ``Wav2Vec2CTC`` and ``hubert.HubertEncoder``: ``_encode(segments [B,n]) -> [B,T,.]``, fp32 on
+    ``device``, on torch's current stream; inference only.  On the GPU the segments go through the ``ENTRY``'s C entry
+    points in chunks of at most ``max_batch`` with the one kept workspace of device_op.DeviceOperator; the default
+    ``max_batch`` is the largest whose workspace for segments of ``SAMPLES`` samples stays within WORKSPACE_LIMIT.  On a
+    CPU device it is the torch statement.  ``tile``: 0, or 1..3 to pin the GEMM tile (the tests hold the tiles against
+    each other bit for bit).  A subclass states the names below."""
 
-    def __init__(self, weights: Wav2Vec2Weights, device="cuda", max_batch=None, tile: int = 0):
-        self.weights, self.device, self.tile = weights, torch.device(device), int(tile)
-        self._ws = None
-        if max_batch is not None and int(max_batch) < 1:
-            raise ValueError(f"Wav2Vec2CTC: max_batch >= 1, got {max_batch}")
-        self.max_batch = None if max_batch is None else int(max_batch)
-        if self.device.type == "cuda":
-            from . import _lib
-            self._L = _lib.lib()
-            self._struct, self._keep = weights.device_pack(self.device)
-            if self.max_batch is None:
-                one = self._bytes(1, RUN_SAMPLES)
-                self.max_batch = max(1, min(4096, (WORKSPACE_LIMIT - 4096) // one))
+    ENTRY = ""               # instag_<ENTRY>_{workspace_bytes, taps_floats, forward}
+    STATEMENT = None         # staticmethod: the torch statement (weights, segments, taps)
+    OUTPUT = ""              # the field of the dimensions that is the output's last dimension
+    DROPPED = ""             # the statement's tap that is the output itself
+    SAMPLES = 0              # the segment length the default max_batch is sized for
+    INPUT = "segments"       # what the messages call the input
 
-    def _bytes(self, batch, n):
+    def __init__(self, weights: EncoderWeights, device="cuda", max_batch=None, tile: int = 0):
+        self.max_batch, self.tile = self._at_least_one(max_batch), int(tile)
+        super().__init__(weights, device)
+        if self.max_batch is None and self.device.type == "cuda":
+            self.max_batch = self.default_max_batch(weights.dims)
+
+    @classmethod
+    def default_max_batch(cls, dims: Wav2Vec2Dims) -> int:
+        """The largest batch whose workspace for segments of ``SAMPLES`` samples stays within WORKSPACE_LIMIT (the entry
+        point works out the size from the dimensions alone: no weights, no GPU)."""
         from . import _lib
-        return _lib.workspace_bytes(self._L.instag_wav2vec_workspace_bytes(C.byref(self._struct), batch, n))
+        s = _lib.Wav2vecWeights()
+        for field, value in asdict(dims).items():
+            setattr(s, field, value)
+        one = _lib.workspace_bytes(cls._entry("workspace_bytes")(C.byref(s), 1, cls.SAMPLES))
+        return max(1, min(4096, (WORKSPACE_LIMIT - 4096) // one))
+
+    @classmethod
+    def _entry(cls, name):
+        from . import _lib
+        return getattr(_lib.lib(), f"instag_{cls.ENTRY}_{name}")
 
     @torch.no_grad()
+    def _encode(self, segments, taps=None):
+        x = torch.as_tensor(segments)
+        if x.dim() != 2:
+            raise ValueError(f"{type(self).__name__}: {self.INPUT} [B,n], got {tuple(x.shape)}")
+        x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if self.device.type != "cuda":
+            return self._statement(self.STATEMENT, x, taps, ("attn_probs", self.DROPPED))
+        from . import _lib
+        B, n = x.shape
+        w, d, T = C.byref(self._struct), self.weights.dims, frames_of(n)
+        # (refuses a segment that is too short or too long)
+        nbytes = _lib.workspace_bytes(self._entry("workspace_bytes")(w, max(1, min(B, self.max_batch)), n))
+        out = torch.empty(B, T, getattr(d, self.OUTPUT), dtype=torch.float32, device=self.device)
+        flat = None if taps is None else self._taps_buffer(self._entry("taps_floats")(w, B, n), B)
+        forward = self._entry("forward")
+        self._each_chunk(B, nbytes, lambda c, m, ws, size: forward(
+            w, _lib.ptr(x[c]), m, n, _lib.ptr(out[c]), ws, size, self.tile, _lib.ptr(flat), _lib.current_stream()),
+            f"{self.ENTRY}_forward")
+        if taps is not None:
+            rows = [n]
+            for k, s in zip(CONV_KERNEL, CONV_STRIDE):
+                rows.append((rows[-1] - k) // s + 1)
+            stages = [(f"conv{l}", (B, t, d.conv_dim)) for l, t in enumerate(rows[1:])]
+            stages += [(name, (B, T, d.hidden)) for name in ["projection", "positional"] + [
+                f"layer{l}.{part}" for l in range(d.layers) for part in ("attention", "feed_forward")]]
+            taps += [(name, v.transpose(1, 2) if name.startswith("conv") else v) for name, v in self._cut(flat, stages)]
+        return out
+
+
+class Wav2Vec2CTC(SegmentEncoder):
+    """``logits(segments [B,n]) -> [B,T,V]`` through csrc/wav2vec.hip (SegmentEncoder); the default ``max_batch`` is
+    sized for full runs of 22,400 samples."""
+    ENTRY, STATEMENT, OUTPUT, DROPPED, SAMPLES = "wav2vec", staticmethod(wav2vec2_torch), "vocab", "logits", RUN_SAMPLES
+
     def logits(self, segments, taps=None):
         """``taps``: a list that receives (name, tensor) of every stage as ``wav2vec2_torch``'s does, but for the
         attention probabilities (debug: one chunk only, B <= max_batch)."""
-        x = torch.as_tensor(segments)
-        if x.dim() != 2:
-            raise ValueError(f"Wav2Vec2CTC: segments [B,n], got {tuple(x.shape)}")
-        x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        if self.device.type != "cuda":
-            stages = None if taps is None else []
-            out = wav2vec2_torch(self.weights, x, stages)
-            if taps is not None:
-                taps += [(name, v) for name, v in stages if not name.endswith("attn_probs") and name != "logits"]
-            return out
-        from . import _lib
-        B, n = x.shape
-        nbytes = self._bytes(max(1, min(B, self.max_batch)), n)              # (refuses a run that is too short or too long)
-        d, T = self.weights.dims, frames_of(n)
-        out = torch.empty(B, T, d.vocab, dtype=torch.float32, device=self.device)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        flat = None
-        if taps is not None:
-            if B > self.max_batch:
-                raise ValueError(f"Wav2Vec2CTC: taps are for one chunk, B = {B} > max_batch = {self.max_batch}")
-            flat = torch.empty(_lib.workspace_bytes(self._L.instag_wav2vec_taps_floats(C.byref(self._struct), B, n)),
-                               dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            for i in range(0, B, self.max_batch):
-                m = min(self.max_batch, B - i)
-                _lib.check_arg(self._L.instag_wav2vec_forward(
-                    C.byref(self._struct), _lib.ptr(x[i:i + m]), m, n, _lib.ptr(out[i:i + m]), _lib.ptr(self._ws),
-                    self._ws.numel(), self.tile, _lib.ptr(flat), _lib.current_stream()), "wav2vec_forward")
-        if taps is not None:
-            off, t = 0, n
-            for l, (k, s) in enumerate(zip(CONV_KERNEL, CONV_STRIDE)):
-                t = (t - k) // s + 1
-                size = B * t * d.conv_dim
-                taps.append((f"conv{l}", flat[off:off + size].view(B, t, d.conv_dim).transpose(1, 2)))
-                off += size
-            names = ["projection", "positional"] + [f"layer{l}.{part}" for l in range(d.layers)
-                                                    for part in ("attention", "feed_forward")]
-            for name in names:
-                taps.append((name, flat[off:off + B * T * d.hidden].view(B, T, d.hidden)))
-                off += B * T * d.hidden
-            assert off == flat.numel()
-        return out
+        return self._encode(segments, taps)
 
 
 # ---- the streaming rule and the features ----------------------------------------------------------------------------

@@ -8,16 +8,17 @@ Every figure is the median of WINDOWS windows of ITERS calls, timed with device 
 are measured in alternating windows of one process.  FLOPs are 2 x the multiply-adds of the thirteen convolutions
 (ave_encoder.MACS_PER_WINDOW per window); the peak is the 157.3 TFLOP/s of the fp32 MFMA.  Per layer: the operator's
 twelve launches from a device trace (layers 11 and 12 are one launch), the torch chain block by block with events."""
-import argparse, json, os, statistics, sys
+import argparse, os, statistics, sys
 import torch
 import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _bench_audio import agreement, alternate, dump, summary
 from instag_amd import ave_encoder as AE
 
 WINDOWS, ITERS = 7, 10
 N_WINDOWS = 1500
 TORCH_BATCH = 128
-PEAK_TFLOPS = 157.3
 dev = torch.device("cuda")
 
 
@@ -97,26 +98,14 @@ def main():
             return torch.cat([AE.audio_encoder_torch(w, windows[i:i + TORCH_BATCH])
                               for i in range(0, N_WINDOWS, TORCH_BATCH)])
 
-    # faster and different is not faster: the two paths agree on the timed inputs
-    got, want = hip(), lib()
-    rel = float((got - want).abs().max() / want.abs().max())
-    assert rel < 1e-5, rel
+    rel = agreement(hip(), lib(), 1e-5)
     for f in (hip, lib):
         window(f, 3)
-    t = {"hip": [], "torch": []}
-    for _ in range(WINDOWS):
-        t["hip"].append(window(hip))
-        t["torch"].append(window(lib))
-    flop = 2.0 * AE.MACS_PER_WINDOW * N_WINDOWS
-    res = dict(windows=N_WINDOWS, gflop_per_clip=flop / 1e9, max_batch=enc.max_batch, hip_vs_torch_rel=rel)
-    for k in ("hip", "torch"):
-        ms = statistics.median(t[k])
-        res[f"{k}_ms_per_clip"] = ms
-        res[f"{k}_min_ms"] = min(t[k])
-        res[f"{k}_tflops"] = flop / (ms * 1e-3) / 1e12
-        res[f"{k}_fraction_of_fp32_mfma_peak"] = res[f"{k}_tflops"] / PEAK_TFLOPS
-        print(f"{k:5s}: {ms:.3f} ms per clip (min {min(t[k]):.3f}), {res[f'{k}_tflops']:.2f} TFLOP/s, "
-              f"{100 * res[f'{k}_fraction_of_fp32_mfma_peak']:.1f} % of the fp32 MFMA peak", flush=True)
+    t = alternate({"hip": hip, "torch": lib}, WINDOWS, window)
+    res = dict(windows=N_WINDOWS, gflop_per_clip=2.0 * AE.MACS_PER_WINDOW * N_WINDOWS / 1e9, max_batch=enc.max_batch,
+               hip_vs_torch_rel=rel)
+    for k, text in summary(res, t, AE.MACS_PER_WINDOW * N_WINDOWS, "{}_ms_per_clip").items():
+        print(f"{k:5s}: {res[f'{k}_ms_per_clip']:.3f} ms per clip (min {res[f'{k}_min_ms']:.3f}), {text}", flush=True)
     res["hip_layers_us"] = operator_layers(hip)
     res["torch_layers_us"] = torch_layers(w, windows[:TORCH_BATCH])
     print("per layer, us per clip (operator | torch chain):")
@@ -125,10 +114,7 @@ def main():
     for k, v in res["hip_layers_us"].items():
         if k not in res["torch_layers_us"]:
             print(f"  {k:12s} {v!s:>10} |")
-    print(json.dumps(res), flush=True)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    dump(res, a.json)
 
 
 if __name__ == "__main__":

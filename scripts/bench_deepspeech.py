@@ -10,11 +10,12 @@ timed with device events, the two paths in alternating windows.  A step of the r
 weights, 2 x 4 cell^2 floats (128 MiB): bytes per step over the step time is the rate at which the step kernel streams
 them.  The weights take about 0.3 GB on the host and as much on the device: not for the test suite.
 """
-import argparse, json, os, statistics, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
-from _bench_frames import WINDOWS, operator_kernels, window
+from _bench_audio import agreement, alternate, dump, seeded_wav, summary
+from _bench_frames import operator_kernels
 from instag_amd import deepspeech as D
 from tests.deepspeech_helpers import torch_chain, torch_lstm
 
@@ -26,12 +27,7 @@ if __name__ == "__main__":
     dev = torch.device("cuda")
     dims = D.DeepSpeechDims()
     weights = D.DeepSpeechWeights.random(dims, 0)
-    n = 16000 * a.seconds
-    g = torch.Generator().manual_seed(1)
-    t = torch.arange(n, dtype=torch.float64) / 16000.0
-    wav = (0.3 * torch.sin(6.283185307179586 * 220.0 * t) * (1.0 + torch.sin(6.283185307179586 * 1.5 * t))
-           + 0.05 * torch.randn(n, generator=g, dtype=torch.float64)).float()
-    rows = torch.from_numpy(D.input_vectors(D.to_int16(wav))).to(dev)
+    rows = torch.from_numpy(D.input_vectors(D.to_int16(seeded_wav(a.seconds)))).to(dev)
     S = rows.shape[0]
     op = D.DeepSpeechEncoder(weights, dev)
     chain = torch_chain(weights, dev, torch.float32)
@@ -43,9 +39,7 @@ if __name__ == "__main__":
     def lib():
         return chain(rows)
 
-    got, want = hip(), lib()                                  # (the warm-up) faster and different is not faster
-    rel = float((got - want).abs().max() / want.abs().max())
-    assert rel < 1e-4, rel
+    rel = agreement(hip(), lib())                             # (the warm-up)
     taps = []
     op.logits(rows, taps)
     h3, hseq = dict(taps)["h3"], dict(taps)["lstm"]
@@ -63,17 +57,11 @@ if __name__ == "__main__":
 
     rel_lstm = float((hip_lstm() - lib_lstm()[:, 0]).abs().max() / hseq.abs().max())
     assert rel_lstm < 1e-4, rel_lstm
-    times = {"hip": [], "torch": [], "hip_lstm": [], "torch_lstm": []}
-    for _ in range(WINDOWS):
-        times["hip"].append(window(hip))
-        times["torch"].append(window(lib))
-        times["hip_lstm"].append(window(hip_lstm))
-        times["torch_lstm"].append(window(lib_lstm))
+    times = alternate({"hip": hip, "torch": lib, "hip_lstm": hip_lstm, "torch_lstm": lib_lstm})
     step_bytes = 2 * 4 * dims.cell * dims.cell * 4
     res = dict(seconds=a.seconds, steps=S, max_rows=op.rows_per_block(S), dims=dims.__dict__, device=torch.cuda.get_device_name(0),
                logits_hip_vs_torch_rel=rel, lstm_hip_vs_torch_rel=rel_lstm, recurrent_weight_bytes_per_step=step_bytes)
-    for k, v in times.items():
-        res[f"{k}_ms"], res[f"{k}_min_ms"] = statistics.median(v), min(v)
+    summary(res, times)
     res["hip_step_us"] = 1e3 * res["hip_lstm_ms"] / S
     res["torch_step_us"] = 1e3 * res["torch_lstm_ms"] / S
     res["hip_step_gb_per_s"] = step_bytes / (res["hip_step_us"] * 1e-6) / 1e9
@@ -88,9 +76,4 @@ if __name__ == "__main__":
           f"of recurrent weights; torch.nn.LSTM {res['torch_lstm_ms']:.1f} ms, {res['torch_step_us']:.1f} us a step; ours / torch's "
           f"{res['hip_lstm_over_torch_lstm']:.3f}", flush=True)
     res["hip_kernels"] = operator_kernels(hip)
-    for k, v in res["hip_kernels"].items():
-        print(f"  {k:62s} {v}")
-    print(json.dumps(res), flush=True)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    dump(res, a.json, res["hip_kernels"])

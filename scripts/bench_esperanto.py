@@ -8,11 +8,12 @@ windows after one warm-up pass of each path (the agreement check), timed with de
 windows of one process.  FLOPs are 2 x wav2vec.macs per run; the peak is the 157.3 TFLOP/s of the fp32 MFMA.  The
 weights take about 2.5 GB (host and device copy): not for the test suite.
 """
-import argparse, json, os, statistics, sys
+import argparse, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
-from _bench_frames import PEAK_TFLOPS, WINDOWS, operator_kernels, window
+from _bench_audio import agreement, alternate, dump, seeded_wav, summary
+from _bench_frames import WINDOWS, operator_kernels, window
 from instag_amd import wav2vec as W
 
 TEETH_FRACTION = 0.398          # of the peak: the teeth segmenter's convolution (profiles/teeth_bench.json)
@@ -27,10 +28,7 @@ if __name__ == "__main__":
     dims = W.Wav2Vec2Dims()
     weights = W.Wav2Vec2Weights.random(dims, 0)
     n = 16000 * a.seconds
-    g = torch.Generator().manual_seed(1)
-    t = torch.arange(n, dtype=torch.float64) / 16000.0
-    wav = (0.3 * torch.sin(6.283185307179586 * 220.0 * t) * (1.0 + torch.sin(6.283185307179586 * 1.5 * t))
-           + 0.05 * torch.randn(n, generator=g, dtype=torch.float64)).float().to(dev)
+    wav = seeded_wav(a.seconds).to(dev)
     plan = W.segment_plan(n)
     runs = [torch.cat([wav.new_zeros(z * W.CHUNK), wav[s * W.CHUNK: s * W.CHUNK + m - z * W.CHUNK]]) for s, z, m, _, _ in plan]
     full = torch.stack([r for r in runs if r.numel() == W.RUN_SAMPLES])
@@ -46,26 +44,16 @@ if __name__ == "__main__":
         with torch.no_grad():
             return [W.wav2vec2_torch(weights, full)] + [W.wav2vec2_torch(weights, r) for r in rest]
 
-    got, want = hip(), lib()                                  # (the warm-up) faster and different is not faster
-    rel = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(got, want))
-    assert rel < 1e-4, rel
-    times = {"hip": [], "torch": []}
-    for _ in range(WINDOWS):
-        times["hip"].append(window(hip))
-        times["torch"].append(window(lib))
+    got = hip()
+    rel = agreement(got, lib())                               # (the warm-up)
+    times = alternate({"hip": hip, "torch": lib})
     mac = sum(W.macs(dims, r.numel()) for r in runs)
     res = dict(seconds=a.seconds, runs=len(runs), rows=rows, windows=rows // 2 + 1, max_batch=op.max_batch,
                gmac_per_full_run=W.macs(dims) / 1e9, gmac=mac / 1e9, logits_hip_vs_torch_rel=rel,
                teeth_fraction_of_fp32_mfma_peak=TEETH_FRACTION)
-    for k in ("hip", "torch"):
-        ms = statistics.median(times[k])
-        res[f"{k}_ms"], res[f"{k}_min_ms"] = ms, min(times[k])
-        res[f"{k}_tflops"] = 2.0 * mac / (ms * 1e-3) / 1e12
-        res[f"{k}_fraction_of_fp32_mfma_peak"] = res[f"{k}_tflops"] / PEAK_TFLOPS
-        print(f"{k:5s}: {ms:.1f} ms for {len(runs)} runs of {a.seconds} s of audio (min {min(times[k]):.1f}), "
-              f"{W.macs(dims) / 1e9:.2f} GMAC per run, {res[f'{k}_tflops']:.2f} TFLOP/s, "
-              f"{100 * res[f'{k}_fraction_of_fp32_mfma_peak']:.1f} % of the fp32 MFMA peak "
-              f"(teeth convolution: {100 * TEETH_FRACTION:.1f} %)", flush=True)
+    for k, text in summary(res, times, mac).items():
+        print(f"{k:5s}: {res[f'{k}_ms']:.1f} ms for {len(runs)} runs of {a.seconds} s of audio (min {res[f'{k}_min_ms']:.1f}), "
+              f"{W.macs(dims) / 1e9:.2f} GMAC per run, {text} (teeth convolution: {100 * TEETH_FRACTION:.1f} %)", flush=True)
     if a.tiles:                                               # every GEMM pinned to one tile: what the choice is worth
         for tile, name in ((1, "64x64"), (2, "64x128"), (3, "128x128")):
             op.tile = tile
@@ -74,9 +62,4 @@ if __name__ == "__main__":
             print(f"  every GEMM on {name}: {res[f'hip_ms_tile_{name}']:.1f} ms")
         op.tile = 0
     res["hip_kernels_full_batch"] = operator_kernels(lambda: op.logits(full))
-    for k, v in res["hip_kernels_full_batch"].items():
-        print(f"  {k:62s} {v}")
-    print(json.dumps(res), flush=True)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    dump(res, a.json, res["hip_kernels_full_batch"])

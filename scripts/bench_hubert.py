@@ -10,12 +10,13 @@ the two paths in alternating windows of one process.  FLOPs are 2 x wav2vec.macs
 are 2 * 2 * T^2 * 64 * heads per segment, its windows are 20 calls each into a kept output and alternate too; the peak is the 157.3 TFLOP/s of the fp32 MFMA.  The input is seeded noise on a
 modulated tone.  The weights take about 2.5 GB (host and device copy): not for the test suite.
 """
-import argparse, json, os, statistics, sys
+import argparse, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 import torch.nn.functional as F
-from _bench_frames import PEAK_TFLOPS, WINDOWS, operator_kernels, window
+from _bench_audio import agreement, alternate, dump, seeded_wav, summary
+from _bench_frames import operator_kernels
 from instag_amd import hubert as HU
 from instag_amd import wav2vec as W
 
@@ -31,10 +32,7 @@ if __name__ == "__main__":
     dims = W.Wav2Vec2Dims()
     weights = HU.HubertWeights.random(dims, 0)
     n = 16000 * a.seconds
-    g = torch.Generator().manual_seed(1)
-    t = torch.arange(n, dtype=torch.float64) / 16000.0
-    wav = (0.3 * torch.sin(6.283185307179586 * 220.0 * t) * (1.0 + torch.sin(6.283185307179586 * 1.5 * t))
-           + 0.05 * torch.randn(n, generator=g, dtype=torch.float64)).float()
+    wav = seeded_wav(a.seconds)
     plan, rows = HU.clip_plan(n)
     values = HU.normalise_utterance(wav).to(dev)
     clips = [values[s:s + m] for s, m in plan]
@@ -50,27 +48,16 @@ if __name__ == "__main__":
         with torch.no_grad():
             return [HU.hubert_torch(weights, c) for c in chunks]
 
-    got, want = hip(), lib()                                  # (the warm-up) faster and different is not faster
-    rel = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(got, want))
-    assert rel < 1e-4, rel
-    del got, want
-    times = {"hip": [], "torch": []}
-    for _ in range(WINDOWS):
-        times["hip"].append(window(hip))
-        times["torch"].append(window(lib))
+    rel = agreement(hip(), lib())                             # (the warm-up)
+    times = alternate({"hip": hip, "torch": lib})
     mac = sum(W.macs(dims, c.numel(), head=False) for c in clips)
     res = dict(seconds=a.seconds, clips=[W.frames_of(c.numel()) for c in clips], rows=rows, pairs=rows // 2,
                chunks=[list(c.shape) for c in chunks], max_batch=op.max_batch,
                gmac_per_full_clip=W.macs(dims, HU.CLIP_SAMPLES, head=False) / 1e9, gmac=mac / 1e9,
                hidden_hip_vs_torch_rel=rel, esperanto_hip_over_torch=ESPERANTO_RATIO)
-    for k in ("hip", "torch"):
-        ms = statistics.median(times[k])
-        res[f"{k}_ms"], res[f"{k}_min_ms"] = ms, min(times[k])
-        res[f"{k}_tflops"] = 2.0 * mac / (ms * 1e-3) / 1e12
-        res[f"{k}_fraction_of_fp32_mfma_peak"] = res[f"{k}_tflops"] / PEAK_TFLOPS
-        print(f"{k:5s}: {ms:.1f} ms for {len(clips)} clips of {a.seconds} s of audio (min {min(times[k]):.1f}), "
-              f"{res[f'{k}_tflops']:.2f} TFLOP/s, {100 * res[f'{k}_fraction_of_fp32_mfma_peak']:.1f} % of the fp32 MFMA peak",
-              flush=True)
+    for k, text in summary(res, times, mac).items():
+        print(f"{k:5s}: {res[f'{k}_ms']:.1f} ms for {len(clips)} clips of {a.seconds} s of audio "
+              f"(min {res[f'{k}_min_ms']:.1f}), {text}", flush=True)
     res["hip_over_torch"] = res["hip_ms"] / res["torch_ms"]
     res["within_bar_1p05"] = res["hip_over_torch"] <= 1.05
     print(f"operator / torch chain: {res['hip_over_torch']:.3f} (bar 1.05; esperanto {ESPERANTO_RATIO}); the outputs differ by "
@@ -98,10 +85,7 @@ if __name__ == "__main__":
         diff = float((HU.attention(qkv, dims.heads) - F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T, -1))
                      .abs().max())
         ours(), sdpa()
-        t_ours, t_sdpa = [], []
-        for _ in range(WINDOWS):                                  # alternating, as the whole path above
-            t_ours.append(window(ours) / ATTENTION_REPEATS)
-            t_sdpa.append(window(sdpa) / ATTENTION_REPEATS)
+        t_ours, t_sdpa = ([t / ATTENTION_REPEATS for t in ts] for ts in alternate({"hip": ours, "sdpa": sdpa}).values())
         flop = 2.0 * 2.0 * T * T * 64 * dims.heads * B
         entry = dict(batch=B, frames=T, heads=dims.heads, hip_us=1e3 * statistics.median(t_ours), hip_min_us=1e3 * min(t_ours),
                      sdpa_us=1e3 * statistics.median(t_sdpa), sdpa_min_us=1e3 * min(t_sdpa), max_abs_diff=diff)
@@ -113,9 +97,4 @@ if __name__ == "__main__":
               f"{entry['sdpa_us']:.1f} us, {entry['sdpa_tflops']:.2f} TFLOP/s; ours / sdpa {entry['hip_over_sdpa']:.2f}"
               + ("  (SLOWER than torch's)" if entry["hip_over_sdpa"] > 1.0 else ""), flush=True)
     res["hip_kernels_first_chunk"] = operator_kernels(lambda: op.hidden(chunks[0]))
-    for k, v in res["hip_kernels_first_chunk"].items():
-        print(f"  {k:62s} {v}")
-    print(json.dumps(res), flush=True)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    dump(res, a.json, res["hip_kernels_first_chunk"])

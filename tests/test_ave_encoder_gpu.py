@@ -116,6 +116,23 @@ def test_batch_independence_bitwise(g9_weights):
     assert not torch.equal(rows[0], rows[mb])
 
 
+def test_a_smaller_call_keeps_the_workspace(g9_weights):
+    """max_batch + 1 windows (the chunk tail), then one: the second call needs fewer bytes, so the workspace stays
+    where it is; both results are a fresh operator's bit for bit."""
+    from instag_amd.ave_encoder import AudioEncoder, cut_windows
+    enc = AudioEncoder(g9_weights, "cuda")
+    seven = cut_windows(H.seeded_mel(34, seed=2))
+    big = seven[torch.arange(enc.max_batch + 1) % 7].contiguous().cuda()
+    first = enc.encode_windows(big).clone()
+    where, size = enc._ws.data_ptr(), enc._ws.numel()
+    second = enc.encode_windows(big[:1])
+    assert enc._ws.data_ptr() == where and enc._ws.numel() == size
+    assert tuple(first.shape) == (enc.max_batch + 1, 512) and float(second.abs().max()) > 0
+    assert torch.equal(first, AudioEncoder(g9_weights, "cuda").encode_windows(big))
+    assert torch.equal(second, AudioEncoder(g9_weights, "cuda").encode_windows(big[:1]))
+    assert torch.equal(second[0], first[0]) and torch.equal(first[enc.max_batch], first[enc.max_batch % 7])
+
+
 def test_two_calls_same_bits(g9, g9_weights):
     from instag_amd.ave_encoder import AudioEncoder
     mel = torch.from_numpy(g9["mel"].astype(np.float32)).cuda()

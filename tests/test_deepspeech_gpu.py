@@ -146,6 +146,21 @@ def test_max_rows_tile_and_call_give_the_same_bits(ops):
             assert torch.equal(DeepSpeechEncoder(H.weights(name), "cuda", max_rows=3, tile=tile).logits(x), base), (name, tile)
 
 
+def test_a_smaller_call_keeps_the_workspace():
+    """67 steps, then one: the second call needs fewer bytes, so the workspace stays where it is; both results are a
+    fresh operator's bit for bit."""
+    from instag_amd.deepspeech import DeepSpeechEncoder
+    w, big, small = H.weights("A"), H.case("A", 67).x.cuda(), H.case("A", 1).x.cuda()
+    op = DeepSpeechEncoder(w, "cuda")
+    first = op.logits(big).clone()
+    where, size = op._ws.data_ptr(), op._ws.numel()
+    second = op.logits(small)
+    assert op._ws.data_ptr() == where and op._ws.numel() == size
+    assert tuple(first.shape) == (67, 29) and tuple(second.shape) == (1, 29) and float(second.abs().max()) > 0
+    assert torch.equal(first, DeepSpeechEncoder(w, "cuda").logits(big))
+    assert torch.equal(second, DeepSpeechEncoder(w, "cuda").logits(small))
+
+
 def test_clip_is_active_on_the_gpu_path():
     from instag_amd.deepspeech import DeepSpeechEncoder
     w = H.scaled(H.scaled(H.weights("A"), "h1", 60.0), "h5", 200.0)

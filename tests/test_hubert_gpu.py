@@ -184,6 +184,21 @@ def test_bits_do_not_depend_on_call_operator_batch_or_tile():
     _check("chunked", first, case.want, e32, scale)
 
 
+def test_a_smaller_call_keeps_the_workspace():
+    """Three segments of 6130 samples in chunks of two (the chunk tail), then one of 400: the second call needs fewer
+    bytes, so the workspace stays where it is; both results are a fresh operator's bit for bit."""
+    from instag_amd.hubert import HubertEncoder
+    w, big, small = H.weights("S"), H.values_of(3, 6130, seed=6130).cuda(), H.values_of(1, 400, seed=400).cuda()
+    op = HubertEncoder(w, "cuda", max_batch=2)
+    first = op.hidden(big).clone()
+    where, size = op._ws.data_ptr(), op._ws.numel()
+    second = op.hidden(small)
+    assert op._ws.data_ptr() == where and op._ws.numel() == size
+    assert tuple(first.shape) == (3, 18, 128) and tuple(second.shape) == (1, 1, 128) and float(second.abs().max()) > 0
+    assert torch.equal(first, HubertEncoder(w, "cuda", max_batch=2).hidden(big))
+    assert torch.equal(second, HubertEncoder(w, "cuda", max_batch=2).hidden(small))
+
+
 def test_features_of_a_wav():
     """hubert_features on the GPU == the same with the torch statement (fp32, on the GPU) in place of the operator: one
     full clip of 1000 rows plus a remainder of 31.  Both are within 8 x e32 (the operator, tested above) and e32 (the

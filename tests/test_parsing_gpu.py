@@ -154,6 +154,21 @@ def test_chunking_bitwise(g14_weights):
     _check_logits("chunked", logits[pick], c)
 
 
+def test_a_smaller_call_keeps_the_workspace(g14_weights):
+    """Three 64 x 64 frames in chunks of two (the chunk tail), then one: the second call needs fewer bytes, so the
+    workspace stays where it is; both results are a fresh operator's bit for bit."""
+    from instag_amd.parsing import FaceParser
+    frames = H.seeded_frames(3, 64, 64, seed=12).cuda()
+    parser = FaceParser(g14_weights, "cuda", max_batch=2)
+    first = parser.logits(frames).clone()
+    where, size = parser._ws.data_ptr(), parser._ws.numel()
+    second = parser.logits(frames[:1])
+    assert parser._ws.data_ptr() == where and parser._ws.numel() == size
+    assert tuple(first.shape) == (3, 19, 8, 8) and float(second.abs().max()) > 0
+    assert torch.equal(first, FaceParser(g14_weights, "cuda", max_batch=2).logits(frames))
+    assert torch.equal(second, FaceParser(g14_weights, "cuda", max_batch=2).logits(frames[:1]))
+
+
 def test_two_calls_same_bits(g14, g14_weights):
     from instag_amd.parsing import FaceParser
     frames = torch.from_numpy(g14["frame"])[None].cuda()

@@ -134,6 +134,21 @@ def test_bits_do_not_depend_on_call_operator_batch_or_tile():
     _check("chunked", first, case.want, e32, scale)
 
 
+def test_a_smaller_call_keeps_the_workspace():
+    """Three segments of 6130 samples in chunks of two (the chunk tail), then one of 400: the second call needs fewer
+    bytes, so the workspace stays where it is; both results are a fresh operator's bit for bit."""
+    from instag_amd.wav2vec import Wav2Vec2CTC
+    w, big, small = H.weights("S"), H.seeded_audio(3, 6130, seed=6130).cuda(), H.seeded_audio(1, 400, seed=400).cuda()
+    op = Wav2Vec2CTC(w, "cuda", max_batch=2)
+    first = op.logits(big).clone()
+    where, size = op._ws.data_ptr(), op._ws.numel()
+    second = op.logits(small)
+    assert op._ws.data_ptr() == where and op._ws.numel() == size
+    assert tuple(first.shape) == (3, 18, 44) and tuple(second.shape) == (1, 1, 44) and float(second.abs().max()) > 0
+    assert torch.equal(first, Wav2Vec2CTC(w, "cuda", max_batch=2).logits(big))
+    assert torch.equal(second, Wav2Vec2CTC(w, "cuda", max_batch=2).logits(small))
+
+
 class NoEncoder(torch.nn.Module):          # the tri-plane encoders play no part in the per-frame branch
     def __init__(self, **kw):
         super().__init__()
