@@ -64,6 +64,10 @@ _FACE_DETECT_STRUCTS, _FACE_DETECT_PROTOTYPES, FACE_DETECT = _cabi.read(os.path.
                                                                                    "instag_face_detect.h"))
 globals().update((cls.__name__, cls) for cls in _FACE_DETECT_STRUCTS.values())
 
+# The tri-plane encode fused into the motion fields' forward MLP kernels, include/instag_encode_mlp.h
+# (instag_amd/encode_mlp.py): the three instag_triplane_mlp* entry points, no struct and no constant.
+_, _ENCODE_MLP_PROTOTYPES, _ = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_encode_mlp.h"))
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -231,7 +235,8 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
                                   **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES,
-                                  **_LANDMARKS_PROTOTYPES, **_FACE_DETECT_PROTOTYPES}.items():
+                                  **_LANDMARKS_PROTOTYPES, **_FACE_DETECT_PROTOTYPES,
+                                  **_ENCODE_MLP_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

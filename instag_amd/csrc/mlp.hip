@@ -21,6 +21,8 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "instag_encode_mlp.h"
+#include "triplane_device.hpp"
 
 namespace instag {
 namespace {
@@ -702,6 +704,139 @@ mlp2_backward_kernel(Mlp2Dims d, const float* __restrict__ dYA, const float* __r
   }
 }
 
+// ---- tri-plane encode in front of the first layer ------------------------------------------------------------------------
+// A motion field opens with its tri-plane encode (csrc/grid.hip: triplane_forward_all_kernel) and the MLPs that read the
+// [N,36] feature rows: align_net for the personalised field, the two attention heads for the universal one.  As two
+// launches the pair pays two staging prologues, two launch ramps and two tails, and the MLP's first action is a dependent
+// read of rows the encode has only just written.  Here one workgroup per CU keeps the three tables AND the weights in LDS
+// and a wave evaluates the rows of its tile straight into the first layer's operand registers: lane (row, h) holds the
+// feature groups 8 g + 4 h .. + 3 (g = 0..4), a feature is plane * 12 + level, so every group is four levels of one plane
+// -- one tp_group4 -- and no value moves between lanes.  The rows are still written out (enc_x: sigma_net's glue and three
+// first-layer weight gradients read them), by the same 16-byte stores store_block would issue.  Same arithmetic as the
+// split kernels, statement for statement: identical bits.
+constexpr uint32_t TPM_L = 12, TPM_K = 3 * TPM_L;
+
+// tables -> LDS [3][T]; returns where the weights go (16-byte aligned)
+template <int THREADS>
+__device__ __forceinline__ float* tpm_stage_tables(const TriPlaneArgs& a, float* s_mem, TpLevel* s_lv, uint32_t T) {
+  tp_levels(a, s_lv);
+#pragma unroll
+  for (int plane = 0; plane < 3; ++plane) tp_stage_table<THREADS, false>(s_mem + plane * T, nullptr, a.tables[plane], T);
+  return s_mem + ((3u * T + 3u) & ~3u);
+}
+
+// features of row `row` in the layout load_block would give them (rows past N and features past 36: zeros).  Branch-free:
+// the half wave without a fifth group (8 * 4 + 4 = 36) evaluates group 32 again and drops it.
+__device__ __forceinline__ void tpm_encode_tile(const TriPlaneArgs& a, const TpLevel* s_lv, const float* s_tab, uint32_t T,
+                                                size_t row, bool valid, int h, float inv2b, f32x16 (&in0)[2]) {
+  float p[3];
+  tp_point(a, valid ? (uint32_t)row : 0u, p);
+#pragma unroll
+  for (int i = 4; i < 16; ++i) in0[1][i] = 0.f;
+#pragma unroll
+  for (int g = 0; g < 5; ++g) {
+    const int f0 = 8 * g + 4 * h;
+    const bool live = valid && f0 < (int)TPM_K;
+    const uint32_t fc = f0 < (int)TPM_K ? (uint32_t)f0 : TPM_K - 4u;
+    const uint32_t plane = fc / TPM_L, l4 = fc - plane * TPM_L;
+    float xw[2];
+    plane_coords((int)plane, p, xw);
+    const float x0 = (xw[0] + a.bound) * inv2b, x1 = (xw[1] + a.bound) * inv2b;
+    const bool oob = x0 < 0.f || x0 > 1.f || x1 < 0.f || x1 > 1.f;
+    float v[4];
+    tp_group4(s_lv, s_tab + plane * T, TPM_L, l4, x0, x1, oob, v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) in0[g >> 2][4 * (g & 3) + i] = live ? v[i] : 0.f;
+  }
+}
+
+// encode -> the 2-layer MLP of mlp_forward_kernel<5, 4, 1, 2, false, KEEP> (align_net: 36 -> 32 -> 6)
+template <int THREADS, bool KEEP>
+__global__ void __launch_bounds__(THREADS)
+triplane_mlp_forward_kernel(TriPlaneArgs a, MlpDims d, const float* __restrict__ W1, const float* __restrict__ W2,
+                            float* __restrict__ enc_x, float* __restrict__ Y, float* __restrict__ A1,
+                            uint32_t* __restrict__ S1) {
+  extern __shared__ __align__(16) float s_mem[];
+  __shared__ TpLevel s_lv[TP_MAX_L];
+  constexpr int KQ0 = 5, HQ = 4, KB0 = 2, HB = 1, WAVES = THREADS / 64;
+  const uint32_t T = (uint32_t)a.offsets[a.L];
+  float* w1 = tpm_stage_tables<THREADS>(a, s_mem, s_lv, T);      // [32][64+1]
+  float* w2 = w1 + 32 * (KB0 * 32 + 1);                         // [32][32+1]
+  stage_weights<32, KB0, THREADS>(w1, W1, d.H, d.K0);
+  stage_weights<32, HB, THREADS>(w2, W2, d.O, d.H);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
+  const int ntiles = (d.N + 31) / 32;
+  const float inv2b = 1.0f / (2.0f * a.bound);
+  for (int tile = blockIdx.x * WAVES + wave; tile < ntiles; tile += gridDim.x * WAVES) {
+    const size_t row = (size_t)tile * 32 + l31;
+    const bool valid = row < (size_t)d.N;
+    f32x16 in0[KB0];
+    tpm_encode_tile(a, s_lv, s_mem, T, row, valid, h, inv2b, in0);
+#pragma unroll
+    for (int b = 0; b < KB0; ++b) store_block<(int)TPM_K>(enc_x, row, valid, (int)TPM_K, b, h, in0[b]);
+    f32x16 h1[HB], out[1];
+    layer_forward<KQ0, KB0, HB>(w1, in0, h1, l31, h);
+    relu_blocks<HB>(h1);
+    if (A1) store_blocks<HB, 8 * HQ>(A1, row, valid, d.H, h, h1);
+    uint32_t sw1 = 0;
+    layer_forward<HQ, HB, 1, KEEP>(w2, h1, out, l31, h, &sw1);
+    if constexpr (KEEP) S1[(size_t)tile * 64 + lane] = sw1;
+    store_block(Y, row, valid, d.O, 0, h, out[0]);
+  }
+}
+
+// encode -> the body of mlp2_forward_kernel<5, 4, 4, 2, 1, KEEP> (aud_ch_att_net 36 -> 32 -> 32, eye_att_net 36 -> 16 -> 6)
+template <int THREADS, bool KEEP>
+__global__ void __launch_bounds__(THREADS)
+triplane_mlp2_forward_kernel(TriPlaneArgs a, Mlp2Dims d, const float* __restrict__ WA1, const float* __restrict__ WA2,
+                             const float* __restrict__ WB1, const float* __restrict__ WB2, float* __restrict__ enc_x,
+                             float* __restrict__ YA, float* __restrict__ YB, float* __restrict__ A1A,
+                             float* __restrict__ A1B, uint32_t* __restrict__ S1) {
+  extern __shared__ __align__(16) float s_mem[];
+  __shared__ TpLevel s_lv[TP_MAX_L];
+  constexpr int KQ0 = 5, HQA = 4, HQB = 2, KB0 = 2, WAVES = THREADS / 64;
+  const uint32_t T = (uint32_t)a.offsets[a.L];
+  float* wa1 = tpm_stage_tables<THREADS>(a, s_mem, s_lv, T);
+  float* wa2 = wa1 + 32 * (KB0 * 32 + 1);
+  float* wb1 = wa2 + 32 * (32 + 1);
+  float* wb2 = wb1 + 32 * (KB0 * 32 + 1);
+  stage_weights<32, KB0, THREADS>(wa1, WA1, d.HA, d.K0);
+  stage_weights<32, 1, THREADS>(wa2, WA2, d.OA, d.HA);
+  stage_weights<32, KB0, THREADS>(wb1, WB1, d.HB, d.K0);
+  stage_weights<32, 1, THREADS>(wb2, WB2, d.OB, d.HB);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
+  const int ntiles = (d.N + 31) / 32;
+  const float inv2b = 1.0f / (2.0f * a.bound);
+  for (int tile = blockIdx.x * WAVES + wave; tile < ntiles; tile += gridDim.x * WAVES) {
+    const size_t row = (size_t)tile * 32 + l31;
+    const bool valid = row < (size_t)d.N;
+    f32x16 in0[KB0];
+    tpm_encode_tile(a, s_lv, s_mem, T, row, valid, h, inv2b, in0);
+#pragma unroll
+    for (int b = 0; b < KB0; ++b) store_block<(int)TPM_K>(enc_x, row, valid, (int)TPM_K, b, h, in0[b]);
+    uint32_t sw = 0;                       // head A's sign bits in the low half, head B's in the high half
+    {
+      f32x16 h1[1], out[1];
+      layer_forward<KQ0, KB0, 1>(wa1, in0, h1, l31, h);
+      relu_blocks<1>(h1);
+      if (A1A) store_blocks<1, 8 * HQA>(A1A, row, valid, d.HA, h, h1);
+      layer_forward<HQA, 1, 1, KEEP>(wa2, h1, out, l31, h, &sw);
+      store_block(YA, row, valid, d.OA, 0, h, out[0]);
+    }
+    {
+      f32x16 h1[1], out[1];
+      layer_forward<KQ0, KB0, 1>(wb1, in0, h1, l31, h);
+      relu_blocks<1>(h1);
+      if (A1B) store_blocks<1, 8 * HQB>(A1B, row, valid, d.HB, h, h1);
+      layer_forward<HQB, 1, 1, KEEP, 16>(wb2, h1, out, l31, h, &sw);
+      store_block(YB, row, valid, d.OB, 0, h, out[0]);
+    }
+    if constexpr (KEEP) S1[(size_t)tile * 64 + lane] = sw;
+  }
+}
+
 // ---- dW[o][k] = sum_rows dZ[row][o] * In[row][k] ---------------------------------------------------
 // A workgroup owns a contiguous range of rows and produces one partial [O][K] matrix.  Round 3: the OB x KB output
 // tiles (32 x 32 each) are DEALT OUT to the four waves instead of every wave holding all of them over a quarter of the
@@ -958,6 +1093,52 @@ int run_bwd(const MlpDims& d, const float* dy, const uint32_t* s1, const uint32_
     }                                                                                              \
   } while (0)
 
+// ---- launches of the encode + MLP kernels ----------------------------------------------------------------------------
+// 4 waves per SIMD.  Measured at 100k rows, kernels alone: 1024 threads 3-4 us faster than 512 for either field (at 512
+// a CU's 8 waves walk two tiles each for 3125 tiles on 256 CUs, at 1024 every wave has one and 196 workgroups suffice)
+constexpr int TPM_THREADS = 1024;
+constexpr size_t TPM_MAX_LDS_BYTES = 150 * 1024;        // what instag_triplane_forward requests as well
+
+// dynamic LDS: the three tables, then the weights of one (align_net's class) or two heads, odd row strides
+inline size_t tpm_lds_bytes(uint32_t total_params, int heads) {
+  const size_t tables = ((size_t)3 * total_params + 3) & ~(size_t)3;
+  const size_t head = 32 * (2 * 32 + 1) + 32 * (32 + 1);
+  return sizeof(float) * (tables + heads * head);
+}
+
+// one workgroup per CU at most; max_blocks > 0 lowers the cap (tests: waves that walk several tiles at small N)
+template <int THREADS>
+inline unsigned tpm_blocks(uint32_t N, uint32_t max_blocks) {
+  const uint32_t ntiles = (N + 31) / 32;
+  uint32_t blocks = std::min<uint32_t>(256u, (ntiles + THREADS / 64 - 1) / (THREADS / 64));
+  if (max_blocks > 0) blocks = std::min(blocks, max_blocks);
+  return std::max(1u, blocks);
+}
+
+template <int THREADS>
+int run_tpm(const TriPlaneArgs& a, const MlpDims& d, uint32_t total_params, const float* w1, const float* w2, float* enc_x,
+            float* y, float* a1, uint32_t* s1, uint32_t max_blocks, hipStream_t s) {
+  auto kernel = s1 ? triplane_mlp_forward_kernel<THREADS, true> : triplane_mlp_forward_kernel<THREADS, false>;
+  if (int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)TPM_MAX_LDS_BYTES)) return rc;
+  ProfScope p(K_MLP_FWD, s);
+  kernel<<<tpm_blocks<THREADS>(a.N, max_blocks), THREADS, tpm_lds_bytes(total_params, 1), s>>>(a, d, w1, w2, enc_x, y, a1, s1);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
+template <int THREADS>
+int run_tpm2(const TriPlaneArgs& a, const Mlp2Dims& d, uint32_t total_params, const float* wa1, const float* wa2,
+             const float* wb1, const float* wb2, float* enc_x, float* ya, float* yb, float* a1a, float* a1b, uint32_t* s1,
+             uint32_t max_blocks, hipStream_t s) {
+  auto kernel = s1 ? triplane_mlp2_forward_kernel<THREADS, true> : triplane_mlp2_forward_kernel<THREADS, false>;
+  if (int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)TPM_MAX_LDS_BYTES)) return rc;
+  ProfScope p(K_MLP_FWD, s);
+  kernel<<<tpm_blocks<THREADS>(a.N, max_blocks), THREADS, tpm_lds_bytes(total_params, 2), s>>>(
+      a, d, wa1, wa2, wb1, wb2, enc_x, ya, yb, a1a, a1b, s1);
+  INSTAG_CHECK_LAUNCH();
+  return INSTAG_OK;
+}
+
 int check_dims(int N, int K0, int H, int O, int NL) {
   INSTAG_REQUIRE(N >= 0, "mlp: N must be >= 0");
   INSTAG_REQUIRE(NL == 2 || NL == 3, "mlp: only 2- or 3-layer MLPs are supported");
@@ -1113,6 +1294,54 @@ int instag_mlp2_backward(const float* dya, const float* dyb, const uint32_t* s1a
       d, dya, dyb, s1a, s1b, wa1, wa2, wb1, wb2, dz1a, dz1b, dx, dx_add);
   INSTAG_CHECK_LAUNCH();
   return INSTAG_OK;
+}
+
+/* Tri-plane encode + the MLPs that read it, one launch per field (see triplane_mlp_forward_kernel).  heads = 1: one
+ * 2-layer MLP 36 -> HA -> OA in the shape class of align_net (HB, OB ignored); heads = 2: the pair instag_mlp2_supported
+ * knows.  The encoder must have 12 levels, and its three tables must fit LDS next to the weights. */
+int instag_triplane_mlp_supported(uint32_t L, uint32_t total_params, int32_t heads, int32_t HA, int32_t OA, int32_t HB,
+                                  int32_t OB) {
+  if (L != TPM_L || total_params == 0 || total_params > TPM_MAX_LDS_BYTES / 12) return 0;
+  if (heads == 1) return tpm_lds_bytes(total_params, 1) <= TPM_MAX_LDS_BYTES && (HA + 7) / 8 == 4 && (OA + 7) / 8 == 1;
+  if (heads == 2)
+    return tpm_lds_bytes(total_params, 2) <= TPM_MAX_LDS_BYTES && instag_mlp2_supported((int32_t)TPM_K, HA, OA, HB, OB);
+  return 0;
+}
+
+int instag_triplane_mlp_forward(const float* xyz, const float* table_xy, const float* table_yz, const float* table_xz,
+                                const int32_t* offsets, const float* shift, uint32_t shift_stride, float shift_scale,
+                                uint32_t N, uint32_t L, float S, uint32_t H, float bound, uint32_t total_params,
+                                const float* w1, const float* w2, float* enc_x, float* y, float* a1, uint32_t* s1,
+                                int32_t HA, int32_t OA, uint32_t max_blocks, instag_stream_t stream) {
+  INSTAG_REQUIRE(instag_triplane_mlp_supported(L, total_params, 1, HA, OA, 0, 0), "triplane_mlp_forward: unsupported shape");
+  INSTAG_REQUIRE(xyz && table_xy && table_yz && table_xz && offsets && w1 && w2 && enc_x && y,
+                 "triplane_mlp_forward: NULL tensor");
+  INSTAG_REQUIRE(shift == nullptr || shift_stride >= 3, "triplane: shift needs at least 3 columns");
+  INSTAG_REQUIRE(N <= 0x7fffffffu / TPM_K, "triplane_mlp_forward: N too large");
+  if (N == 0) return INSTAG_OK;
+  const TriPlaneArgs a{xyz, {table_xy, table_yz, table_xz}, offsets, N, L, H, S, bound, shift, shift_stride, shift_scale};
+  const MlpDims d{(int)N, (int)TPM_K, HA, OA};
+  hipStream_t s = (hipStream_t)stream;
+  return run_tpm<TPM_THREADS>(a, d, total_params, w1, w2, enc_x, y, a1, s1, max_blocks, s);
+}
+
+int instag_triplane_mlp2_forward(const float* xyz, const float* table_xy, const float* table_yz, const float* table_xz,
+                                 const int32_t* offsets, const float* shift, uint32_t shift_stride, float shift_scale,
+                                 uint32_t N, uint32_t L, float S, uint32_t H, float bound, uint32_t total_params,
+                                 const float* wa1, const float* wa2, const float* wb1, const float* wb2, float* enc_x,
+                                 float* ya, float* yb, float* a1a, float* a1b, uint32_t* s1, int32_t HA, int32_t OA,
+                                 int32_t HB, int32_t OB, uint32_t max_blocks, instag_stream_t stream) {
+  INSTAG_REQUIRE(instag_triplane_mlp_supported(L, total_params, 2, HA, OA, HB, OB), "triplane_mlp2_forward: unsupported shape");
+  INSTAG_REQUIRE(xyz && table_xy && table_yz && table_xz && offsets && wa1 && wa2 && wb1 && wb2 && enc_x && ya && yb,
+                 "triplane_mlp2_forward: NULL tensor");
+  INSTAG_REQUIRE((a1a == nullptr) == (a1b == nullptr), "triplane_mlp2_forward: a1a and a1b go together (both NULL: forward only)");
+  INSTAG_REQUIRE(shift == nullptr || shift_stride >= 3, "triplane: shift needs at least 3 columns");
+  INSTAG_REQUIRE(N <= 0x7fffffffu / TPM_K, "triplane_mlp2_forward: N too large");
+  if (N == 0) return INSTAG_OK;
+  const TriPlaneArgs a{xyz, {table_xy, table_yz, table_xz}, offsets, N, L, H, S, bound, shift, shift_stride, shift_scale};
+  const Mlp2Dims d{(int)N, (int)TPM_K, HA, OA, HB, OB};
+  hipStream_t s = (hipStream_t)stream;
+  return run_tpm2<TPM_THREADS>(a, d, total_params, wa1, wa2, wb1, wb2, enc_x, ya, yb, a1a, a1b, s1, max_blocks, s);
 }
 
 size_t instag_linear_weight_grad_workspace_bytes(int32_t N, int32_t O, int32_t K) {

@@ -185,32 +185,40 @@ class _tri_plane_encode(Function):
     @staticmethod
     def backward(ctx, grad, g_xyz=None, g_shift=None):
         saved = ctx.saved_tensors
-        xyz, t0, t1, t2, offsets = saved[:5]
         shift = saved[5] if len(saved) > 5 else None
-        N, L, S, H, bound, T, shift_scale = ctx.meta
-        grad = grad.contiguous().float()
-        L_ = _lib.lib()
-        want_shift = shift is not None and ctx.needs_input_grad[8]
-        dxyz = torch.empty_like(xyz) if (ctx.needs_input_grad[0] or want_shift) else None
-        dshift = torch.empty_like(shift) if want_shift else None
-        g_xyz = g_xyz.contiguous().float() if (g_xyz is not None and dxyz is not None) else None
-        g_shift = g_shift.contiguous().float() if (g_shift is not None and dshift is not None) else None
-        dt = torch.empty(3, T, 1, device=xyz.device, dtype=torch.float32)
-        # A field's encoder backward is the last kernel of that field: the weight gradients its MLPs queued
-        # (instag_amd/deferred.py) start on the side stream BESIDE it -- the flush comes first, so that the side stream
-        # waits for the MLPs' backward only, not for this kernel.
-        from . import deferred
-        if FLUSH_BEFORE_ENCODER_BACKWARD or shift is None:
-            deferred.flush_async(xyz.device)
-        ws_bytes = L_.instag_triplane_backward_workspace_bytes(N, T)
-        ws = torch.empty(max(1, ws_bytes // 4), device=xyz.device, dtype=torch.float32)
-        check(L_.instag_triplane_backward(ptr(grad), ptr(xyz), ptr(t0), ptr(t1), ptr(t2), ptr(offsets),
-                                          ptr(dxyz), ptr(dt[0]), ptr(dt[1]), ptr(dt[2]), ptr(ws), ws_bytes,
-                                          ptr(shift), 0 if shift is None else shift.shape[1], shift_scale, ptr(dshift),
-                                          N, L, S, H, bound, T, ptr(g_xyz), ptr(g_shift), _lib.current_stream()),
-              "triplane_backward")
-        return ((dxyz if ctx.needs_input_grad[0] else None), dt[0], dt[1], dt[2], None, None, None, None, dshift, None,
-                None)
+        dxyz, dt, dshift = tri_plane_backward(saved[:5], shift, ctx.meta, grad, g_xyz, g_shift, ctx.needs_input_grad[0],
+                                              shift is not None and ctx.needs_input_grad[8])
+        return (dxyz, dt[0], dt[1], dt[2], None, None, None, None, dshift, None, None)
+
+
+def tri_plane_backward(saved, shift, meta, grad, g_xyz, g_shift, want_xyz, want_shift):
+    """The encoder's backward launch for the tensors and ``meta`` its forward saved -> (dxyz or None, dtables [3,T,1],
+    dshift or None).  g_xyz / g_shift: the gradients of the position's / the shift's other consumers (passthrough), summed
+    in by the kernel.  Shared by _tri_plane_encode and the nodes that run the encode inside an MLP's forward kernel
+    (instag_amd/encode_mlp.py)."""
+    xyz, t0, t1, t2, offsets = saved
+    N, L, S, H, bound, T, shift_scale = meta
+    grad = grad.contiguous().float()
+    L_ = _lib.lib()
+    dxyz = torch.empty_like(xyz) if (want_xyz or want_shift) else None
+    dshift = torch.empty_like(shift) if want_shift else None
+    g_xyz = g_xyz.contiguous().float() if (g_xyz is not None and dxyz is not None) else None
+    g_shift = g_shift.contiguous().float() if (g_shift is not None and dshift is not None) else None
+    dt = torch.empty(3, T, 1, device=xyz.device, dtype=torch.float32)
+    # A field's encoder backward is the last kernel of that field: the weight gradients its MLPs queued
+    # (instag_amd/deferred.py) start on the side stream BESIDE it -- the flush comes first, so that the side stream
+    # waits for the MLPs' backward only, not for this kernel.
+    from . import deferred
+    if FLUSH_BEFORE_ENCODER_BACKWARD or shift is None:
+        deferred.flush_async(xyz.device)
+    ws_bytes = L_.instag_triplane_backward_workspace_bytes(N, T)
+    ws = torch.empty(max(1, ws_bytes // 4), device=xyz.device, dtype=torch.float32)
+    check(L_.instag_triplane_backward(ptr(grad), ptr(xyz), ptr(t0), ptr(t1), ptr(t2), ptr(offsets),
+                                      ptr(dxyz), ptr(dt[0]), ptr(dt[1]), ptr(dt[2]), ptr(ws), ws_bytes,
+                                      ptr(shift), 0 if shift is None else shift.shape[1], shift_scale, ptr(dshift),
+                                      N, L, S, H, bound, T, ptr(g_xyz), ptr(g_shift), _lib.current_stream()),
+          "triplane_backward")
+    return (dxyz if want_xyz else None), dt, dshift
 
 
 def tri_plane_supported(enc_xy, enc_yz, enc_xz) -> bool:

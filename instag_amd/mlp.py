@@ -123,21 +123,27 @@ class _FusedMLP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
-        x, w1, w2, w3, a1, a2, s1, s2 = ctx.saved_tensors
-        (N, K0), H = x.shape, w1.shape[0]
-        NL = 2 if w3 is None else 3
-        O = dy.shape[1]
-        dy = dy.contiguous().float()
-        dev = dy.device
-        dz1 = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dz2 = torch.empty(N, H, dtype=torch.float32, device=dev) if NL == 3 else None
-        dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        check(L.instag_mlp_backward(ptr(dy), ptr(s1), ptr(s2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2), ptr(dx),
-                                    N, K0, H, O, NL, _lib.current_stream()), "mlp_backward")
-        STATS["bwd_flops"] += 2 * N * (H * O + (H * H if NL == 3 else 0) + (K0 * H if dx is not None else 0))
-        jobs = [(dz1, x, None)] + ([(dz2, a1, None), (dy, a2, None)] if NL == 3 else [(dy, a1, None), None])
-        return (dx, *emit_weight_grads(jobs, ctx.weights, ctx.needs_input_grad[1:]))
+        return mlp_backward(ctx.saved_tensors, dy, ctx.needs_input_grad[0], ctx.weights, ctx.needs_input_grad[1:])
+
+
+def mlp_backward(saved, dy, want_dx, weights, wanted):
+    """Backward launch of one MLP for what its forward saved -> (dx or None, dw1, dw2, dw3); see emit_weight_grads for
+    ``weights`` and ``wanted``.  Shared by _FusedMLP and instag_amd/encode_mlp.py."""
+    L = _lib.lib()
+    x, w1, w2, w3, a1, a2, s1, s2 = saved
+    (N, K0), H = x.shape, w1.shape[0]
+    NL = 2 if w3 is None else 3
+    O = dy.shape[1]
+    dy = dy.contiguous().float()
+    dev = dy.device
+    dz1 = torch.empty(N, H, dtype=torch.float32, device=dev)
+    dz2 = torch.empty(N, H, dtype=torch.float32, device=dev) if NL == 3 else None
+    dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if want_dx else None
+    check(L.instag_mlp_backward(ptr(dy), ptr(s1), ptr(s2), ptr(w1), ptr(w2), ptr(w3), ptr(dz1), ptr(dz2), ptr(dx),
+                                N, K0, H, O, NL, _lib.current_stream()), "mlp_backward")
+    STATS["bwd_flops"] += 2 * N * (H * O + (H * H if NL == 3 else 0) + (K0 * H if dx is not None else 0))
+    jobs = [(dz1, x, None)] + ([(dz2, a1, None), (dy, a2, None)] if NL == 3 else [(dy, a1, None), None])
+    return (dx, *emit_weight_grads(jobs, weights, wanted))
 
 
 class _SharedInputMLPs(torch.autograd.Function):
@@ -177,30 +183,37 @@ class _SharedInputMLPs(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dya, dyb, dx_other):
         # (all three are tensors: autograd hands in zeros for an output that nothing read)
-        L = _lib.lib()
-        x, wa1, wa2, a1a, s1a, wb1, wb2, a1b, s1b = ctx.saved_tensors
-        N, K0 = x.shape
-        (HA, OA), (HB, OB) = (wa1.shape[0], wa2.shape[0]), (wb1.shape[0], wb2.shape[0])
-        dev = x.device
-        stream = _lib.current_stream()
-        want_dx = ctx.needs_input_grad[0]
-        dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if want_dx else None
-        add = dx_other.contiguous().float() if want_dx else None
-        dya, dyb = dya.contiguous().float(), dyb.contiguous().float()
-        dz1a = torch.empty(N, HA, dtype=torch.float32, device=dev)
-        dz1b = torch.empty(N, HB, dtype=torch.float32, device=dev)
-        if ctx.fused:
-            check(L.instag_mlp2_backward(ptr(dya), ptr(dyb), ptr(s1a), ptr(s1b), ptr(wa1), ptr(wa2), ptr(wb1),
-                                         ptr(wb2), ptr(dz1a), ptr(dz1b), ptr(dx), ptr(add), N, K0, HA, OA, HB, OB,
-                                         stream), "mlp2_backward")
-        else:
-            for dy, s1, w1, w2, dz1 in ((dya, s1a, wa1, wa2, dz1a), (dyb, s1b, wb1, wb2, dz1b)):
-                check(L.instag_mlp_backward_add(ptr(dy), ptr(s1), None, ptr(w1), ptr(w2), None, ptr(dz1), None, ptr(dx),
-                                                ptr(add), N, K0, w1.shape[0], w2.shape[0], 2, stream), "mlp_backward")
-                add = dx                          # the second kernel adds onto what the first wrote
-        STATS["bwd_flops"] += 2 * N * (HA * OA + HB * OB + (K0 * (HA + HB) if want_dx else 0))
-        jobs = [(dz1a, x, None), (dya, a1a, None), (dz1b, x, None), (dyb, a1b, None)]
-        return (dx, *emit_weight_grads(jobs, ctx.weights, ctx.needs_input_grad[1:]))
+        return shared_input_backward(ctx.saved_tensors, ctx.fused, dya, dyb, dx_other, ctx.needs_input_grad[0],
+                                     ctx.weights, ctx.needs_input_grad[1:])
+
+
+def shared_input_backward(saved, fused, dya, dyb, dx_other, want_dx, weights, wanted):
+    """Backward launch(es) of two MLPs over one input for what their forward saved -> (dx or None, four weight gradients);
+    dx includes ``dx_other``, the gradient of the input's other consumers.  Shared by _SharedInputMLPs and
+    instag_amd/encode_mlp.py."""
+    L = _lib.lib()
+    x, wa1, wa2, a1a, s1a, wb1, wb2, a1b, s1b = saved
+    N, K0 = x.shape
+    (HA, OA), (HB, OB) = (wa1.shape[0], wa2.shape[0]), (wb1.shape[0], wb2.shape[0])
+    dev = x.device
+    stream = _lib.current_stream()
+    dx = torch.empty(N, K0, dtype=torch.float32, device=dev) if want_dx else None
+    add = dx_other.contiguous().float() if want_dx else None
+    dya, dyb = dya.contiguous().float(), dyb.contiguous().float()
+    dz1a = torch.empty(N, HA, dtype=torch.float32, device=dev)
+    dz1b = torch.empty(N, HB, dtype=torch.float32, device=dev)
+    if fused:
+        check(L.instag_mlp2_backward(ptr(dya), ptr(dyb), ptr(s1a), ptr(s1b), ptr(wa1), ptr(wa2), ptr(wb1),
+                                     ptr(wb2), ptr(dz1a), ptr(dz1b), ptr(dx), ptr(add), N, K0, HA, OA, HB, OB,
+                                     stream), "mlp2_backward")
+    else:
+        for dy, s1, w1, w2, dz1 in ((dya, s1a, wa1, wa2, dz1a), (dyb, s1b, wb1, wb2, dz1b)):
+            check(L.instag_mlp_backward_add(ptr(dy), ptr(s1), None, ptr(w1), ptr(w2), None, ptr(dz1), None, ptr(dx),
+                                            ptr(add), N, K0, w1.shape[0], w2.shape[0], 2, stream), "mlp_backward")
+            add = dx                          # the second kernel adds onto what the first wrote
+    STATS["bwd_flops"] += 2 * N * (HA * OA + HB * OB + (K0 * (HA + HB) if want_dx else 0))
+    jobs = [(dz1a, x, None), (dya, a1a, None), (dz1b, x, None), (dyb, a1b, None)]
+    return (dx, *emit_weight_grads(jobs, weights, wanted))
 
 
 def shared_input_mlps(x, weights_a, weights_b):

@@ -227,10 +227,16 @@ class _TriPlaneField(nn.Module):
         from . import _lib
         fork = x.is_cuda and CONCURRENT_AUDIO and _lib.may_fork(x.device)
         pending = self.__dict__.pop("_audio_pending", None)
+        aud_ch_att = eye_pre = None
+        if enc_x is None and self.exp_eye:
+            from . import encode_mlp as _em
+            if _em.supported(self, x, [self.aud_ch_att_net, self.eye_att_net]):
+                # encode + both attention heads in one forward launch (instag_amd/encode_mlp.py)
+                aud_ch_att, eye_pre, enc_x = _em.encode_heads(self, x, self.bound, x_shift, self.aud_ch_att_net,
+                                                              self.eye_att_net)
         if enc_x is None:
             enc_x = self.encode_x(x, bound=self.bound, shift=x_shift)
-        aud_ch_att = eye_pre = None
-        if self.exp_eye and enc_x.is_cuda and enc_x.dim() == 2:
+        if aud_ch_att is None and self.exp_eye and enc_x.is_cuda and enc_x.dim() == 2:
             from . import mlp as _mlp
             na, ne = self.aud_ch_att_net, self.eye_att_net
             if na.num_layers == 2 and ne.num_layers == 2 and \
@@ -347,8 +353,13 @@ class PersonalizedMotionNetwork(_TriPlaneField):
         so a caller that renders with ``personalized=False`` (train_face.py warm stage) does not pay for outputs
         it never reads -- the values, when read, are the same."""
         face = self.args.type == "face"
-        enc_x = self.encode_x(x, bound=self.bound)
-        p = self.align_net(enc_x)
+        from . import encode_mlp as _em
+        if _em.supported(self, x, [self.align_net]):
+            # encode + alignment head in one forward launch (instag_amd/encode_mlp.py)
+            p, enc_x = _em.encode_align(self, x, self.bound, self.align_net)
+        else:
+            enc_x = self.encode_x(x, bound=self.bound)
+            p = self.align_net(enc_x)
         memo = {}
 
         def head():
