@@ -68,6 +68,12 @@ globals().update((cls.__name__, cls) for cls in _FACE_DETECT_STRUCTS.values())
 # (instag_amd/encode_mlp.py): the three instag_triplane_mlp* entry points, no struct and no constant.
 _, _ENCODE_MLP_PROTOTYPES, _ = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_encode_mlp.h"))
 
+# The Sapiens normal / depth network's part, include/instag_sapiens.h (instag_amd/sapiens.py): struct SapiensWeights as
+# the C side sees it (_lib.SapiensStruct; the name SapiensWeights is the Python class of sapiens.py), the
+# instag_sapiens_* entry points and the INSTAG_SAPIENS_* bounds.
+_SAPIENS_STRUCTS, _SAPIENS_PROTOTYPES, SAPIENS = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_sapiens.h"))
+SapiensStruct = _SAPIENS_STRUCTS["instag_sapiens_weights"]
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -236,7 +242,7 @@ def lib():
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
                                   **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES,
                                   **_LANDMARKS_PROTOTYPES, **_FACE_DETECT_PROTOTYPES,
-                                  **_ENCODE_MLP_PROTOTYPES}.items():
+                                  **_ENCODE_MLP_PROTOTYPES, **_SAPIENS_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

@@ -61,6 +61,7 @@ SOURCES = {
     "mesh_render.hip": [],
     "wav2vec.hip": [],
     "hubert.hip": [],
+    "sapiens.hip": [],
     "deepspeech.hip": [],
     # landmarks: the crop's and the decode's fp64 transform is the torch statement's operation by operation, and its
     # result is truncated to an integer; the convolution's FMAs are written out and stay

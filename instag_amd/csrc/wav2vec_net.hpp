@@ -7,11 +7,12 @@
 // projection and the two feed-forward products with bias, GELU and the residual in their epilogues and the feature
 // projection.  Around it: layer 0 (one input channel: VALU) fused with its LayerNorm and GELU, a one-wave-per-row
 // LayerNorm (+GELU) and the padded copy.  The attention is the entry's own and comes to run_network as a parameter.
+// The LayerNorm, the plain product and the loop over the transformer's layers are transformer.hpp's, which the Sapiens
+// backbone (sapiens.hip) shares.
 //
 // No atomics; every reduction has a fixed order and no kernel's arithmetic depends on the batch size.
 #pragma once
-#include "gemm_mfma.hpp"
-#include "device_math.hpp"
+#include "transformer.hpp"
 #include "instag_wav2vec.h"
 
 namespace instag {
@@ -20,8 +21,6 @@ namespace {
 constexpr int N_CONV = 7;
 constexpr int CONV_K[N_CONV] = {10, 3, 3, 3, 3, 2, 2};
 constexpr int CONV_S[N_CONV] = {5, 2, 2, 2, 2, 2, 2};
-constexpr int HEAD_DIM = 64;
-constexpr int MAX_ROW = 1024;                          // a LayerNorm row: 16 values per lane of one wave
 constexpr int MAX_SAMPLES = 1 << 20;
 constexpr float LN_EPS = 1e-5f, NORM_EPS = 1e-7f;
 
@@ -72,37 +71,6 @@ __global__ void __launch_bounds__(TB) conv0_kernel(const float* __restrict__ x, 
     for (int q = 0; q < 4; ++q) {
       const int c = threadIdx.x + TB * q;
       if (c < C) row[c] = gelu_erf((y[q] - mu) * rs * ga[q] + be[q]);
-    }
-  }
-}
-
-// ---- LayerNorm over a row of C <= 1024 (+ GELU), one wave per row; out may be in ----------------------------------------
-__global__ void __launch_bounds__(TB) layernorm_kernel(const float* in, float* out, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, int rows, int C, int gelu) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const float* src = in + (size_t)r * C;
-  float v[MAX_ROW / 64], s = 0.f;
-#pragma unroll
-  for (int i = 0; i < MAX_ROW / 64; ++i) {
-    const int c = lane + 64 * i;
-    v[i] = c < C ? src[c] : 0.f;
-    s += v[i];
-  }
-  const float mu = wave_sum(s) / (float)C;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < MAX_ROW / 64; ++i)
-    if (lane + 64 * i < C) q += (v[i] - mu) * (v[i] - mu);
-  const float rs = 1.f / sqrtf(wave_sum(q) / (float)C + LN_EPS);
-  float* dst = out + (size_t)r * C;
-#pragma unroll
-  for (int i = 0; i < MAX_ROW / 64; ++i) {
-    const int c = lane + 64 * i;
-    if (c < C) {
-      const float y = (v[i] - mu) * rs * gamma[c] + beta[c];
-      dst[c] = gelu ? gelu_erf(y) : y;
     }
   }
 }
@@ -233,21 +201,6 @@ int forward_prologue(const Net& net, const instag_wav2vec_weights* w, const void
   return INSTAG_OK;
 }
 
-int layernorm(const float* in, float* out, const float* g, const float* b, size_t rows, int C, int gelu, hipStream_t st) {
-  layernorm_kernel<<<(unsigned)div_up(rows, (size_t)(TB / 64)), TB, 0, st>>>(in, out, g, b, (int)rows, C, gelu);
-  INSTAG_CHECK_LAUNCH();
-  return INSTAG_OK;
-}
-
-// D [M, N] = epilogue(A [M, K] W + bias): the ordinary case, one batch of contiguous rows
-int linear(const float* a, const float* w, const float* bias, const float* res, float* d, int M, int K, int N, int gelu,
-           int tile, hipStream_t st) {
-  GemmArgs g{};
-  g.a = a; g.w = w; g.bias = bias; g.res = res; g.d = d;
-  g.M = M; g.rows = M; g.N = N; g.K = K; g.groups = 1; g.lda = K; g.ldd = N; g.gelu = gelu;
-  return launch_gemm(g, st, tile);
-}
-
 // The network behind the samples' normalisation: feature extractor, projection, positional convolution, the layers and
 // the encoder's last LayerNorm, which writes `out` [B, T, hidden] (a piece of the workspace, or the caller's tensor).
 // stats: the per-segment statistics layer 0 applies, or NULL.  attention(qkv, ctx, B, T, H, st) -> code runs
@@ -255,7 +208,7 @@ int linear(const float* a, const float* w, const float* bias, const float* res, 
 template <typename Attention>
 int run_network(const instag_wav2vec_weights* w, const Plan& p, const float* segments, const float* stats, int B,
                 float* ws, int tile, float* taps, float* out, hipStream_t st, Attention&& attention) {
-  const int n = p.t[0], C = w->conv_dim, H = w->hidden, I = w->intermediate, G = w->pos_groups;
+  const int n = p.t[0], C = w->conv_dim, H = w->hidden, G = w->pos_groups;
   const int T = p.t[N_CONV], M = B * T, Cg = H / G;
   float* buf[2] = {ws + p.buf_a, ws + p.buf_b};
   float *h = ws + p.h, *x = ws + p.x, *qkv = ws + p.qkv, *ctx = ws + p.ctx, *ff = ws + p.ff, *pad = ws + p.pad;
@@ -283,11 +236,11 @@ int run_network(const instag_wav2vec_weights* w, const Plan& p, const float* seg
     g.a_batch = (int64_t)p.t[l] * C; g.lda = CONV_S[l] * C; g.d_batch = (int64_t)p.t[l + 1] * C; g.ldd = C;
     INSTAG_TRY(launch_gemm(g, st, tile));
     cur ^= 1;
-    INSTAG_TRY(layernorm(buf[cur], buf[cur], w->conv_ln_g[l], w->conv_ln_b[l], (size_t)g.M, C, 1, st));
+    INSTAG_TRY(layernorm(buf[cur], buf[cur], w->conv_ln_g[l], w->conv_ln_b[l], (size_t)g.M, C, 1, LN_EPS, st));
     INSTAG_TRY(tap(buf[cur], (size_t)g.M * C));
   }
   // feature projection
-  INSTAG_TRY(layernorm(buf[cur], buf[cur], w->proj_ln_g, w->proj_ln_b, M, C, 0, st));
+  INSTAG_TRY(layernorm(buf[cur], buf[cur], w->proj_ln_g, w->proj_ln_b, M, C, 0, LN_EPS, st));
   INSTAG_TRY(linear(buf[cur], w->proj_w, w->proj_b, nullptr, h, M, C, H, 0, tile, st));
   INSTAG_TRY(tap(h, (size_t)M * H));
   // positional convolution: h += GELU(conv(h))
@@ -304,18 +257,8 @@ int run_network(const instag_wav2vec_weights* w, const Plan& p, const float* seg
     INSTAG_TRY(tap(h, (size_t)M * H));
   }
   // transformer
-  for (int l = 0; l < w->layers; ++l) {
-    INSTAG_TRY(layernorm(h, x, w->ln1_g[l], w->ln1_b[l], M, H, 0, st));
-    INSTAG_TRY(linear(x, w->qkv_w[l], w->qkv_b[l], nullptr, qkv, M, H, 3 * H, 0, tile, st));
-    INSTAG_TRY(attention(qkv, ctx, B, T, H, st));
-    INSTAG_TRY(linear(ctx, w->out_w[l], w->out_b[l], h, h, M, H, H, 0, tile, st));
-    INSTAG_TRY(tap(h, (size_t)M * H));
-    INSTAG_TRY(layernorm(h, x, w->ln2_g[l], w->ln2_b[l], M, H, 0, st));
-    INSTAG_TRY(linear(x, w->ff1_w[l], w->ff1_b[l], nullptr, ff, M, H, I, 1, tile, st));
-    INSTAG_TRY(linear(ff, w->ff2_w[l], w->ff2_b[l], h, h, M, I, H, 0, tile, st));
-    INSTAG_TRY(tap(h, (size_t)M * H));
-  }
-  return layernorm(h, out, w->enc_ln_g, w->enc_ln_b, M, H, 0, st);
+  INSTAG_TRY(run_layers(w, B, T, LayerBuffers{h, x, qkv, ctx, ff}, LN_EPS, tile, tap, st, attention));
+  return layernorm(h, out, w->enc_ln_g, w->enc_ln_b, M, H, 0, LN_EPS, st);
 }
 
 }  // namespace

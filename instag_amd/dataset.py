@@ -172,11 +172,27 @@ def _latest(path, kind):
     return c[0]
 
 
+def _select_priors(priors, img_ids):
+    """The rows of ``priors`` (read_identity) for the frames ``img_ids``, in their order -> (normal, depth) tensors."""
+    if priors.get("normal") is None or priors.get("depth") is None:
+        raise ValueError("priors: normal and depth come together (run both networks)")
+    where = {int(i): k for k, i in enumerate(np.asarray(priors["ids"]).reshape(-1).tolist())}
+    for i in img_ids:
+        if int(i) not in where:
+            raise KeyError(f"priors: no geometry prior for train frame {int(i)} (ids cover {len(where)} frames)")
+    normal, depth = torch.as_tensor(priors["normal"]), torch.as_tensor(priors["depth"])
+    rows = torch.tensor([where[int(i)] for i in img_ids], dtype=torch.int64, device=normal.device)
+    return normal.index_select(0, rows), depth.index_select(0, rows.to(depth.device))
+
+
 def read_identity(path, split, audio_extractor="deepspeech", audio_file="", n_views=-1, extension=".jpg",
-                  preload_priors: Optional[bool] = None, audio_features=None) -> dict:
+                  preload_priors: Optional[bool] = None, audio_features=None, priors=None) -> dict:
     """-> dict: the raw uint8 arrays (gt, torso, bc, parsing, teeth), cameras (scene_synth.Camera), au_exp, lips_rect,
     lhalf_rect, audio_index, audio [T,C,L], normal / depth (train split with n_views > 0, unless preload_priors is
-    False) and ``meta``: img_id, blink, au25 [F,5], mouth_bound [F,3], R, T, FovX, FovY."""
+    False) and ``meta``: img_id, blink, au25 [F,5], mouth_bound [F,3], R, T, FovX, FovY.
+    ``priors``: a dict {"ids", "normal" [N,3,H,W], "depth" [N,H,W]} as ``sapiens.geometry_identity`` returns it, used in
+    place of the sapiens/ files (the maps stay tensors on their device); a train frame whose id is not among ``ids``
+    raises KeyError naming it."""
     with open(os.path.join(path, f"transforms_{split}.json")) as f:
         contents = json.load(f)
     audio = audio_table(path, audio_extractor, audio_file, audio_features)
@@ -190,9 +206,12 @@ def read_identity(path, split, audio_extractor="deepspeech", audio_file="", n_vi
     out.update(au_exp=table["au_exp"], lips_rect=table["lips_rect"], lhalf_rect=table["lhalf_rect"],
                audio_index=table["audio_index"], audio=audio)
     if split == "train" and table["n_views"] > 0 and preload_priors is not False:      # :286-314
-        nd, dd = _latest(path, "normal"), _latest(path, "depth")
-        out["normal"] = np.stack([np.load(os.path.join(nd, f"{i}.npy")).transpose(2, 0, 1) for i in table["img_id"]])
-        out["depth"] = np.stack([np.load(os.path.join(dd, f"{i}.npy")) for i in table["img_id"]])
+        if priors is not None:
+            out["normal"], out["depth"] = _select_priors(priors, table["img_id"])
+        else:
+            nd, dd = _latest(path, "normal"), _latest(path, "depth")
+            out["normal"] = np.stack([np.load(os.path.join(nd, f"{i}.npy")).transpose(2, 0, 1) for i in table["img_id"]])
+            out["depth"] = np.stack([np.load(os.path.join(dd, f"{i}.npy")) for i in table["img_id"]])
     out["meta"] = dict(img_id=table["img_id"], blink=table["blink"], au25=table["au25"],
                        mouth_bound=table["mouth_bound"], R=table["R"], T=table["T"],
                        FovX=2 * math.atan(w / (2 * focal)), FovY=2 * math.atan(h / (2 * focal)))
