@@ -74,6 +74,10 @@ _, _ENCODE_MLP_PROTOTYPES, _ = _cabi.read(os.path.join(os.path.dirname(_cabi.HEA
 _SAPIENS_STRUCTS, _SAPIENS_PROTOTYPES, SAPIENS = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_sapiens.h"))
 SapiensStruct = _SAPIENS_STRUCTS["instag_sapiens_weights"]
 
+# The JPEG encoder's part, include/instag_mjpeg.h (instag_amd/mjpeg.py): the three instag_mjpeg_* entry points and the
+# INSTAG_MJPEG_* bounds, no struct.
+_, _MJPEG_PROTOTYPES, MJPEG = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_mjpeg.h"))
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -242,7 +246,7 @@ def lib():
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
                                   **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES,
                                   **_LANDMARKS_PROTOTYPES, **_FACE_DETECT_PROTOTYPES,
-                                  **_ENCODE_MLP_PROTOTYPES, **_SAPIENS_PROTOTYPES}.items():
+                                  **_ENCODE_MLP_PROTOTYPES, **_SAPIENS_PROTOTYPES, **_MJPEG_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

@@ -68,6 +68,7 @@ SOURCES = {
     "landmarks.hip": ["-ffp-contract=off"],
     # face_detect: the tail's fp64 box decode and overlap are the torch statement's operations one by one
     "face_detect.hip": ["-ffp-contract=off"],
+    "mjpeg.hip": [],
 }
 
 
