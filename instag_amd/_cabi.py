@@ -14,7 +14,8 @@ import re
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "instag_hip.h")
 
 _SCALARS = {"int": C.c_int32, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "size_t": C.c_size_t,
-            "float": C.c_float, "double": C.c_double, "uint8_t": C.c_uint8, "uint64_t": C.c_uint64, "int16_t": C.c_int16}
+            "float": C.c_float, "double": C.c_double, "uint8_t": C.c_uint8, "uint64_t": C.c_uint64, "int16_t": C.c_int16,
+            "uint16_t": C.c_uint16}
 _SPACE = re.compile(r"\s*")
 _STRUCT = re.compile(r"typedef\s+struct\s*(\w*)\s*\{([^{}]*)\}\s*(\w+)\s*;")
 _FUNCTION = re.compile(r"([\w\s*]+?)\b(\w+)\s*\(([^()]*)\)")

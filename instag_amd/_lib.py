@@ -78,6 +78,10 @@ SapiensStruct = _SAPIENS_STRUCTS["instag_sapiens_weights"]
 # INSTAG_MJPEG_* bounds, no struct.
 _, _MJPEG_PROTOTYPES, MJPEG = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_mjpeg.h"))
 
+# The JPEG decoder's part, include/instag_jpeg_decode.h (instag_amd/jpeg_decode.py): the four instag_jpeg_decode* entry
+# points, the INSTAG_JPEG_DECODE_* bounds and status codes, no struct.
+_, _JPEG_DECODE_PROTOTYPES, JPEG_DECODE = _cabi.read(os.path.join(os.path.dirname(_cabi.HEADER), "instag_jpeg_decode.h"))
+
 
 # ---- streams -------------------------------------------------------------------------------------------------------
 # torch.cuda.Stream() does not create a HIP stream: it hands out the next of 32 pooled streams per (device, priority),
@@ -246,7 +250,8 @@ def lib():
         for name, (res, args) in {**_PROTOTYPES, **_WAV2VEC_PROTOTYPES, **_HUBERT_PROTOTYPES,
                                   **_FRAME_CODE_WIDE_PROTOTYPES, **_DEEPSPEECH_PROTOTYPES,
                                   **_LANDMARKS_PROTOTYPES, **_FACE_DETECT_PROTOTYPES,
-                                  **_ENCODE_MLP_PROTOTYPES, **_SAPIENS_PROTOTYPES, **_MJPEG_PROTOTYPES}.items():
+                                  **_ENCODE_MLP_PROTOTYPES, **_SAPIENS_PROTOTYPES, **_MJPEG_PROTOTYPES,
+                                  **_JPEG_DECODE_PROTOTYPES}.items():
             if not hasattr(handle, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it (python -m instag_amd.build)")
             fn = getattr(handle, name)

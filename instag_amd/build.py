@@ -69,6 +69,7 @@ SOURCES = {
     # face_detect: the tail's fp64 box decode and overlap are the torch statement's operations one by one
     "face_detect.hip": ["-ffp-contract=off"],
     "mjpeg.hip": [],
+    "jpeg_decode.hip": [],
 }
 
 

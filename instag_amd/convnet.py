@@ -245,14 +245,43 @@ class FrameOperator(DeviceOperator):
 
 
 # ---- a directory --------------------------------------------------------------------------------------------------------
-def frame_batches(path, batch: int, resize=None):
+def _decoded_on_device(paths, size, resize, decoder):
+    """The files of one batch through ``decoder`` (a ``jpeg_decode.JpegDecoder``) -> (frames on its device, (width,
+    height)), or None where the batch is PIL's: a file the decoder's parser refuses, files of different sizes or not of
+    ``size``, or a size that ``resize`` changes."""
+    from .jpeg_decode import UnsupportedJpeg, parse_jpeg
+    files = []
+    for p in paths:
+        with open(p, "rb") as f:
+            files.append(f.read())
+    try:
+        infos = [parse_jpeg(f) for f in files]
+    except UnsupportedJpeg:
+        return None
+    sizes = {(i.W, i.H) for i in infos} | ({size} if size is not None else set())
+    if len(sizes) != 1 or len({i.subsampling for i in infos}) != 1 or (resize and sizes != {(resize, resize)}):
+        return None
+    return decoder.decode_checked(files, infos), sizes.pop()
+
+
+def frame_batches(path, batch: int, resize=None, decoder=None):
     """ori_imgs/<i>.jpg of ``path`` in ascending numeric order, ``batch`` at a time -> (ids, u8 frames [b,H,W,3], the
     files' (width, height)).  Every file has the first one's size; ``resize``: frames of another size are resized to
-    (resize, resize) on the host (PIL, bilinear)."""
+    (resize, resize) on the host (PIL, bilinear).  ``decoder``: a ``jpeg_decode.JpegDecoder``; a batch is then decoded
+    on its device from the files' bytes and comes back there, with the same bytes as PIL's; a batch with a file its
+    parser refuses (progressive, grayscale, restart markers, ...), with files of mixed sizes or one that ``resize``
+    changes is PIL's as before."""
     from PIL import Image
     from .prepare import list_frames
     ids, size = list_frames(path), None
     for s in range(0, len(ids), batch):
+        if decoder is not None:
+            got = _decoded_on_device([os.path.join(path, "ori_imgs", f"{i}.jpg") for i in ids[s:s + batch]], size, resize,
+                                     decoder)
+            if got is not None:
+                size = got[1]
+                yield ids[s:s + batch], got[0], size
+                continue
         frames = []
         for i in ids[s:s + batch]:
             img = Image.open(os.path.join(path, "ori_imgs", f"{i}.jpg"))

@@ -17,6 +17,7 @@
 //   scatter    every byte to header + index + 0xFF bytes in front of it, a 0x00 behind each 0xFF; nothing at or past
 //              `capacity`
 #include "common.hpp"
+#include "block_scan.hpp"
 #include "instag_mjpeg.h"
 
 namespace instag {
@@ -242,15 +243,6 @@ __device__ __forceinline__ void lane_symbol(const int16_t* __restrict__ fc, int 
   }
 }
 
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
 // bit length of every block: offset[b][blk]
 __global__ __launch_bounds__(256) void mjpeg_bits(const int16_t* __restrict__ coef, int nblk, int sub,
                                                   uint32_t* __restrict__ offset) {
@@ -261,24 +253,6 @@ __global__ __launch_bounds__(256) void mjpeg_bits(const int16_t* __restrict__ co
   lane_symbol(coef + (size_t)b * nblk * 64, blk, sub, lane, val, n);
   const int sum = wave_inclusive_sum(n, lane);
   if (lane == 63) offset[(size_t)b * nblk + blk] = (uint32_t)sum;
-}
-
-// exclusive scan of `n` values of one workgroup's thread each, plus `carry`; -> the sum of all
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_wave, uint32_t& exclusive) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t inc = (uint32_t)wave_inclusive_sum((int)v, lane);
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (int w = 0; w < THREADS / 64; ++w) {
-    const uint32_t t = s_wave[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  __syncthreads();
-  exclusive = before + inc - v;
-  return all;
 }
 
 // lengths -> exclusive bit offsets, in place; total[b] = {bits, bytes before stuffing, -, -}; zero the words in use

@@ -504,9 +504,10 @@ def l2norm_device(x, weight):
 
 
 # ---- a directory --------------------------------------------------------------------------------------------------------
-def detect_identity(path, weights: S3FDWeights, device="cuda", batch: int = 7):
+def detect_identity(path, weights: S3FDWeights, device="cuda", batch: int = 7, decoder=None):
     """ori_imgs/<i>.jpg of ``path`` in ascending numeric order -> float32 [N,4] on ``device``: each frame's first box, a
-    NaN row where a frame has no detection."""
+    NaN row where a frame has no detection.  ``decoder``: a ``jpeg_decode.JpegDecoder`` that decodes the files on the device
+    (``convnet.frame_batches``)."""
     det = FaceDetector(weights, torch.device(device), max_batch=batch)
-    out = [det.first(frames) for _, frames, _ in convnet.frame_batches(path, batch)]
+    out = [det.first(frames) for _, frames, _ in convnet.frame_batches(path, batch, decoder=decoder)]
     return torch.cat(out, dim=0) if out else torch.zeros(0, 4, device=det.device)

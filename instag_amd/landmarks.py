@@ -531,12 +531,13 @@ def write_landmarks(path, lms):
 
 
 def landmarks_identity(path, weights: FANWeights, device="cuda", boxes=None, write: bool = True, batch: int = 32,
-                       detector=None):
+                       detector=None, decoder=None):
     """ori_imgs/<i>.jpg of ``path`` (ascending numeric order) and ``boxes`` [N,4] (or [4]) in that order -> landmarks
     float32 [N,68,2] on ``device``.  Without boxes, ``detector`` (a ``face_detect.FaceDetector``) finds them: each
     batch's boxes are ``detector.first(frames)``, the face process.py takes.  ``write``: also ori_imgs/<i>.lms, what
     ``track.read_landmarks`` reads; a frame whose box row has a NaN gets no file (and a NaN row), as a frame without a
-    detection gets none in the reference."""
+    detection gets none in the reference.  ``decoder``: a ``jpeg_decode.JpegDecoder`` that decodes the files on the device
+    (``convnet.frame_batches``)."""
     from .prepare import list_frames
     if boxes is None and detector is None:
         raise ValueError("landmarks_identity: boxes [N,4], one per frame (the face detector is not part of this project)")
@@ -544,7 +545,7 @@ def landmarks_identity(path, weights: FANWeights, device="cuda", boxes=None, wri
         boxes = check_boxes(boxes, len(list_frames(path)))
     net = LandmarkNet(weights, torch.device(device), max_batch=batch)
     out, at = [], 0
-    for ids, frames, _ in convnet.frame_batches(path, batch):
+    for ids, frames, _ in convnet.frame_batches(path, batch, decoder=decoder):
         lms = net.landmarks(frames, detector.first(frames) if boxes is None else boxes[at:at + len(ids)])
         at += len(ids)
         out.append(lms)

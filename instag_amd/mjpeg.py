@@ -11,7 +11,7 @@ this project's (``planes_torch``, ``coefficients_torch``): a JPEG decoder does n
     AviWriter(path, H, W)              JPEG bytes (and audio) -> RIFF AVI, on the host
     VideoWriter(path, H, W, device)    both: ``.append(frames_u8)``
     write_video(renderer, frames, path)   synthesize_fuse.py's render_set
-    read_avi(path)                     -> frames, fps, audio (PIL decodes)
+    read_avi(path)                     -> frames, fps, audio (PIL decodes, or a jpeg_decode.JpegDecoder)
 """
 from __future__ import annotations
 
@@ -541,10 +541,12 @@ def _riff_chunks(buf, start, end):
         pos += 8 + size + (size & 1)
 
 
-def read_avi(path):
+def read_avi(path, decoder=None):
     """-> (frames uint8 [N,H,W,3], fps, audio fp32 [L] in [-1, 1] or None) of a file ``AviWriter`` wrote (or any AVI 1.0
     with an MJPG stream 0 and PCM16 mono stream 1): walks ``movi`` in file order, PIL decodes the frames on the host.
-    Two written videos go to ``metrics.frame_metrics`` this way, as the reference's metrics.py:189-217 reads its two."""
+    Two written videos go to ``metrics.frame_metrics`` this way, as the reference's metrics.py:189-217 reads its two.
+    ``decoder``: a ``jpeg_decode.JpegDecoder``; the frames are then decoded on its device and come back there, with the
+    same bytes (PIL's, uploaded, where its parser refuses a frame or the frames differ in size)."""
     from PIL import Image
     with open(path, "rb") as f:
         buf = f.read()
@@ -563,13 +565,27 @@ def read_avi(path):
         elif kind == b"movi":
             for cc, a, n in _riff_chunks(buf, at + 4, at + size):
                 if cc == b"00dc":
-                    frames.append(np.asarray(Image.open(io.BytesIO(buf[a:a + n])).convert("RGB")))
+                    frames.append(buf[a:a + n])
                 elif cc == b"01wb":
                     audio.append(np.frombuffer(buf, "<i2", n // 2, a))
     if fps is None or not frames:
         raise ValueError(f"{path}: no video stream or no frame")
     sound = torch.from_numpy(np.concatenate(audio).astype(np.float32) / 32768.0) if audio else None
-    return torch.from_numpy(np.stack(frames)), fps, sound
+    pixels = None
+    if decoder is not None:
+        from .jpeg_decode import UnsupportedJpeg, parse_jpeg
+        try:
+            infos = [parse_jpeg(f) for f in frames]
+            if len({(i.H, i.W, i.subsampling) for i in infos}) == 1:
+                pixels = torch.cat([decoder.decode_checked(frames[i:i + MAX_BATCH], infos[i:i + MAX_BATCH])
+                                    for i in range(0, len(frames), MAX_BATCH)])
+        except UnsupportedJpeg:
+            pass
+    if pixels is None:
+        pixels = torch.from_numpy(np.stack([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in frames]))
+        if decoder is not None:
+            pixels = pixels.to(decoder.device)
+    return pixels, fps, sound
 
 
 class VideoWriter:

@@ -296,7 +296,7 @@ def colour_map(logits8, H: int, W: int, out_size=None, want_labels: bool = False
 
 
 # ---- a directory --------------------------------------------------------------------------------------------------------
-def parse_identity(path, weights: BiSeNetWeights, device="cuda", write: bool = True, batch: int = 8):
+def parse_identity(path, weights: BiSeNetWeights, device="cuda", write: bool = True, batch: int = 8, decoder=None):
     """ori_imgs/<i>.jpg of ``path`` (ascending numeric order) -> parsing u8 [N,H,W,3] on ``device``, what
     ``extract_background`` / ``gt_and_torso`` take, H x W the frames' own size.  As test.py:92-106 does, a frame that is
     not 512 x 512 is resized to it on the host (PIL, bilinear) and its colour map resized back (nearest).  ``write``:
@@ -306,7 +306,7 @@ def parse_identity(path, weights: BiSeNetWeights, device="cuda", write: bool = T
     out = []
     if write:
         os.makedirs(os.path.join(path, "parsing"), exist_ok=True)
-    for ids, frames, size in convnet.frame_batches(path, batch, resize=SIZE):
+    for ids, frames, size in convnet.frame_batches(path, batch, resize=SIZE, decoder=decoder):
         par = parser.parse(frames, out_size=(size[1], size[0]))
         out.append(par)
         if write:

@@ -316,18 +316,23 @@ def list_frames(path):
     return ids
 
 
-def prepare_identity(path, device, every: int = 20, write: bool = True, batch: int = 256, parsing=None):
+def prepare_identity(path, device, every: int = 20, write: bool = True, batch: int = 256, parsing=None, decoder=None):
     """ori_imgs/*.jpg + parsing/*.png of ``path`` -> (bc [H,W,3], gt [N,H,W,3], torso [N,H,W,4]) uint8 on ``device``,
     frames in ascending numeric order, ready for FrameStore.append.  ``write``: also bc.jpg, gt_imgs/<i>.jpg (quality 95)
     and torso_imgs/<i>.png, after which dataset.open_identity works on the directory.  ``parsing``: the parsing maps
     u8 [N,H,W,3] in the same order (a tensor on any device or an array; parsing.parse_identity's result), used in place
-    of reading parsing/*.png."""
+    of reading parsing/*.png.  ``decoder``: a ``jpeg_decode.JpegDecoder``; ori_imgs/*.jpg are then decoded on its device
+    (``convnet.frame_batches``) and stay there."""
     from PIL import Image
     ids = list_frames(path)
-    ori = np.stack([np.array(Image.open(os.path.join(path, "ori_imgs", f"{i}.jpg")).convert("RGB")) for i in ids])
+    if decoder is None:
+        ori = np.stack([np.array(Image.open(os.path.join(path, "ori_imgs", f"{i}.jpg")).convert("RGB")) for i in ids])
+    else:
+        from .convnet import frame_batches
+        ori = torch.cat([f.to(decoder.device) for _, f, _ in frame_batches(path, min(batch, 64), decoder=decoder)])
     if parsing is None:
         parsing = np.stack([np.array(Image.open(os.path.join(path, "parsing", f"{i}.png")).convert("RGB")) for i in ids])
-    elif tuple(parsing.shape) != ori.shape:
+    elif tuple(parsing.shape) != tuple(ori.shape):
         raise ValueError(f"prepare_identity: parsing {tuple(parsing.shape)}, the frames are {ori.shape}")
     device = torch.device(device)
     bc = extract_background(ori, parsing, every, device)

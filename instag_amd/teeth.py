@@ -271,15 +271,16 @@ def teeth_labels(logits4, H: int, W: int, want_mask: bool = False):
 
 
 # ---- a directory --------------------------------------------------------------------------------------------------------
-def teeth_identity(path, weights: FPNWeights, device="cuda", write: bool = True, batch: int = 8):
+def teeth_identity(path, weights: FPNWeights, device="cuda", write: bool = True, batch: int = 8, decoder=None):
     """ori_imgs/<i>.jpg of ``path`` (ascending numeric order) -> teeth masks u8 [N,H,W] (1 = teeth) on ``device``, what
     ``FrameStore.append(teeth=...)`` takes, H x W the frames' own size (create_teeth_mask.py does not resize).
-    ``write``: also teeth_mask/<i>.npy as ``np.bool_ [H,W]``, the file ``dataset.decode_images`` reads."""
+    ``write``: also teeth_mask/<i>.npy as ``np.bool_ [H,W]``, the file ``dataset.decode_images`` reads.  ``decoder``: a
+    ``jpeg_decode.JpegDecoder`` that decodes the files on the device (``convnet.frame_batches``)."""
     seg = TeethSegmenter(weights, torch.device(device), max_batch=batch)
     out = []
     if write:
         os.makedirs(os.path.join(path, "teeth_mask"), exist_ok=True)
-    for ids, frames, _ in convnet.frame_batches(path, batch):
+    for ids, frames, _ in convnet.frame_batches(path, batch, decoder=decoder):
         mask = seg.mask(frames)
         out.append(mask)
         if write:
