@@ -249,19 +249,14 @@ def _decoded_on_device(paths, size, resize, decoder):
     """The files of one batch through ``decoder`` (a ``jpeg_decode.JpegDecoder``) -> (frames on its device, (width,
     height)), or None where the batch is PIL's: a file the decoder's parser refuses, files of different sizes or not of
     ``size``, or a size that ``resize`` changes."""
-    from .jpeg_decode import UnsupportedJpeg, parse_jpeg
     files = []
     for p in paths:
         with open(p, "rb") as f:
             files.append(f.read())
-    try:
-        infos = [parse_jpeg(f) for f in files]
-    except UnsupportedJpeg:
+    want = (resize, resize) if resize else size
+    if size is not None and want != size:
         return None
-    sizes = {(i.W, i.H) for i in infos} | ({size} if size is not None else set())
-    if len(sizes) != 1 or len({i.subsampling for i in infos}) != 1 or (resize and sizes != {(resize, resize)}):
-        return None
-    return decoder.decode_checked(files, infos), sizes.pop()
+    return decoder.decode_uniform(files, want)
 
 
 def frame_batches(path, batch: int, resize=None, decoder=None):

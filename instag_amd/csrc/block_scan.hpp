@@ -33,4 +33,19 @@ __device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_wave
   return all;
 }
 
+// v[0..n) -> its exclusive prefix sums, in place, THREADS values at a time with a carried total; -> the sum of all.
+// `s_wave` as above.  Every thread of the workgroup calls it; a thread sees the others' writes after a __syncthreads().
+template <int THREADS>
+__device__ __forceinline__ uint32_t carried_exclusive(uint32_t* v, uint32_t n, uint32_t* s_wave) {
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < n; base += THREADS) {
+    const uint32_t i = base + threadIdx.x;
+    uint32_t ex;
+    const uint32_t all = block_exclusive<THREADS>(i < n ? v[i] : 0, s_wave, ex);
+    if (i < n) v[i] = carry + ex;
+    carry += all;
+  }
+  return carry;
+}
+
 }  // namespace instag

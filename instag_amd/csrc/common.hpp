@@ -78,6 +78,12 @@ struct Arena {
   size_t take(size_t n) { const size_t o = off; off += align_up(n, 64); return o; }
 };
 
+// the same in bytes: every piece starts at a multiple of 256
+struct ByteArena {
+  size_t off = 0;
+  size_t take(size_t n) { const size_t o = off; off += align_up(n, 256); return o; }
+};
+
 // ---- rasterizer buffer layouts (device memory, opaque to the caller) ----------------------------
 constexpr int TILE_X = 16;
 constexpr int TILE_Y = 16;

@@ -16,9 +16,8 @@
 //              (e) running sum of the DC differences per component
 //   idct       eight lanes per block: dequantise, jidctint's "islow" columns then rows, into Y / Cb / Cr planes
 //   colour     one lane per pixel: h2v2 "fancy" upsampling at 4:2:0, YCbCr -> RGB, cropped
-#include "common.hpp"
 #include "block_scan.hpp"
-#include "instag_jpeg_decode.h"
+#include "jpeg_common.hpp"
 
 namespace instag {
 namespace {
@@ -31,14 +30,8 @@ constexpr int TABLE_BYTES = INSTAG_JPEG_DECODE_TABLE_BYTES;
 constexpr uint32_t IDLE = 0xffffffffu;           // k | j << 8 of a lane that walks no further
 static_assert(SCAN_THREADS * STUFF_BYTES == INSTAG_JPEG_DECODE_SCAN_BYTES && TABLE_BYTES == 16 * 4 + 16 * 4 + 256, "");
 
-__device__ const uint8_t d_zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
-                                         41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22,
-                                         15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
-                                         62, 63};
-
 // ---- geometry and the workspace --------------------------------------------------------------------------------------
-struct Geom {
-  int H, W, sub, mx, my, per, nblk;
+struct Geom : JpegGrid {
   int Hp, Wp, Hc, Wc;                    // the luma and chroma planes, whole blocks
   uint32_t sstride;                      // bytes of one frame's unstuffed stream: capacity, and room for two words more
   uint32_t counts;                       // counts of dropped bytes of one frame
@@ -46,38 +39,27 @@ struct Geom {
   size_t coef, y, c, stream, count, total, state, bytes;   // byte offsets of the pieces in the workspace of B frames
 };
 
-bool shape_ok(int B, int H, int W, int sub) {
-  return B >= 1 && B <= INSTAG_JPEG_DECODE_MAX_BATCH && H >= 1 && H <= INSTAG_JPEG_DECODE_MAX_SIDE && W >= 1 &&
-         W <= INSTAG_JPEG_DECODE_MAX_SIDE && (sub == 1 || sub == 2);
-}
 bool scan_ok(int capacity, int sub_bits) {
   return capacity >= 1 && capacity <= INSTAG_JPEG_DECODE_MAX_CAPACITY && sub_bits >= INSTAG_JPEG_DECODE_MIN_SUB_BITS &&
          sub_bits <= INSTAG_JPEG_DECODE_MAX_SUB_BITS && sub_bits % 32 == 0;
 }
-const char* const SHAPE_OK = ": 1 <= B <= 64, 1 <= H, W <= 4096, sub 1 (4:4:4) or 2 (4:2:0)";
 const char* const SCAN_OK = ": 1 <= capacity <= 2^28, sub_bits a multiple of 32 in 64..4096";
 
 Geom geometry(int B, int H, int W, int sub, int capacity, int sub_bits) {
-  Geom g{};
-  g.H = H, g.W = W, g.sub = sub;
-  const int mcu = 8 * sub;
-  g.mx = div_up(W, mcu), g.my = div_up(H, mcu);
-  g.per = sub * sub + 2;
-  g.nblk = g.mx * g.my * g.per;
-  g.Hp = g.my * mcu, g.Wp = g.mx * mcu, g.Hc = g.my * 8, g.Wc = g.mx * 8;
+  Geom g{jpeg_grid(H, W, sub)};
+  g.Hp = g.my * 8 * sub, g.Wp = g.mx * 8 * sub, g.Hc = g.my * 8, g.Wc = g.mx * 8;
   g.sstride = (uint32_t)align_up((size_t)capacity, 4) + 8;
   g.counts = div_up((uint32_t)capacity, (uint32_t)STUFF_BYTES);
   g.nsub = (uint32_t)div_up((uint64_t)capacity * 8, (uint64_t)sub_bits);
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t o = at; at += align_up(n, 256); return o; };
-  g.coef = take((size_t)B * g.nblk * 64 * sizeof(int16_t));
-  g.y = take((size_t)B * g.Hp * g.Wp);
-  g.c = take((size_t)B * 2 * g.Hc * g.Wc);
-  g.stream = take((size_t)B * g.sstride);
-  g.count = take((size_t)B * g.counts * sizeof(uint32_t));
-  g.total = take((size_t)B * 4 * sizeof(uint32_t));
-  g.state = take((size_t)B * 5 * (g.nsub + 1) * sizeof(uint32_t));
-  g.bytes = at;
+  ByteArena a;
+  g.coef = a.take((size_t)B * g.nblk * 64 * sizeof(int16_t));
+  g.y = a.take((size_t)B * g.Hp * g.Wp);
+  g.c = a.take((size_t)B * 2 * g.Hc * g.Wc);
+  g.stream = a.take((size_t)B * g.sstride);
+  g.count = a.take((size_t)B * g.counts * sizeof(uint32_t));
+  g.total = a.take((size_t)B * 4 * sizeof(uint32_t));
+  g.state = a.take((size_t)B * 5 * (g.nsub + 1) * sizeof(uint32_t));
+  g.bytes = a.off;
   return g;
 }
 
@@ -121,16 +103,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_unstuff_scan(uint32_t* __re
   const int b = blockIdx.x;
   const uint32_t n = scan_length(scan_bytes, b, capacity);
   const uint32_t used = min(counts, (n + STUFF_BYTES - 1) / STUFF_BYTES);
-  uint32_t* c = count + (size_t)b * counts;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < used; base += SCAN_THREADS) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < used ? c[i] : 0;
-    uint32_t ex;
-    const uint32_t all = block_exclusive<SCAN_THREADS>(v, s_wave, ex);
-    if (i < used) c[i] = carry + ex;
-    carry += all;
-  }
+  const uint32_t carry = carried_exclusive<SCAN_THREADS>(count + (size_t)b * counts, used, s_wave);
   if (threadIdx.x == 0) total[b * 4] = 8u * (n - min(carry, n));
 }
 
@@ -192,13 +165,13 @@ template <bool WRITE>
 __device__ __forceinline__ int decode_span(const uint32_t* __restrict__ s, uint32_t nbits, uint32_t end, const Tables& T,
                                            int sub, State& st, uint32_t& done, int16_t* __restrict__ fc, uint32_t first,
                                            uint32_t nblk) {
-  const int ny = sub * sub, per = ny + 2;
+  const int per = sub * sub + 2;
   uint32_t p = st.p;
   int k = (int)(st.kj & 255), j = (int)(st.kj >> 8), err = 0;
   done = 0;
   while (p < end) {
     if (WRITE && first + done >= nblk) break;
-    const int t = (k == 0 ? 0 : 3) + (j < ny ? 0 : j - ny + 1);
+    const int t = (k == 0 ? 0 : 3) + mcu_component(j, sub);
     const uint32_t v = peek32(s, p, nbits), v16 = v >> 16;
     int l = 0;
 #pragma unroll
@@ -347,15 +320,7 @@ __global__ __launch_bounds__(LANES) void jpeg_huffman(const uint8_t* __restrict_
   __syncthreads();
 
   // (c)
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < nsub; base += LANES) {
-    const uint32_t m = base + tid;
-    const uint32_t v = m < nsub ? cnt[m] : 0;
-    uint32_t ex;
-    const uint32_t all = block_exclusive<LANES>(v, s_wave, ex);
-    if (m < nsub) cnt[m] = carry + ex;
-    carry += all;
-  }
+  carried_exclusive<LANES>(cnt, nsub, s_wave);
   __syncthreads();
 
   // (d): a lane stops at its first error; the states behind it are those of a decoder that went on, so their lanes
@@ -433,12 +398,12 @@ __global__ __launch_bounds__(256) void jpeg_idct(const int16_t* __restrict__ coe
                                                  uint8_t* __restrict__ yplane, uint8_t* __restrict__ cplane) {
   __shared__ int s[IDCT_BLOCKS][65];
   const int tid = threadIdx.x, b = blockIdx.y, g0 = blockIdx.x * IDCT_BLOCKS;
-  const int ny = sub * sub, per = ny + 2;
+  const int per = sub * sub + 2;
   for (int i = tid; i < IDCT_BLOCKS * 64; i += 256) {
     const int blk = i >> 6, k = i & 63, g = g0 + blk, nat = d_zigzag[k];
     int v = 0;
     if (g < nblk) {
-      const int j = g % per, comp = j < ny ? 0 : j - ny + 1;
+      const int comp = mcu_component(g % per, sub);
       v = (int)coef[((size_t)b * nblk + g) * 64 + k] * (int)quant[((size_t)b * 3 + comp) * 64 + nat];
     }
     s[blk][nat] = v;
@@ -456,12 +421,12 @@ __global__ __launch_bounds__(256) void jpeg_idct(const int16_t* __restrict__ coe
   for (int k = 0; k < 8; ++k) x[k] = s[blk][c * 8 + k];                    // (c is the row now)
   idct_pass<18>(x);
   if (g >= nblk) return;
-  const int m = g / per, j = g % per, mrow = m / mx, mcol = m % mx;
+  const int m = g / per, j = g % per, mrow = m / mx, mcol = m % mx, comp = mcu_component(j, sub);
   uint8_t* out;
-  if (j < ny)
+  if (comp == 0)
     out = yplane + ((size_t)b * Hp + (mrow * sub + j / sub) * 8 + c) * Wp + (mcol * sub + j % sub) * 8;
   else
-    out = cplane + (((size_t)b * 2 + (j - ny)) * Hc + mrow * 8 + c) * Wc + mcol * 8;
+    out = cplane + (((size_t)b * 2 + (comp - 1)) * Hc + mrow * 8 + c) * Wc + mcol * 8;
   uint64_t packed = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k) packed |= (uint64_t)min(max(x[k] + 128, 0), 255) << (8 * k);
@@ -542,8 +507,8 @@ using namespace instag;
 extern "C" {
 
 size_t instag_jpeg_decode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t sub, int32_t capacity, int32_t sub_bits) {
-  if (!shape_ok(B, H, W, sub) || !scan_ok(capacity, sub_bits)) {
-    set_error(std::string("jpeg_decode_workspace_bytes") + (shape_ok(B, H, W, sub) ? SCAN_OK : SHAPE_OK));
+  if (!jpeg_shape_ok(B, H, W, sub) || !scan_ok(capacity, sub_bits)) {
+    set_error(std::string("jpeg_decode_workspace_bytes") + (jpeg_shape_ok(B, H, W, sub) ? SCAN_OK : JPEG_SHAPE_OK));
     return 0;
   }
   return geometry(B, H, W, sub, capacity, sub_bits).bytes;
@@ -554,7 +519,7 @@ int instag_jpeg_decode_coefficients(const uint8_t* scans, int32_t capacity, cons
                                     int32_t sub_bits, int16_t* coef, int32_t* status, void* workspace,
                                     size_t workspace_bytes, instag_stream_t stream) {
   INSTAG_REQUIRE(scans && scan_bytes && huffman && coef && status && workspace, "jpeg_decode_coefficients: NULL tensor");
-  INSTAG_REQUIRE(shape_ok(B, H, W, sub), std::string("jpeg_decode_coefficients") + SHAPE_OK);
+  INSTAG_REQUIRE(jpeg_shape_ok(B, H, W, sub), std::string("jpeg_decode_coefficients") + JPEG_SHAPE_OK);
   INSTAG_REQUIRE(scan_ok(capacity, sub_bits), std::string("jpeg_decode_coefficients") + SCAN_OK);
   const Geom g = geometry(B, H, W, sub, capacity, sub_bits);
   if (workspace_bytes < g.bytes) {
@@ -568,7 +533,7 @@ int instag_jpeg_decode_coefficients(const uint8_t* scans, int32_t capacity, cons
 int instag_jpeg_decode_pixels(const int16_t* coef, const uint16_t* quant, int32_t B, int32_t H, int32_t W, int32_t sub,
                               uint8_t* frames, void* workspace, size_t workspace_bytes, instag_stream_t stream) {
   INSTAG_REQUIRE(coef && quant && frames && workspace, "jpeg_decode_pixels: NULL tensor");
-  INSTAG_REQUIRE(shape_ok(B, H, W, sub), std::string("jpeg_decode_pixels") + SHAPE_OK);
+  INSTAG_REQUIRE(jpeg_shape_ok(B, H, W, sub), std::string("jpeg_decode_pixels") + JPEG_SHAPE_OK);
   const Geom g = geometry(B, H, W, sub, 1, INSTAG_JPEG_DECODE_MIN_SUB_BITS);
   if (workspace_bytes < g.bytes) {
     set_error("jpeg_decode_pixels: workspace too small");
@@ -581,7 +546,7 @@ int instag_jpeg_decode(const uint8_t* scans, int32_t capacity, const int32_t* sc
                        const uint16_t* quant, int32_t B, int32_t H, int32_t W, int32_t sub, int32_t sub_bits,
                        uint8_t* frames, int32_t* status, void* workspace, size_t workspace_bytes, instag_stream_t stream) {
   INSTAG_REQUIRE(scans && scan_bytes && huffman && quant && frames && status && workspace, "jpeg_decode: NULL tensor");
-  INSTAG_REQUIRE(shape_ok(B, H, W, sub), std::string("jpeg_decode") + SHAPE_OK);
+  INSTAG_REQUIRE(jpeg_shape_ok(B, H, W, sub), std::string("jpeg_decode") + JPEG_SHAPE_OK);
   INSTAG_REQUIRE(scan_ok(capacity, sub_bits), std::string("jpeg_decode") + SCAN_OK);
   const Geom g = geometry(B, H, W, sub, capacity, sub_bits);
   if (workspace_bytes < g.bytes) {

@@ -16,9 +16,8 @@
 //   finish     one workgroup per frame: exclusive scan of those counts; header, EOI, length and overflow
 //   scatter    every byte to header + index + 0xFF bytes in front of it, a 0x00 behind each 0xFF; nothing at or past
 //              `capacity`
-#include "common.hpp"
 #include "block_scan.hpp"
-#include "instag_mjpeg.h"
+#include "jpeg_common.hpp"
 
 namespace instag {
 namespace {
@@ -37,10 +36,6 @@ __device__ const uint8_t d_quant[2][64] = {
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
      47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-__device__ const uint8_t d_zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
-                                         41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22,
-                                         15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
-                                         62, 63};
 // round(16384 C), C the orthonormal 8-point DCT-II matrix
 __device__ const int16_t d_dct[64] = {
     5793, 5793,  5793,  5793,  5793,  5793,  5793,  5793,  8035, 6811,  4551,  1598,  -1598, -4551, -6811, -8035,
@@ -101,38 +96,25 @@ constexpr HuffCodes make_codes() {
 __device__ const HuffCodes d_codes = make_codes();
 
 // ---- geometry and the workspace --------------------------------------------------------------------------------------
-struct Geom {
-  int H, W, sub, mx, my, per, nblk;
+struct Geom : JpegGrid {
   uint32_t max_bits;                     // of one frame's scan: nblk * BLOCK_BITS (< 2^30 at 4096 x 4096)
   uint32_t words;                        // of one frame's word stream, three spare for the last lane's span
   uint32_t counts;                       // 0xFF counts of one frame
   size_t coef, offset, total, stream, count, bytes;   // byte offsets of the pieces in the workspace of B frames
 };
 
-bool shape_ok(int B, int H, int W, int sub) {
-  return B >= 1 && B <= INSTAG_MJPEG_MAX_BATCH && H >= 1 && H <= INSTAG_MJPEG_MAX_SIDE && W >= 1 &&
-         W <= INSTAG_MJPEG_MAX_SIDE && (sub == 1 || sub == 2);
-}
-const char* const SHAPE_OK = ": 1 <= B <= 64, 1 <= H, W <= 4096, sub 1 (4:4:4) or 2 (4:2:0)";
-
 Geom geometry(int B, int H, int W, int sub) {
-  Geom g{};
-  g.H = H, g.W = W, g.sub = sub;
-  const int mcu = 8 * sub;
-  g.mx = div_up(W, mcu), g.my = div_up(H, mcu);
-  g.per = sub * sub + 2;
-  g.nblk = g.mx * g.my * g.per;
+  Geom g{jpeg_grid(H, W, sub)};
   g.max_bits = (uint32_t)g.nblk * INSTAG_MJPEG_BLOCK_BITS;
   g.words = div_up(g.max_bits, 32u) + 3;
   g.counts = div_up(div_up(g.max_bits, 8u), (uint32_t)STUFF_BYTES);
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t o = at; at += align_up(n, 256); return o; };
-  g.coef = take((size_t)B * g.nblk * 64 * sizeof(int16_t));
-  g.offset = take((size_t)B * g.nblk * sizeof(uint32_t));
-  g.total = take((size_t)B * 4 * sizeof(uint32_t));
-  g.stream = take((size_t)B * g.words * sizeof(uint32_t));
-  g.count = take((size_t)B * g.counts * sizeof(uint32_t));
-  g.bytes = at;
+  ByteArena a;
+  g.coef = a.take((size_t)B * g.nblk * 64 * sizeof(int16_t));
+  g.offset = a.take((size_t)B * g.nblk * sizeof(uint32_t));
+  g.total = a.take((size_t)B * 4 * sizeof(uint32_t));
+  g.stream = a.take((size_t)B * g.words * sizeof(uint32_t));
+  g.count = a.take((size_t)B * g.counts * sizeof(uint32_t));
+  g.bytes = a.off;
   return g;
 }
 
@@ -178,7 +160,7 @@ __global__ __launch_bounds__(256) void mjpeg_blocks(const uint8_t* __restrict__ 
   for (int blk = wave; blk < NB; blk += 4) {
     const int m = blk / PER, j = blk % PER, gm = blockIdx.x * MPS + m;
     const bool live = gm < mx;
-    const int comp = j < SUB * SUB ? 0 : j - SUB * SUB + 1;
+    const int comp = mcu_component(j, SUB);
     // rows: T[i][v] = (sum_j X[i][j] Q[v][j] + 512) >> 10
     int acc = 0;
     if (live) {
@@ -218,7 +200,7 @@ __device__ __forceinline__ int bit_length(int mag) { return 32 - __clz(mag); }  
 // what lane `lane` of the wave that owns block `blk` of a frame writes: `n` bits, the low ones of `val`, MSB first
 __device__ __forceinline__ void lane_symbol(const int16_t* __restrict__ fc, int blk, int sub, int lane, uint64_t& val,
                                             int& n) {
-  const int tab = sub == 1 ? blk % 3 > 0 : blk % 6 >= 4;
+  const int tab = (sub == 1 ? mcu_component(blk % 3, 1) : mcu_component(blk % 6, 2)) > 0;
   const int v = fc[(size_t)blk * 64 + lane];
   const uint64_t set = __ballot(v != 0) | 1ull;            // bit 0 stands for "in front of the first AC position"
   val = 0, n = 0;
@@ -261,16 +243,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mjpeg_scan(uint32_t* __restrict_
                                                            uint32_t words) {
   __shared__ uint32_t s_wave[SCAN_THREADS / 64];
   const int b = blockIdx.x;
-  uint32_t* o = offset + (size_t)b * nblk;
-  uint32_t carry = 0;
-  for (int base = 0; base < nblk; base += SCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const uint32_t v = i < nblk ? o[i] : 0;
-    uint32_t ex;
-    const uint32_t all = block_exclusive<SCAN_THREADS>(v, s_wave, ex);
-    if (i < nblk) o[i] = carry + ex;
-    carry += all;
-  }
+  const uint32_t carry = carried_exclusive<SCAN_THREADS>(offset + (size_t)b * nblk, (uint32_t)nblk, s_wave);
   if (threadIdx.x == 0) {
     total[b * 4 + 0] = carry;
     total[b * 4 + 1] = (carry + 7) >> 3;
@@ -350,16 +323,7 @@ __global__ __launch_bounds__(FINISH_THREADS) void mjpeg_finish(uint32_t* __restr
   const int b = blockIdx.x;
   const uint32_t bytes = total[b * 4 + 1];
   const uint32_t used = (bytes + STUFF_BYTES - 1) / STUFF_BYTES;         // <= counts
-  uint32_t* c = count + (size_t)b * counts;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < used; base += FINISH_THREADS) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < used ? c[i] : 0;
-    uint32_t ex;
-    const uint32_t all = block_exclusive<FINISH_THREADS>(v, s_wave, ex);
-    if (i < used) c[i] = carry + ex;
-    carry += all;
-  }
+  const uint32_t carry = carried_exclusive<FINISH_THREADS>(count + (size_t)b * counts, used, s_wave);
   uint8_t* row = out + (size_t)b * capacity;
   for (int i = threadIdx.x; i < header_bytes && i < capacity; i += FINISH_THREADS) row[i] = header[i];
   const uint32_t end = (uint32_t)header_bytes + bytes + carry;           // < 2^31: two bytes per bit-stream byte at most
@@ -415,8 +379,8 @@ using namespace instag;
 extern "C" {
 
 size_t instag_mjpeg_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t sub) {
-  if (!shape_ok(B, H, W, sub)) {
-    set_error(std::string("mjpeg_workspace_bytes") + SHAPE_OK);
+  if (!jpeg_shape_ok(B, H, W, sub)) {
+    set_error(std::string("mjpeg_workspace_bytes") + JPEG_SHAPE_OK);
     return 0;
   }
   return geometry(B, H, W, sub).bytes;
@@ -425,7 +389,7 @@ size_t instag_mjpeg_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t sub
 int instag_mjpeg_coefficients(const uint8_t* frames, int32_t B, int32_t H, int32_t W, int32_t quality, int32_t sub,
                               int16_t* coef, instag_stream_t stream) {
   INSTAG_REQUIRE(frames && coef, "mjpeg_coefficients: NULL tensor");
-  INSTAG_REQUIRE(shape_ok(B, H, W, sub), std::string("mjpeg_coefficients") + SHAPE_OK);
+  INSTAG_REQUIRE(jpeg_shape_ok(B, H, W, sub), std::string("mjpeg_coefficients") + JPEG_SHAPE_OK);
   INSTAG_REQUIRE(quality >= 1 && quality <= 100, "mjpeg_coefficients: quality in 1..100");
   return launch_blocks(frames, B, geometry(B, H, W, sub), quality, coef, (hipStream_t)stream);
 }
@@ -434,7 +398,7 @@ int instag_mjpeg_encode(const uint8_t* frames, int32_t B, int32_t H, int32_t W, 
                         const uint8_t* header, int32_t header_bytes, uint8_t* out, int32_t capacity, int32_t* length,
                         uint8_t* overflow, void* workspace, size_t workspace_bytes, instag_stream_t stream) {
   INSTAG_REQUIRE(frames && header && out && length && overflow && workspace, "mjpeg_encode: NULL tensor");
-  INSTAG_REQUIRE(shape_ok(B, H, W, sub), std::string("mjpeg_encode") + SHAPE_OK);
+  INSTAG_REQUIRE(jpeg_shape_ok(B, H, W, sub), std::string("mjpeg_encode") + JPEG_SHAPE_OK);
   INSTAG_REQUIRE(quality >= 1 && quality <= 100, "mjpeg_encode: quality in 1..100");
   INSTAG_REQUIRE(header_bytes >= 1 && header_bytes <= 4096 && capacity >= 1,
                  "mjpeg_encode: 1 <= header_bytes <= 4096, capacity >= 1");

@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from .device_op import DeviceOperator
-from .mjpeg import MAX_BATCH, MAX_SIDE, SUBSAMPLING, ZIGZAG, _sub, block_count
+from .jpeg_common import (MAX_BATCH, MAX_SIDE, MCU_COMPONENTS, SUBSAMPLING, ZIGZAG, block_count, code_ranges, mcu_grid,
+                          planes_from_blocks, sub_of)
 
 STATUS = {1: "a code that is in no Huffman table", 2: "a coefficient index past 63",
           3: "the scan ends before the last block"}
@@ -52,12 +53,9 @@ class JpegInfo:
 # ---- the file -----------------------------------------------------------------------------------------------------------
 def _check_table(bits, vals, what):
     """Annex C: the codes of every length fit that length."""
-    code = 0
-    for length in range(1, 17):
-        code += bits[length - 1]
-        if code > 1 << length:
+    for length, (code, n, _) in enumerate(code_ranges(bits), 1):
+        if code + n > 1 << length:
             raise UnsupportedJpeg(f"DHT {what}: more codes of length {length} than there are")
-        code <<= 1
     if len(vals) > 256:
         raise UnsupportedJpeg(f"DHT {what}: more than 256 symbols")
 
@@ -209,11 +207,9 @@ def decode_tables(bits, vals):
     """The canonical description of a Huffman table the device reads (include/instag_jpeg_decode.h): int32 limit[16],
     base[16] and uint8 vals[256]."""
     limit, base = np.zeros(16, np.int32), np.zeros(16, np.int32)
-    code, k = 0, 0
-    for length in range(1, 17):
-        limit[length - 1] = (code + bits[length - 1]) << (16 - length)
+    for length, (code, n, k) in enumerate(code_ranges(bits), 1):
+        limit[length - 1] = (code + n) << (16 - length)
         base[length - 1] = k - code
-        code, k = (code + bits[length - 1]) << 1, k + bits[length - 1]
     v = np.zeros(256, np.uint8)
     v[:len(vals)] = vals
     return limit, base, v
@@ -221,14 +217,10 @@ def decode_tables(bits, vals):
 
 def _lookup(bits, vals):
     """The next 16 bits -> length << 8 | symbol, 0 where they start no code."""
-    limit, base, v = decode_tables(bits, vals)
-    out, lo = np.zeros(65536, np.int32), 0
-    for length in range(1, 17):
-        hi = int(limit[length - 1])
-        if hi > lo:
-            idx = np.arange(lo, hi)
-            out[lo:hi] = v[((idx >> (16 - length)) + int(base[length - 1])) & 255].astype(np.int32) | length << 8
-            lo = hi
+    out = np.zeros(65536, np.int32)
+    for length, (code, n, k) in enumerate(code_ranges(bits), 1):
+        for i in range(n):                                                      # every 16 bits that begin with code + i
+            out[(code + i) << (16 - length):(code + i + 1) << (16 - length)] = vals[k + i] | length << 8
     return out.tolist()
 
 
@@ -242,7 +234,7 @@ def coefficients_from_scan_torch(info: JpegInfo, data: bytes) -> torch.Tensor:
     nbits = 8 * len(raw)
     raw += b"\xff" * 8
     nblk = block_count(info.H, info.W, info.subsampling)
-    per = (0, 1, 2) if _sub(info.subsampling) == 1 else (0, 0, 0, 0, 1, 2)
+    per = MCU_COMPONENTS[sub_of(info.subsampling)]
     dc = [_lookup(*t) for t in info.dc]
     ac = [_lookup(*t) for t in info.ac]
     out = np.zeros((nblk, 64), np.int64)
@@ -341,25 +333,16 @@ def colour_torch(Y, Cb, Cr):
     return torch.stack([R, G, B], -1).clamp(0, 255).to(torch.uint8)
 
 
-def _check_size(H, W):
-    if not (1 <= int(H) <= MAX_SIDE and 1 <= int(W) <= MAX_SIDE):
-        raise ValueError(f"1 <= H, W <= {MAX_SIDE}, got {H} x {W}")
-
-
 def pixels_torch(coef, quant, H, W, subsampling="4:2:0"):
     """coef int16 [nblk, 64] (``coefficients_from_scan_torch``), quant [3, 64] -> uint8 [H, W, 3]: inverse DCT per block
     (``idct_torch``), the planes put together, 4:2:0 chroma upsampled (``upsample_torch``), colour, cropped."""
-    s = _sub(subsampling)
-    _check_size(H, W)
+    s = sub_of(subsampling)
     nblk = block_count(H, W, subsampling)
     if coef.dim() != 2 or tuple(coef.shape) != (nblk, 64) or tuple(quant.shape) != (3, 64):
         raise ValueError(f"coef is [{nblk}, 64] and quant [3, 64], got {tuple(coef.shape)} and {tuple(quant.shape)}")
-    per = s * s + 2
-    my, mx = -(-H // (8 * s)), -(-W // (8 * s))
-    comp = torch.tensor(((0,) * (s * s) + (1, 2)) * (my * mx), device=coef.device)
-    px = idct_torch(coef, quant.to(coef.device)[comp]).reshape(my, mx, per, 8, 8)
-    Y = px[:, :, :s * s].reshape(my, mx, s, s, 8, 8).permute(0, 2, 4, 1, 3, 5).reshape(my * s * 8, mx * s * 8)
-    Cb, Cr = (px[:, :, s * s + i].permute(0, 2, 1, 3).reshape(my * 8, mx * 8) for i in (0, 1))
+    my, mx = mcu_grid(H, W, s)
+    comp = torch.tensor(MCU_COMPONENTS[s] * (my * mx), device=coef.device)
+    Y, Cb, Cr = planes_from_blocks(idct_torch(coef, quant.to(coef.device)[comp]), s, my, mx)
     if s == 2:
         Cb, Cr = upsample_torch(Cb, H, W), upsample_torch(Cr, H, W)
     return colour_torch(Y[:H, :W], Cb[:H, :W], Cr[:H, :W])
@@ -466,7 +449,7 @@ class JpegDecoder(DeviceOperator):
         int32 [B]: launches on the current stream only, so it can be captured."""
         from . import _lib
         B, H, W, _ = frames.shape
-        sub, cap = _sub(subsampling), int(scans.shape[1])
+        sub, cap = sub_of(subsampling), int(scans.shape[1])
         self._check_packed(B, scans, scan_bytes, huffman, quant)
         if (frames.dtype != torch.uint8 or frames.shape[3] != 3 or not frames.is_contiguous() or status.dtype != torch.int32
                 or tuple(status.shape) != (B,) or not status.is_contiguous()):
@@ -510,7 +493,7 @@ class JpegDecoder(DeviceOperator):
         """``coefficients`` of scans that are on the device already (rows of a ``JpegEncoder.encode`` behind the header):
         ``scans`` uint8 [B, capacity], ``scan_bytes`` int32 [B], ``huffman`` uint8 [B, 6, 384]."""
         from . import _lib
-        B, sub, cap = int(scans.shape[0]), _sub(subsampling), int(scans.shape[1])
+        B, sub, cap = int(scans.shape[0]), sub_of(subsampling), int(scans.shape[1])
         self._check_packed(B, scans, scan_bytes, huffman, None)
         nblk = block_count(H, W, subsampling)
         coef = torch.empty(B, nblk, 64, dtype=torch.int16, device=self.device) if coef is None else coef
@@ -522,8 +505,7 @@ class JpegDecoder(DeviceOperator):
 
     def pixels(self, coef, quant, H, W, subsampling="4:2:0", frames=None):
         """coef int16 [B, nblk, 64], quant [3, 64] or [B, 3, 64] -> uint8 [B,H,W,3] (``pixels_torch`` per frame)."""
-        _check_size(H, W)
-        sub, nblk = _sub(subsampling), block_count(H, W, subsampling)
+        sub, nblk = sub_of(subsampling), block_count(H, W, subsampling)
         if coef.dtype != torch.int16 or coef.dim() != 3 or tuple(coef.shape[1:]) != (nblk, 64) or coef.shape[0] < 1:
             raise ValueError(f"JpegDecoder: coef int16 [B,{nblk},64], got {coef.dtype} {tuple(coef.shape)}")
         B = coef.shape[0]
@@ -553,3 +535,15 @@ class JpegDecoder(DeviceOperator):
             if s:
                 raise ValueError(f"JpegDecoder: file {b} of the call: {STATUS.get(s, f'status {s}')}")
         return frames
+
+    def decode_uniform(self, files, want=None):
+        """-> (``decode_checked``'s frames, ``MAX_BATCH`` files at a time, (W, H)); None where ``parse_jpeg`` refuses a file,
+        the files do not share (H, W, subsampling) or their size is not ``want`` (a (W, H)).  A damaged scan still raises."""
+        try:
+            infos, H, W, _ = self.parse(files)
+        except ValueError:                                                      # (UnsupportedJpeg is one)
+            return None
+        if want is not None and tuple(want) != (W, H):
+            return None
+        pieces = [self.decode_checked(files[i:i + MAX_BATCH], infos[i:i + MAX_BATCH]) for i in range(0, len(files), MAX_BATCH)]
+        return pieces[0] if len(pieces) == 1 else torch.cat(pieces), (W, H)

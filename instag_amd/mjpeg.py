@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from .device_op import DeviceOperator
+from .jpeg_common import (MAX_BATCH, MAX_SIDE, MCU_COMPONENTS, SUBSAMPLING, ZIGZAG, block_components, block_count,
+                          blocks_from_planes, check_size, code_ranges, mcu_grid, sub_of)
 
 # ---- ITU T.81 Annex K ---------------------------------------------------------------------------------------------------
 LUMA_QUANT = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
@@ -41,29 +43,12 @@ AC_CHROMA_VALS = tuple(bytes.fromhex(
     "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a353637"
     "38393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3"
     "a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
-# zig-zag position k -> index in the 8 x 8 block, row by row
-ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
-          21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53,
-          60, 61, 54, 47, 55, 62, 63)
 # round(16384 C), C the orthonormal 8-point DCT-II matrix: C[u][j] = c(u) cos((2 j + 1) u pi / 16)
 DCT_Q14 = ((5793, 5793, 5793, 5793, 5793, 5793, 5793, 5793), (8035, 6811, 4551, 1598, -1598, -4551, -6811, -8035),
            (7568, 3135, -3135, -7568, -7568, -3135, 3135, 7568), (6811, -1598, -8035, -4551, 4551, 8035, 1598, -6811),
            (5793, -5793, -5793, 5793, 5793, -5793, -5793, 5793), (4551, -8035, 1598, 6811, -6811, -1598, 8035, -4551),
            (3135, -7568, 7568, -3135, -3135, 7568, -7568, 3135), (1598, -4551, 6811, -8035, 8035, -6811, 4551, -1598))
-SUBSAMPLING = {"4:4:4": 1, "4:2:0": 2}              # -> the C side's `sub`: the chroma planes' divisor
 BLOCK_BITS = 1660                                   # 11 + 11 bits of DC, 63 x (16 + 10) of AC: no block codes longer
-MAX_SIDE, MAX_BATCH = 4096, 64
-
-
-def _sub(subsampling) -> int:
-    if subsampling not in SUBSAMPLING:
-        raise ValueError(f"subsampling is '4:2:0' or '4:4:4', got {subsampling!r}")
-    return SUBSAMPLING[subsampling]
-
-
-def _check_size(H, W):
-    if not (1 <= int(H) <= MAX_SIDE and 1 <= int(W) <= MAX_SIDE):
-        raise ValueError(f"1 <= H, W <= {MAX_SIDE}, got {H} x {W}")
 
 
 def quant_tables(quality: int):
@@ -78,13 +63,7 @@ def quant_tables(quality: int):
 
 def huffman_codes(bits, vals):
     """Annex C: symbol -> (code, length) of the table with ``bits[l - 1]`` codes of length l over ``vals``."""
-    out, code, k = {}, 0, 0
-    for length in range(1, 17):
-        for _ in range(bits[length - 1]):
-            out[vals[k]] = (code, length)
-            code, k = code + 1, k + 1
-        code <<= 1
-    return out
+    return {vals[k + i]: (code + i, length) for length, (code, n, k) in enumerate(code_ranges(bits), 1) for i in range(n)}
 
 
 def _code_arrays(bits, vals):
@@ -98,24 +77,11 @@ _DC = (_code_arrays(DC_LUMA_BITS, DC_VALS), _code_arrays(DC_CHROMA_BITS, DC_VALS
 _AC = (_code_arrays(AC_LUMA_BITS, AC_LUMA_VALS), _code_arrays(AC_CHROMA_BITS, AC_CHROMA_VALS))
 
 
-def block_count(H, W, subsampling="4:2:0") -> int:
-    """Blocks of one frame's scan: 3 per 8 x 8 MCU at 4:4:4, 6 per 16 x 16 MCU at 4:2:0."""
-    _check_size(H, W)
-    m = 8 * _sub(subsampling)
-    return -(-int(H) // m) * -(-int(W) // m) * (3 if m == 8 else 6)
-
-
-def block_components(H, W, subsampling="4:2:0") -> np.ndarray:
-    """int64 [nblk]: 0 (Y), 1 (Cb) or 2 (Cr) for every block in scan order."""
-    per = (0, 1, 2) if _sub(subsampling) == 1 else (0, 0, 0, 0, 1, 2)
-    return np.tile(np.asarray(per, np.int64), block_count(H, W, subsampling) // len(per))
-
-
 # ---- stages -------------------------------------------------------------------------------------------------------------
 def _frames(frames_u8):
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3 or frames_u8.shape[0] < 1:
         raise ValueError(f"frames are uint8 [B,H,W,3] with B >= 1, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-    _check_size(frames_u8.shape[1], frames_u8.shape[2])
+    check_size(frames_u8.shape[1], frames_u8.shape[2])
     return frames_u8
 
 
@@ -127,11 +93,10 @@ def planes_torch(frames_u8, subsampling="4:2:0"):
     + 128`` (the JFIF matrix in 16 fraction bits, the shift an arithmetic one; the half less one keeps 0..255 without a
     clamp); the last row and column are repeated up to the MCU multiple; 4:2:0 chroma is ``(a + b + c + d + 2) >> 2``
     of the 2 x 2 full-resolution Cb / Cr values."""
-    s = _sub(subsampling)
+    s = sub_of(subsampling)
     x = _frames(frames_u8).to(torch.int64)
     B, H, W, _ = x.shape
-    m = 8 * s
-    Hp, Wp = -(-H // m) * m, -(-W // m) * m
+    Hp, Wp = (8 * s * n for n in mcu_grid(H, W, s))
     rows = torch.arange(Hp, device=x.device).clamp(max=H - 1)
     cols = torch.arange(Wp, device=x.device).clamp(max=W - 1)
     x = x[:, rows][:, :, cols]
@@ -144,11 +109,6 @@ def planes_torch(frames_u8, subsampling="4:2:0"):
     return Y, Cb, Cr
 
 
-def _blocks(plane):
-    B, h, w = plane.shape
-    return plane.view(B, h // 8, 8, w // 8, 8).permute(0, 1, 3, 2, 4)          # [B, by, bx, 8, 8]
-
-
 def coefficients_torch(frames_u8, quality=90, subsampling="4:2:0"):
     """-> int16 [B, nblk, 64]: the quantised DCT coefficients in zig-zag order, the blocks in scan order (per MCU its Y
     blocks row by row, Cb, Cr).
@@ -156,13 +116,7 @@ def coefficients_torch(frames_u8, quality=90, subsampling="4:2:0"):
     With X the block minus 128 and Q = ``DCT_Q14``: rows ``T = (X Q^T + 512) >> 10``, columns ``U = Q T`` (the
     orthonormal DCT times 2^18), ``coef = sign(U) ((|U| + (q << 17)) // (q << 18))``: division by the table entry q,
     halves away from zero.  Every intermediate fits 32 bits; integer sums do not depend on their order."""
-    s = _sub(subsampling)
-    Y, Cb, Cr = planes_torch(frames_u8, subsampling)
-    B = Y.shape[0]
-    Yb, Cbb, Crb = _blocks(Y), _blocks(Cb), _blocks(Cr)
-    my, mx = Cbb.shape[1], Cbb.shape[2]
-    Yb = Yb.reshape(B, my, s, mx, s, 8, 8).permute(0, 1, 3, 2, 4, 5, 6).reshape(B, my * mx, s * s, 8, 8)
-    X = torch.cat([Yb, Cbb.reshape(B, my * mx, 1, 8, 8), Crb.reshape(B, my * mx, 1, 8, 8)], 2).reshape(B, -1, 8, 8) - 128
+    X = blocks_from_planes(*planes_torch(frames_u8, subsampling), sub_of(subsampling)) - 128
     Q = torch.tensor(DCT_Q14, dtype=torch.int64, device=X.device)
     T = (X @ Q.t() + 512) >> 10
     U = Q @ T
@@ -171,7 +125,7 @@ def coefficients_torch(frames_u8, quality=90, subsampling="4:2:0"):
     q = torch.where((comp == 0)[:, None, None], luma, chroma)
     coef = torch.sign(U) * ((U.abs() + (q << 17)) // (q << 18))
     zz = torch.tensor(ZIGZAG, device=X.device)
-    return coef.reshape(B, -1, 64)[:, :, zz].to(torch.int16)
+    return coef.reshape(X.shape[0], -1, 64)[:, :, zz].to(torch.int16)
 
 
 def _size(mag):
@@ -192,13 +146,12 @@ def scan_torch(coef, subsampling="4:2:0", H=None, W=None):
     codes, MSB first, 0xFF followed by 0x00, the last byte filled with ones.  Counters: ``zrl`` symbols, ``stuffed``
     bytes, ``dc_size`` and ``ac_size`` the largest categories, ``bits`` before the fill.  The block-to-component map
     follows from the block count and ``subsampling`` alone (``H``, ``W`` are not needed)."""
-    s = _sub(subsampling)
+    per = MCU_COMPONENTS[sub_of(subsampling)]
     c = np.asarray(coef.cpu() if torch.is_tensor(coef) else coef).astype(np.int64)
     nblk = c.shape[0]
-    per = 3 if s == 1 else 6
-    if c.ndim != 2 or c.shape[1] != 64 or nblk % per:
-        raise ValueError(f"coef is [nblk, 64] with nblk a multiple of {per}, got {c.shape}")
-    comp = np.tile(np.asarray((0, 1, 2) if s == 1 else (0, 0, 0, 0, 1, 2)), nblk // per)
+    if c.ndim != 2 or c.shape[1] != 64 or nblk % len(per):
+        raise ValueError(f"coef is [nblk, 64] with nblk a multiple of {len(per)}, got {c.shape}")
+    comp = np.tile(np.asarray(per), nblk // len(per))
     tab = (comp > 0).astype(np.int64)                                           # Huffman table of the block
 
     # DC differences
@@ -275,8 +228,8 @@ def _segment(marker, body):
 
 def header_bytes(H, W, quality=90, subsampling="4:2:0") -> bytes:
     """SOI, JFIF APP0 (1.01, aspect 1:1), the luma and chroma DQT (zig-zag order), SOF0, the four Annex K DHT, SOS."""
-    _check_size(H, W)
-    s = _sub(subsampling)
+    check_size(H, W)
+    s = sub_of(subsampling)
     luma, chroma = quant_tables(quality)
     zz = np.asarray(ZIGZAG)
     out = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
@@ -322,9 +275,9 @@ class JpegEncoder(DeviceOperator):
     needs.  ``encode_bytes`` encodes such a chunk again at ``max_bytes``."""
 
     def __init__(self, H, W, device, quality=90, subsampling="4:2:0", max_batch=None, capacity=None):
-        _check_size(H, W)
+        check_size(H, W)
         self.H, self.W, self.quality, self.subsampling = int(H), int(W), int(quality), subsampling
-        self.sub = _sub(subsampling)
+        self.sub = sub_of(subsampling)
         quant_tables(quality)
         self.header = header_bytes(H, W, quality, subsampling)
         self.max_bytes = max_bytes(H, W, subsampling)
@@ -448,7 +401,7 @@ class AviWriter:
     2^31 - 2^20 bytes (``AVI_LIMIT``), index included."""
 
     def __init__(self, path, H, W, fps=25, audio=None, rate=16000):
-        _check_size(H, W)
+        check_size(H, W)
         self.H, self.W, self.rate = int(H), int(W), int(rate)
         self.fps_rate, self.fps_scale = _fps_ratio(fps)
         self.audio = None if audio is None else pcm16(audio)
@@ -571,21 +524,11 @@ def read_avi(path, decoder=None):
     if fps is None or not frames:
         raise ValueError(f"{path}: no video stream or no frame")
     sound = torch.from_numpy(np.concatenate(audio).astype(np.float32) / 32768.0) if audio else None
-    pixels = None
-    if decoder is not None:
-        from .jpeg_decode import UnsupportedJpeg, parse_jpeg
-        try:
-            infos = [parse_jpeg(f) for f in frames]
-            if len({(i.H, i.W, i.subsampling) for i in infos}) == 1:
-                pixels = torch.cat([decoder.decode_checked(frames[i:i + MAX_BATCH], infos[i:i + MAX_BATCH])
-                                    for i in range(0, len(frames), MAX_BATCH)])
-        except UnsupportedJpeg:
-            pass
-    if pixels is None:
-        pixels = torch.from_numpy(np.stack([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in frames]))
-        if decoder is not None:
-            pixels = pixels.to(decoder.device)
-    return pixels, fps, sound
+    got = decoder.decode_uniform(frames) if decoder is not None else None
+    if got is not None:
+        return got[0], fps, sound
+    pixels = torch.from_numpy(np.stack([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in frames]))
+    return pixels if decoder is None else pixels.to(decoder.device), fps, sound
 
 
 class VideoWriter:
